@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py - synthesized frames/s of the per-frame path (run_imitator, 512x512, AttLWB-SPADE fp32) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]      (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps, writes the last step's video to DIR (--dump-outputs) and prints the line: ``value``,
+``ms_per_step`` and the configuration.  Everything else below (conv-launch events and the roofline, the self-check, the uint8-exchange
+loop, the separately reported measurements, the CPU baseline) runs only with ``--full``.
 
 Workload (all N): ONE source/reference pair, a ``--frames``-frame reference clip (300: BASELINE.json configs[2]; the same clip on
 one GPU is configs[1]).  A step = one pass of the hot path (camera swap, SMPL-H skinning, projection +
@@ -713,6 +717,27 @@ def shard_of_8(im, tgt, n_clip, reps=6):
                 pass
 
 
+DUMP_BYTES = 56 << 20          # the frame sample of --dump-outputs (the whole 300-frame 512x512 clip is 944 MB)
+
+
+def dump_outputs(video, out_dir):
+    """--dump-outputs: what a caller of the timed path receives, as float32 / float64 .npy files - a sample of frames drawn with a fixed
+    seed (``video_frames``, as many as fit DUMP_BYTES, at least one), their indices in the clip (``video_frame_index``) and the mean of
+    every frame of the clip in float64 (``video_frame_mean``).  The same arguments give the same inputs, so two builds compare file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = video.shape[0]
+    per_frame = max(1, video[0].numel() * 4)
+    k = max(1, min(n, DUMP_BYTES // per_frame))
+    idx = np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+    frames = video[torch.as_tensor(idx, device=video.device)].float().cpu().numpy()
+    if frames.nbytes > DUMP_BYTES:           # one frame alone above the budget: a seeded sample of its elements
+        flat = frames.reshape(-1)
+        frames = flat[np.sort(np.random.RandomState(1).choice(flat.size, DUMP_BYTES // 4, replace=False))]
+    np.save(os.path.join(out_dir, "video_frames.npy"), np.ascontiguousarray(frames, dtype=np.float32))
+    np.save(os.path.join(out_dir, "video_frame_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "video_frame_mean.npy"), video.reshape(n, -1).mean(1, dtype=torch.float64).cpu().numpy())
+
+
 def _extra(fn, *a, **kw):
     """A separately reported measurement must never take the headline line with it: an exception becomes {"error": ...}."""
     try:
@@ -725,14 +750,8 @@ def _extra(fn, *a, **kw):
         return {"error": f"{type(e).__name__}: {e}"[:500]}
 
 
-def main(argv=None):
-    import faulthandler
-    faulthandler.enable()                    # a crash inside a native library leaves a Python traceback on stderr
-    # ONE JSON line on stdout, whatever the libraries print (RCCL writes its version banner to stdout when a communicator is created): file
-    # descriptor 1 points at stderr for the whole run, the line goes to the saved descriptor at the end
-    sys.stdout.flush()
-    real_stdout = os.dup(1)
-    os.dup2(2, 1)
+def parse_args(argv=None):
+    """The command line, with what a plain run (no --full) leaves out already switched off."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -761,7 +780,7 @@ def main(argv=None):
                     help="N > 1: the chunk schedule of a rank's shard.  batches: frame batches of --frame-batch, each exchanged behind the next one's "
                          "synthesis (38 frames -> 24 + 14); one: the shard as ONE chunk (no launch set cut, the exchange exposed); auto: whichever the "
                          "ring model of sharding.choose_chunk_plan predicts faster from this run's measured per-frame time")
-    ap.add_argument("--cpu-frames", type=int, default=3, help="frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="frames of the CPU baseline sample (0 = skip; default: 3 with --full, else 0)")
     ap.add_argument("--precision", choices=("fp32", "bf16", "split", "winograd"), default="winograd",
                     help="bf16: BASELINE configs[3] mode - bf16 MFMA operands and bf16 activation storage in the convs (fp32 accumulation); "
                          "the headline metric (configs[1]) is fp32")
@@ -783,7 +802,33 @@ def main(argv=None):
     ap.add_argument("--lab-no-wino4", action="store_true", help="lab A/B: the F(4x4,3x3) kernel off (every eligible 3x3 layer on the F(2x2,3x3) kernel, rounds 5-6's engine)")
     ap.add_argument("--no-sizes-extra", dest="sizes_extra", action="store_false")
     ap.add_argument("--no-exchange-u8", dest="exchange_u8", action="store_false", help="N > 1 with the f32 exchange: skip the extra uint8-exchange loop")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: HIP events around every conv launch of the timed steps (roofline), the "
+                         "self-check, the uint8-exchange loop (N > 1), the separately reported measurements, the CPU baseline and the "
+                         "configuration stamp for tools/pmc_summary.py.  Without it a run does set-up, warm-up, the timed steps, "
+                         "--dump-outputs and the result line; --conv-breakdown, --only-extras and --cpu-frames N still ask for their own item")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, < 64 MB): a "
+                         "fixed seeded sample of the video's frames, their indices and every frame's mean")
     args = ap.parse_args(argv)
+    if args.cpu_frames is None:
+        args.cpu_frames = 3 if args.full else 0
+    if not args.full:            # a plain run: only what the headline needs, unless an item is asked for by name
+        args.no_conv_events = args.no_conv_events or not args.conv_breakdown
+        args.self_check = args.exchange_u8 = False
+        args.extras = args.extras and bool(args.only_extras)
+    return args
+
+
+def main(argv=None):
+    import faulthandler
+    faulthandler.enable()                    # a crash inside a native library leaves a Python traceback on stderr
+    # ONE JSON line on stdout, whatever the libraries print (RCCL writes its version banner to stdout when a communicator is created): file
+    # descriptor 1 points at stderr for the whole run, the line goes to the saved descriptor at the end
+    sys.stdout.flush()
+    real_stdout = os.dup(1)
+    os.dup2(2, 1)
+    args = parse_args(argv)
     self_launch_if_needed(sys.argv[1:] if argv is None else argv)      # N > 1 without torchrun: spawn the ranks ourselves
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -838,7 +883,7 @@ def main(argv=None):
     if args.precision != "winograd":                          # the sources were encoded in the default mode: again in this one
         im.set_source(case.src_smpl, case.uv_img, case.bg_img, src_img=case.src_img)
     FB_requested, FB = FB, im.frame_batch        # (no clamp any more: batches beyond the kernels' 3 GiB buffer range are sliced inside the C entry points)
-    if rank == 0:                                                # what tools/pmc_summary.py stamps the PMC traffic file with
+    if rank == 0 and args.full:                                  # what tools/pmc_summary.py stamps the PMC traffic file with
         try:
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "bench_last_config.json"), "w") as fp:
@@ -916,6 +961,8 @@ def main(argv=None):
     dt = time.perf_counter() - t0
     timer.enabled = False
     assert last.shape[0] == frames_per_step and bool(torch.isfinite(last.float()).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
 
     # self-check, outside the timed region: 8 frames spread over the clip rendered again ONE frame per launch (the reference's calling
     # convention, imitator.py:341) must equal the frames of the timed step bit for bit - every launch shape the timed loop used (full

@@ -47,8 +47,8 @@ def _run(tmp_path, extra, env_extra=None, launcher=None):
 
 def test_bench_self_launches_two_ranks_gloo(tmp_path):
     """Plain ``python <bench> --gpus 2`` (WORLD_SIZE unset): two ranks, a 7-frame clip in shards of 4 + 3; the headline exchanges the
-    fp32 (n,3,S,S) video (the result tensor of N = 1 and of the reference), the uint8 exchange is measured beside it."""
-    line = _run(tmp_path, ["--gpus", "2"])
+    fp32 (n,3,S,S) video (the result tensor of N = 1 and of the reference), the uint8 exchange is measured beside it (--full)."""
+    line = _run(tmp_path, ["--gpus", "2", "--full"])
     assert line["n_gpus"] == 2 and line["config"]["world_size"] == 2 and line["scaling"] == "strong"
     assert line["value"] > 0 and line["unit"] == "frames/s" and line["config"]["frames_per_step"] == 7
     per_rank = line["config"]["per_rank"]
@@ -90,6 +90,75 @@ def test_bench_single_process_line(tmp_path):
     line = _run(tmp_path, ["--gpus", "1"])
     assert line["n_gpus"] == 1 and line["config"]["world_size"] == 1 and "per_rank" not in line["config"]
     assert line["config"]["frame_batch"] == 2 and line["config"]["frame_batch_requested"] == 2
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run skips the self-check (the CPU plumbing run of the parent commit reported one); --dump-outputs writes the last
+    timed step's video sample as float32 / float64 .npy files, consistent with each other, and two runs with the same arguments write the
+    same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        line = _run(tmp_path, ["--gpus", "1", "--steps", "2", "--dump-outputs", str(d)])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "frames/s"
+        assert line["self_check"] is None and "self_check_detail" not in line
+        arrs = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert sorted(arrs) == ["video_frame_index", "video_frame_mean", "video_frames"]
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["video_frames"].shape == (7, 3, 64, 64) and arrs["video_frame_mean"].shape == (7,)
+        assert arrs["video_frame_index"].tolist() == list(range(7))
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20 and np.isfinite(arrs["video_frames"]).all()
+        assert np.allclose(arrs["video_frames"].astype(np.float64).mean((1, 2, 3)), arrs["video_frame_mean"], rtol=0, atol=1e-6)
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_plain_and_full_switches():
+    """What a plain run leaves out, independent of the device: conv events (the roofline), the self-check, the uint8-exchange loop, the
+    separately reported measurements, the CPU baseline - each back with --full, or alone when asked for by name."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.no_conv_events, a.self_check, a.exchange_u8, a.extras, a.cpu_frames) == (False, True, False, False, False, 0)
+    assert (a.steps, a.warmup, a.dump_outputs) == (3, 1, None)
+    a = bench.parse_args(["--full"])
+    assert (a.full, a.no_conv_events, a.self_check, a.exchange_u8, a.extras, a.cpu_frames) == (True, False, True, True, True, 3)
+    a = bench.parse_args(["--full", "--no-conv-events", "--no-self-check", "--no-extras", "--cpu-frames", "0"])
+    assert (a.no_conv_events, a.self_check, a.extras, a.cpu_frames) == (True, False, False, 0)
+    a = bench.parse_args(["--conv-breakdown", "--only-extras", "b1_latency", "--cpu-frames", "2"])
+    assert (a.no_conv_events, a.self_check, a.extras, a.cpu_frames) == (False, False, True, 2)
+    assert bench.parse_args(["--conv-breakdown", "--no-conv-events"]).no_conv_events
+
+
+def test_bench_dump_outputs_sampling(tmp_path, monkeypatch):
+    """dump_outputs on a clip larger than its budget: a seeded sample of whole frames (the same one every time) whose indices, frames and
+    per-frame means agree with the clip; a uint8 video (the u8 exchange) as float32; one frame above the budget: a seeded element sample."""
+    import numpy as np
+    import torch
+    import bench
+    video = torch.tensor(np.random.RandomState(3).uniform(-1, 1, (40, 3, 8, 8)).astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 3 * 8 * 8 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(video, str(tmp_path / d))
+    got = {f: np.load(tmp_path / "a" / f"{f}.npy") for f in ("video_frames", "video_frame_index", "video_frame_mean")}
+    idx = got["video_frame_index"].astype(np.int64)
+    assert got["video_frames"].dtype == np.float32 and got["video_frame_index"].dtype == got["video_frame_mean"].dtype == np.float64
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and idx.max() < 40 and idx.tolist() != list(range(10))
+    assert np.array_equal(got["video_frames"], video.numpy()[idx])
+    assert np.allclose(got["video_frame_mean"], video.double().reshape(40, -1).mean(1).numpy(), rtol=0, atol=1e-12)
+    assert np.allclose(got["video_frame_mean"][idx], got["video_frames"].astype(np.float64).mean((1, 2, 3)), rtol=0, atol=1e-12)
+    for f, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{f}.npy")), f
+    u8 = (video.permute(0, 2, 3, 1) * 100 + 120).to(torch.uint8)            # (n,S,S,3) uint8
+    bench.dump_outputs(u8, str(tmp_path / "u8"))
+    fr = np.load(tmp_path / "u8" / "video_frames.npy")
+    assert fr.dtype == np.float32 and np.array_equal(fr, u8.numpy()[np.load(tmp_path / "u8" / "video_frame_index.npy").astype(np.int64)])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 400)                         # below one frame (192 floats = 768 bytes)
+    bench.dump_outputs(video, str(tmp_path / "el"))
+    fr = np.load(tmp_path / "el" / "video_frames.npy")
+    one = video.numpy()[int(np.load(tmp_path / "el" / "video_frame_index.npy")[0])].reshape(-1)
+    assert fr.shape == (100,) and fr.nbytes <= 400 and np.isin(fr, one).all()
 
 
 # the training graph's CUDA-only guards (ConvFn.forward etc.) are answered "yes" for CPU tensors, as tests/test_abi_and_sharding.py's

@@ -9,7 +9,7 @@ import subprocess
 
 steps = sys.argv[1] if len(sys.argv) > 1 else "4"
 code = ("import sys; sys.path.insert(0, %r); from ipercore_amd import ops; ops.BF16_UP4_HEAD = %s; import bench; "
-        "bench.main(['--precision', 'bf16', '--size', '1024', '--workload', 'novel_view', '--steps', %r, '--warmup', '2', '--no-extras', '--cpu-frames', '0'])")
+        "bench.main(['--precision', 'bf16', '--size', '1024', '--workload', 'novel_view', '--steps', %r, '--warmup', '2', '--full', '--no-extras', '--cpu-frames', '0'])")
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for rep in range(2):
     for fused in (False, True):

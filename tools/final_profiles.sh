@@ -13,7 +13,7 @@ if [[ " $WHAT " == *" pytest "* ]]; then
   timeout 1500 python -m pytest tests -q -m gpu --durations=8 2>&1 | tail -30 > $O/pytest_gpu.log; echo "pytest exit=${PIPESTATUS[0]}"; tail -4 $O/pytest_gpu.log
 fi
 if [[ " $WHAT " == *" bench "* ]]; then
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit=$?"; head -c 300 $O/bench_final.json; echo
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench exit=$?"; head -c 300 $O/bench_final.json; echo
 fi
 if [[ " $WHAT " == *" prof "* ]]; then
   rm -rf $O/prof $O/prof_bf16

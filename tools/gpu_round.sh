@@ -26,10 +26,12 @@ if [[ " $WHAT " == *" pytest "* ]]; then
   timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -25 | tee gpurun_out/pytest_gpu.log
 fi
 if [[ " $WHAT " == *" bench "* ]]; then
+  # the headline line and the CPU baseline (asked for by --cpu-frames); BENCH_ARGS="--full ..." adds every separately reported measurement
   timeout 900 python bench.py ${BENCH_ARGS:---steps 6 --warmup 2 --cpu-frames 2} > gpurun_out/bench.log 2> gpurun_out/bench.err
   echo "bench exit=$?"; tail -3 gpurun_out/bench.log; tail -5 gpurun_out/bench.err
 fi
 if [[ " $WHAT " == *" prof "* ]]; then
+  # a plain bench run (no --full): the kernels of the headline's set-up, warm-up and timed steps only
   ( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/gpurun_out/prof" -o lwg -- python "$OLDPWD/bench.py" --steps 4 --warmup 2 --cpu-frames 0 --no-conv-events --pipelined-streams 0 --output-frames 0 --no-split-extra > "$OLDPWD/gpurun_out/prof_bench.log" 2>&1 )
   echo "prof exit=$?"; find gpurun_out/prof -name "*stats*" | head; 
   f=$(find gpurun_out/prof -name "*kernel_stats*" | head -1); [ -n "$f" ] && head -25 "$f"
