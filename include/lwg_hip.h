@@ -188,6 +188,15 @@ int lwg_conv_transpose4_is_one_grid(const LwgConvArgs* args);
  * mode of ipercore_amd.ops; a frame's result does not depend on the batch it is launched in. */
 int lwg_conv_transpose4_winograd_f32(const LwgConvArgs* args, lwg_stream_t stream);
 
+/* The same layer as a fused F(2x4, 2x2) Winograd convolution (csrc/convt_winograd24.hip): F(2, 2) along rows, F(4, 2) with the points
+ * {0, 1, -1, 1/2, inf} along columns - 15 multiplies per 2 x 4 outputs of a parity instead of 18 (F(2x2, 2x2)) or 32 (direct).  The contract of
+ * lwg_conv_transpose4_winograd_f32 above, EXCEPT args->w = the panel Upk[4][Cin/8][4][2][15 N] (240 Cin N bytes) - per (parity 2 py + px, s, kk, kh)
+ * [N][4] products 0-3, [N][4] products 4-7, [N] product 8, [N][4] products 9-12, [N] product 13, [N] product 14; product 3 xi + nu (nu < 3) or
+ * 9 + 2 xi + nu - 3 (nu >= 3) of column n = sgn (G_y g G_x^T)[xi][nu] for input channel 8 s + 2 kk + kh, g as above, G_y = [[1,0],[1,1],[0,1]],
+ * G_x = [[1,0],[1/2,1/2],[-1/6,1/6],[-8/3,-4/3],[0,1/2]], sgn = (py == 1 && xi == 0 ? -1 : 1); formed in fp64 and rounded once (ops._wwino_t24).
+ * fp32-grade results, neither the direct forms' bits nor those of lwg_conv_transpose4_winograd_f32; a frame's result does not depend on its batch. */
+int lwg_conv_transpose4_winograd24_f32(const LwgConvArgs* args, lwg_stream_t stream);
+
 /* fp32 convolution on the bf16 matrix pipe ("bf16x6"): both operands are split exactly into three bf16 parts
  * (activations in the kernel, weights on the host: args->w = [3][ntaps*Cin/8][N][8] bf16 planes hi / mid / lo), six bf16 MFMAs
  * per fp32 product, fp32 accumulation; dropped terms < 2^-23 |a b|.  Same contract and restrictions as the bf16 entry point. */

@@ -69,7 +69,7 @@ def _stream():
 
 class ConvSpec:
     """Host description of one packed convolution (weights already in the kernel's layout)."""
-    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_w16v2", "_w16hr", "_w16x3", "_w16c8", "_w16up", "_w32up", "_wwino", "_wwino_t", "_wwino4")
+    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_w16v2", "_w16hr", "_w16x3", "_w16c8", "_w16up", "_w32up", "_wwino", "_wwino_t", "_wwino_t24", "_wwino4")
 
     def __init__(self, w, bias, N, Cin, taps, stride=1, omul=1, ooy=0, oox=0, algo_kn=None):
         self.w, self.bias, self.N, self.Cin = w, bias, int(N), int(Cin)
@@ -87,6 +87,7 @@ class ConvSpec:
         self._w32up = None
         self._wwino = None
         self._wwino_t = None
+        self._wwino_t24 = None
         self._wwino4 = None
         self.cshift = 0
         if self.Cin % 32 != 0:
@@ -439,6 +440,57 @@ def _wwino_t(specs):
     return U
 
 
+# F(4, 2) along the columns of the F(2x4, 2x2) kernel (csrc/convt_winograd24.hip): the points {0, 1, -1, 1/2, inf}, the scale factors of its data
+# transform moved here so that the kernel's B^T has the entries 0, +-1, +-2, -3 only (tools/convt_tile_study.py)
+_G_X24 = ((1.0, 0.0), (0.5, 0.5), (-1.0 / 6.0, 1.0 / 6.0), (-8.0 / 3.0, -4.0 / 3.0), (0.0, 0.5))
+
+
+def _wwino_t24(specs):
+    """The transformed-weight panel of lwg_conv_transpose4_winograd24_f32 from the four parity GEMM panels, built once per layer:
+    Upk[4][Cin/8][4][2][15 N] - per (parity 2 py + px, s, kk, kh) [N][4] products 0-3, [N][4] products 4-7, [N] product 8, [N][4] products 9-12,
+    [N] product 13, [N] product 14 (every load of the kernel reads contiguous memory).  Product 3 xi + nu (nu < 3) / 9 + 2 xi + nu - 3 (nu >= 3) of column n =
+    sgn (G_y g G_x^T)[xi][nu] for input channel 8 s + 2 kk + kh, g the parity's 2 x 2 sub-kernel in input-offset order, G_y = [[1,0],[1,1],[0,1]],
+    G_x = _G_X24, sgn = -1 for the parity-1 row form the parity-0 one already holds negated (xi = 0, py = 1); formed in fp64 and rounded once."""
+    s0 = specs[0]
+    U = s0._wwino_t24
+    if U is not None and U.device == s0.w.device:
+        return U
+    Cin, N = s0.Cin, s0.N
+    Gy = torch.tensor([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=torch.float64, device=s0.w.device)
+    Gx = torch.tensor(_G_X24, dtype=torch.float64, device=s0.w.device)
+    parts = []
+    for par, sp in enumerate(specs):
+        py, px = par >> 1, par & 1
+        W = sp.w.double().permute(0, 2, 1).reshape(4 * Cin, N)                  # rows k = ((c / 32) 4 + tap) 32 + c % 32
+        W = W.view(Cin // 32, 4, 32, N).permute(1, 0, 2, 3).reshape(4, Cin, N)  # [tap][c][n]
+        g = torch.zeros(2, 2, Cin, N, dtype=torch.float64, device=W.device)
+        for t, (dy, dx) in enumerate(zip(sp.dy, sp.dx)):
+            g[dy - (py - 1), dx - (px - 1)] = W[t]                               # g[r][q] multiplies x[i + py - 1 + r][j + px - 1 + q]
+        u = torch.einsum("ar,rqcn,bq->abcn", Gy, g, Gx)                        # (3, 5, Cin, N)
+        if py:
+            u[0] = -u[0]
+        parts.append(torch.cat([u[:, :3].reshape(9, Cin, N), u[:, 3:].reshape(6, Cin, N)]))
+    U15 = torch.stack(parts).float()                                             # (4, 15, Cin, N)
+    quad = lambda lo, hi: U15[:, lo:hi].permute(0, 2, 3, 1).reshape(4, Cin, (hi - lo) * N)     # noqa: E731
+    U = torch.cat([quad(0, 4), quad(4, 8), U15[:, 8], quad(9, 13), U15[:, 13], U15[:, 14]], dim=2)
+    U = U.view(4, Cin // 8, 4, 2, 15 * N).contiguous()                           # c = 8 s + 2 kk + kh
+    s0._wwino_t24 = U
+    return U
+
+
+WINO_UP4_24 = True          # lab switch: the synthesis path's eligible transposed convolutions run the F(2x4, 2x2) kernel (False: F(2x2, 2x2))
+# ... for images of at least this many input pixels; smaller launches keep F(2x2, 2x2).  NOT a measured crossover: the bound is set so that the
+# shapes tests/gpu_checks.py::check_winograd_up4 pins to lwg_conv_transpose4_winograd_f32's bits (<= 48 x 64 input pixels) keep that kernel, while
+# the 512 x 512 decoder's three layers (64^2, 128^2, 256^2 inputs, where both kernels were timed) take the new one.  The 256 x 256 pipeline's
+# first layer (32^2) stays on F(2x2, 2x2) untimed against F(2x4, 2x2); tests/test_gpu_convt_winograd24.py runs the new kernel on the small shapes.
+WINO_UP4_24_MIN_HW = 64 * 64
+
+
+def _up4_24(x):
+    """Whether a "winograd"-mode transposed convolution of x (B, H, W, Cin) runs lwg_conv_transpose4_winograd24_f32."""
+    return WINO_UP4_24 and x.shape[1] * x.shape[2] >= WINO_UP4_24_MIN_HW
+
+
 class _FusedTransposeSpec(object):
     """What a launch-accounting hook (bench.ConvTimer) sees for the fused transposed convolution: per INPUT pixel 16 taps and 4 N
     outputs; flops = 2 M algo_kn, bytes = M Cin in + 4 M N out + the four panels."""
@@ -476,13 +528,18 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
             and s0.Cin % 32 == 0 and s0.N % 32 == 0 and _parity_specs_ok(specs)):
         # the synthesis path in the "winograd" mode: the layer as ONE fused F(2x2, 2x2) Winograd launch (36 products per 4 x 4 input patch instead
         # of 64; per-image work in a fixed order: a frame does not depend on its batch).  Training callers (splitk=True) keep the direct forms.
+        # Images of >= WINO_UP4_24_MIN_HW input pixels: F(2x4, 2x2) (60 products per 2 x 4 input patch instead of 72).
         a = conv_args(x, s0, y, act=act, q4=q4)
-        panel = _wwino_t(specs)
+        f24 = _up4_24(x)
+        panel = _wwino_t24(specs) if f24 else _wwino_t(specs)
         a.w = _ptr(panel)
         if CONV_HOOK is not None:
             whole = _FusedTransposeSpec(s0, panel)
             CONV_HOOK(True, a.M, whole, EPI_NONE, None)
-        _lib.check(_lib.lib().lwg_conv_transpose4_winograd_f32(a, _stream()), "lwg_conv_transpose4_winograd_f32")
+        if f24:
+            _lib.check(_lib.lib().lwg_conv_transpose4_winograd24_f32(a, _stream()), "lwg_conv_transpose4_winograd24_f32")
+        else:
+            _lib.check(_lib.lib().lwg_conv_transpose4_winograd_f32(a, _stream()), "lwg_conv_transpose4_winograd_f32")
         if CONV_HOOK is not None:
             _hook_end(a, whole, EPI_NONE, "winograd_up4", False)
         return y
