@@ -463,7 +463,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
         const int lx = tide & 31, cq = (tide >> 5) & 7, lyh = tide >> 8;
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * (size_t)(a.YC >> 2) * plane * 4, 0,
                                                                             (int)((unsigned)(a.YC >> 2) * (unsigned)plane * 16u), 0x00020000);
-        const unsigned yv = ox0 + lx < a.YW ? (unsigned)(((((a.ycoff + en0) >> 2) + cq) * (int)plane + (oy0 + lyh) * a.YW + ox0 + lx) * 16) : WINO_OOB;
+        const unsigned yv = ox0 + lx < a.YW ? (unsigned)((((a.ycoff + en0) >> 2) + cq) * (int)plane + (oy0 + lyh) * a.YW + ox0 + lx) * 16u : WINO_OOB;
         const float* src = smem + (lyh * 32 + ctw_slot(lx)) * OROW + 4 * cq;
         const unsigned rowpair = (unsigned)a.YW * 32u;           // bytes between the rows of two passes (two rows of 16-byte pixels)
 #pragma unroll
@@ -478,9 +478,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
         // NHWC: 8 lanes = the block's 32 channels of one pixel, 128 contiguous bytes
         const int cq = tide & 7, lx = (tide >> 3) & 31, lyh = tide >> 8;
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * plane * a.YC, 0, (int)((unsigned)plane * (unsigned)a.YC * 4u), 0x00020000);
-        const unsigned yv = ox0 + lx < a.YW ? (unsigned)((((oy0 + lyh) * a.YW + ox0 + lx) * a.YC + a.ycoff + en0 + 4 * cq) * 4) : WINO_OOB;
+        const bool in_x = ox0 + lx < a.YW;
+        const unsigned yv = in_x ? (unsigned)(((oy0 + lyh) * a.YW + ox0 + lx) * a.YC + a.ycoff + en0 + 4 * cq) * 4u : WINO_OOB;
         const float* src = smem + (lyh * 32 + ctw_slot(lx)) * OROW + 4 * cq;
-        const unsigned rowpair = (unsigned)a.YW * (unsigned)a.YC * 8u;
+        // right of the image every pass keeps the marker: added to it, the pass offsets wrapped past 2^32 into the image once 15 rowpair
+        // reached 1 GiB (tests/test_conv_offsets_cpu.py); rows below the image lie beyond the buffer's end (host: 32 rows of slack)
+        const unsigned rowpair = in_x ? (unsigned)a.YW * (unsigned)a.YC * 8u : 0u;
 #pragma unroll
         for (int pass = 0; pass < 16; ++pass) {
             const ctw_u4 v = *reinterpret_cast<const ctw_u4*>(src + pass * 64 * OROW);
