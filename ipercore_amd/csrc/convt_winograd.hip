@@ -19,7 +19,7 @@
 // and rounded once.  fp32-grade, NOT the direct kernel's bits: part of the "winograd" precision mode.
 #include <hip/hip_runtime.h>
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_convt_wino.h"       // the block footprint, the block walk, the halo staging, the store phase and the launch (shared with convt_winograd24.hip)
 
 #ifndef CTW_NT_ST
 #define CTW_NT_ST 0          // cache policy of the output stores: 0 = default; 2 = non-temporal - worth 0.5 % in conv_winograd4.hip, measured neutral here (profiles/r06_az_*)
@@ -27,24 +27,9 @@
 #ifndef LWG_CTW_XCD
 #define LWG_CTW_XCD 1        // XCD-aware block order (see the kernel): 0 = column-block-major (lab)
 #endif
-#define WG_THREADS 512
-#define TPB 8            // patches per block edge: 8 x 8 patches = 16 x 16 input pixels
-#define NPATCH 64
-#define NBT 32           // output channels per block
-#define KS 8             // input channels per stage
-#define HALO 18
-#define PLANE (HALO * HALO)
-#define RAW_FLOATS (KS * PLANE)              // [c][py][px]
 #define VSTR 64
 #define NFORM 25
 #define VS_FLOATS (NFORM * KS * VSTR)        // [form][k][patch]
-#define DUMP_OFF (2 * RAW_FLOATS + 2 * VS_FLOATS)                 // where the threads without a halo element store their zeros (dead LDS)
-#define DUMP_FLOATS (WG_THREADS + 3 * PLANE + RAW_FLOATS)
-#define LOOP_FLOATS (DUMP_OFF + DUMP_FLOATS)
-#define OROW 36                              // floats per pixel row of the epilogue's exchange buffer [32 x 32 output pixels][32 channels + 4]
-#define OUT_FLOATS (32 * 32 * OROW)
-#define BIAS_OFF (LOOP_FLOATS > OUT_FLOATS ? LOOP_FLOATS : OUT_FLOATS)    // the block's 32 bias values, behind both uses of the LDS
-#define WINO_OOB 0xC0000000u                 // >= any image's byte size (host: H * W * C * 4 < 3 GiB): the buffer load returns 0
 // slot plan of the K loop (profiles/r05_h_convt_winograd_lab.txt, 64 frames, all three layers): first plan (patch reads and transform in one slot each,
 // barrier behind k-pair 2) 0.622 of the pipe; barrier in front of k-pair 2 0.644; barrier in the middle of k-pair 3 0.646; that + the patch reads and the
 // transform a few instructions per slot 0.650 = the product's plan.  -DCTW_LAB_BASE builds the first plan.
@@ -57,9 +42,6 @@
 #else
 #define WSB() __builtin_amdgcn_sched_barrier(0)
 #endif
-
-
-template <int V> struct IntT { static constexpr int value = V; };
 
 // lab instrumentation (compiled out of the product): tools/up4lab.py --ts on a -DLWG_CTW_TS variant library - every wave stamps kernel entry, K-loop
 // entry, K-loop exit and its end into args->res (four 64-bit stamps per wave)
@@ -88,21 +70,12 @@ __device__ __forceinline__ int ctw_slot(int lx) {
 #endif
 }
 
-__device__ __forceinline__ floatx4 ctw_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-
 __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const LwgConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int H = a.H, W = a.W, Cin = a.C0, N = a.N;
+    const int Cin = a.C0, N = a.N;
     float* const raw0 = smem;                                // [2][RAW], then [2][VS] (25 planes of [k][patch])
     const int tid = threadIdx.x, lane = tid & 63;
-    const int bx = (W + 2 * TPB - 1) / (2 * TPB), by = (H + 2 * TPB - 1) / (2 * TPB);
-    // persistent workgroups (round 6, as conv_winograd.hip): min(blocks, CUs) workgroups walk the block ids blockIdx.x + k gridDim.x (id = column block *
-    // tiles + tile); the next block's first halo stages and weights are requested inside this block's epilogue.  Bitwise the one-block-per-workgroup results.
-    const int tiles = bx * by * a.B;
-    const int total = tiles * (N / NBT);
     int blk = blockIdx.x;
     const int nst = Cin / KS;                                // even (host: Cin % 16 == 0)
     CTS(0);
@@ -110,62 +83,17 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
     const int par = wid & 3, py = par >> 1, px = par & 1;    // this wave's output parity
     const int pt = wid >> 2;                                  // ... and its 32-patch tile
     floatx16 acc[9];                                         // [product 3 xi + nu]
-    // ---- per-block state (workgroup-uniform): image b, tile corner (x0, y0), first output column n0, this image as a buffer; this thread's two halo
-    // elements (pixel, channel quad): byte offset of the pixel inside the image (out of range: padding / none); this lane's column of the panel
-    int b, x0, y0, n0;
-    __amdgpu_buffer_rsrc_t rx0;
-    unsigned voff0[2];
-    unsigned uvoff, uvoffc;                                  // this lane's column of the panel: the 16-byte parts, the ninth product
-    // XCD-aware block order (as conv_winograd4.hip; persistent grids of a multiple of 8 workgroups, N / 32 = 2, 4 or 8 column blocks): workgroup w runs on
-    // XCD w % 8 and keeps ONE column block, (w % 8) % ncb, for the whole launch (an XCD's L2 holds that column block's panel only), while the ncb
-    // workgroups (w % 8) / ncb, w / 8 of adjacent XCDs walk the same tile sequence in step: a tile's halo comes from HBM once instead of ncb times
-    const int ncb = N / NBT;
-    const bool xcd = LWG_CTW_XCD && (gridDim.x & 7u) == 0 && (ncb == 2 || ncb == 4 || ncb == 8) && (int)gridDim.x < total && tiles >= (int)gridDim.x / ncb;
-    const int xg = (int)gridDim.x / ncb;                     // workgroups per column block = tiles per round
-    const int xr = (int)(((blockIdx.x & 7u) / (unsigned)ncb) * (gridDim.x >> 3) + (blockIdx.x >> 3));      // this workgroup's place among them
-    auto has_block = [&](int id) -> bool {                   // (id = blockIdx.x + k gridDim.x)
-        return xcd ? (id / (int)gridDim.x) * xg + xr < tiles : id < total;
-    };
+    // the workgroup's walk over its blocks and the per-block state - image b, block corner (x0, y0), first output column n0, the halo elements
+    // (lwg_convt_wino.h) - and this lane's column of the panel: the 16-byte parts, the ninth product
+    CtwBlock<LWG_CTW_XCD != 0> bk(a, tid, DUMP_OFF);
+    unsigned uvoff, uvoffc;
     auto setup = [&](int id) {
-        int cb, t;
-        if (xcd) {
-            cb = (int)(blockIdx.x & 7u) & (ncb - 1);
-            t = __builtin_amdgcn_readfirstlane((id / (int)gridDim.x) * xg + xr);
-        } else {
-            cb = __builtin_amdgcn_readfirstlane(id / tiles);
-            t = __builtin_amdgcn_readfirstlane(id - cb * tiles);
-        }
-        b = __builtin_amdgcn_readfirstlane(t / (bx * by));
-        t -= b * bx * by;
-        x0 = (t % bx) * 2 * TPB;
-        y0 = (t / bx) * 2 * TPB;
-        n0 = cb * NBT;
-        rx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x0 + (size_t)b * H * W * Cin), 0, (int)((unsigned)(H * W) * (unsigned)Cin * 4u), 0x00020000);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = tid + WG_THREADS * q;
-            const int pix = i >> 1, half = i & 1, hy = pix / HALO, hx = pix - hy * HALO;
-            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const bool in = i < PLANE * 2 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            voff0[q] = in ? (unsigned)((gy * W + gx) * Cin + 4 * half) * 4u : WINO_OOB;
-        }
-        uvoff = (unsigned)(((lane >> 5) * 9 * N + 4 * (n0 + (lane & 31))) * 4);
-        uvoffc = (unsigned)(((lane >> 5) * 9 * N + 8 * N + n0 + (lane & 31)) * 4);
+        bk.setup(a, tid, id);
+        uvoff = (unsigned)(((lane >> 5) * 9 * N + 4 * (bk.n0 + (lane & 31))) * 4);
+        uvoffc = (unsigned)(((lane >> 5) * 9 * N + 8 * N + bk.n0 + (lane & 31)) * 4);
     };
     setup(blk);
-    int wst[2];                                              // the halo elements' LDS slot (threads without one store their zeros into dead LDS)
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = tid + WG_THREADS * q;
-        wst[q] = i < PLANE * 2 ? 4 * (i & 1) * PLANE + (i >> 1) : DUMP_OFF + tid;
-    }
     floatx4 rreg[2];
-    auto rld1 = [&](int st, int q) -> floatx4 { return ctw_buf_load(rx0, voff0[q], (unsigned)(st * KS) * 4u); };
-    auto rst1 = [&](int buf, int q, floatx4 v) {
-        float* dst = raw0 + buf * RAW_FLOATS + wst[q];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k * PLANE] = v[k];
-    };
     // weights: lane = (k-half lane / 32, channel lane % 32); element (parity, stage, k-pair, k-half) = 9 N floats: [N][4] products 0-3, [N][4] products 4-7,
     // [N] product 8 - every load instruction reads contiguous memory (as conv_winograd4.hip; the first layout, [N][12] with three of padding, made a
     // half-wave's 16-byte load span 1.5 KB for 512 useful bytes)
@@ -247,10 +175,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
         fragread(set, 1);
         WSB();
         mf(0, 0);
-        if (nxt) { rst1(set, 0, rreg[0]); rreg[0] = rld1(s3, 0); }
+        if (nxt) { bk.rst1(raw0, set, 0, rreg[0]); rreg[0] = bk.rld1(s3, 0); }
         WSB();
         mf(0, 1);
-        if (nxt) { rst1(set, 1, rreg[1]); rreg[1] = rld1(s3, 1); }
+        if (nxt) { bk.rst1(raw0, set, 1, rreg[1]); rreg[1] = bk.rld1(s3, 1); }
         WSB();
 #ifdef CTW_SPREAD                            // the patch reads and the transform a few instructions per MFMA slot
         float t[5][4];
@@ -351,11 +279,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
     float bq;                                                // the block's bias, one value per lane: requested with the first loads, parked in LDS by the
                                                              // prologue (read straight from global memory in the epilogue it was an exposed L2 round trip)
     auto issue_loads = [&]() {
-        bq = a.bias ? a.bias[n0 + (tid & 31)] : 0.f;
+        bq = a.bias ? a.bias[bk.n0 + (tid & 31)] : 0.f;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            r0[q] = rld1(0, q);
-            r1[q] = rld1(1, q);
+            r0[q] = bk.rld1(0, q);
+            r1[q] = bk.rld1(1, q);
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -363,7 +291,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
             ufr[1][j] = uld1(0, 1, j);
         }
 #pragma unroll
-        for (int q = 0; q < 2; ++q) rreg[q] = rld1(nst > 2 ? 2 : 1, q);
+        for (int q = 0; q < 2; ++q) rreg[q] = bk.rld1(nst > 2 ? 2 : 1, q);
     };
     issue_loads();
 #ifdef LWG_CTW_TS
@@ -373,8 +301,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
     CTSB(2, 10);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        rst1(0, q, r0[q]);
-        rst1(1, q, r1[q]);
+        bk.rst1(raw0, 0, q, r0[q]);
+        bk.rst1(raw0, 1, q, r1[q]);
     }
     if (tid < 32) smem[BIAS_OFF + tid] = bq;
     __syncthreads();
@@ -407,7 +335,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
     }
     CTS(2);
     CTSB(1, 5);
-    const int eb = b, ex0 = x0, ey0 = y0, en0 = n0;          // this block's coordinates (the state moves on to the next block below)
+    const int eb = bk.b, ex0 = bk.x0, ey0 = bk.y0, en0 = bk.n0;          // this block's coordinates (the state moves on to the next block below)
     // epilogue: Y[a][b] = sum over xi in {a, a + 1}, nu in {b, b + 1} of M[xi][nu] is register-local (this lane holds patch pt * 32 + lane % 32 and,
     // per register group g, the four channels 8 g + 4 (lane / 32) ..); + bias, activation; then ONE exchange through LDS - the block's 32 x 32 output
     // pixels x 32 channels, rows of 36 floats - so that the global stores are whole lines: written straight from the accumulator layout a lane's
@@ -445,51 +373,14 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
     // the last block re-requests its own first stages, nobody waits for them; see conv_winograd.hip)
     CTSB(1, 7);
     const int nblk = blk + (int)gridDim.x;
-    const bool more = has_block(nblk);
+    const bool more = bk.has_block(nblk);
     setup(more ? nblk : blk);
     issue_loads();
     CTSB(1, 8);
     __syncthreads();
     CTSB(1, 9);
-    const int oy0 = 2 * ey0, ox0 = 2 * ex0;
-    const size_t plane = (size_t)a.YH * a.YW;
-    // The block's 32 x 32 x 32 outputs leave as BUFFER stores (round 6): image eb is one buffer, a thread's offset inside it is computed once, the
-    // sixteen passes differ by one 32-bit add - no per-pass 64-bit address arithmetic, no per-pass bounds branch (profiles/r06_m_*: the store phase was
-    // 4.2-5.4 k cycles of instruction issue per block).  Pixels right of the image: an out-of-range thread offset (the store is dropped); rows below it:
-    // beyond the buffer's end in the NHWC layout (rows are its slowest dimension), an out-of-range scalar offset for the pass in the plane layout.
-    typedef unsigned int ctw_u4 __attribute__((ext_vector_type(4)));
-    if (a.ydt == LWG_DT_F32_Q4) {
-        // channel-quad planes (B, YC/4, YH, YW, 4): 32 lanes = one output row of the block in one plane, 512 contiguous bytes
-        const int lx = tide & 31, cq = (tide >> 5) & 7, lyh = tide >> 8;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * (size_t)(a.YC >> 2) * plane * 4, 0,
-                                                                            (int)((unsigned)(a.YC >> 2) * (unsigned)plane * 16u), 0x00020000);
-        const unsigned yv = ox0 + lx < a.YW ? (unsigned)((((a.ycoff + en0) >> 2) + cq) * (int)plane + (oy0 + lyh) * a.YW + ox0 + lx) * 16u : WINO_OOB;
-        const float* src = smem + (lyh * 32 + ctw_slot(lx)) * OROW + 4 * cq;
-        const unsigned rowpair = (unsigned)a.YW * 32u;           // bytes between the rows of two passes (two rows of 16-byte pixels)
-#pragma unroll
-        for (int pass = 0; pass < 16; ++pass) {
-            const ctw_u4 v = *reinterpret_cast<const ctw_u4*>(src + pass * 64 * OROW);
-            // (the pass offset goes into the VECTOR offset, the scalar offset stays the constant 0: with a register in the scalar-offset field the compiler
-            //  plans no wait state between a 16-byte store and a VALU write of its data registers - and the next pass's address add landed in the first
-            //  data register right behind the store: intermittently corrupted first channels, found by tools/determinism_stress.py; r06_ar)
-            __builtin_amdgcn_raw_buffer_store_b128(v, ry, (int)(oy0 + 2 * pass < a.YH ? yv + (unsigned)pass * rowpair : WINO_OOB), 0, CTW_NT_ST);
-        }
-    } else {
-        // NHWC: 8 lanes = the block's 32 channels of one pixel, 128 contiguous bytes
-        const int cq = tide & 7, lx = (tide >> 3) & 31, lyh = tide >> 8;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * plane * a.YC, 0, (int)((unsigned)plane * (unsigned)a.YC * 4u), 0x00020000);
-        const bool in_x = ox0 + lx < a.YW;
-        const unsigned yv = in_x ? (unsigned)(((oy0 + lyh) * a.YW + ox0 + lx) * a.YC + a.ycoff + en0 + 4 * cq) * 4u : WINO_OOB;
-        const float* src = smem + (lyh * 32 + ctw_slot(lx)) * OROW + 4 * cq;
-        // right of the image every pass keeps the marker: added to it, the pass offsets wrapped past 2^32 into the image once 15 rowpair
-        // reached 1 GiB (tests/test_conv_offsets_cpu.py); rows below the image lie beyond the buffer's end (host: 32 rows of slack)
-        const unsigned rowpair = in_x ? (unsigned)a.YW * (unsigned)a.YC * 8u : 0u;
-#pragma unroll
-        for (int pass = 0; pass < 16; ++pass) {
-            const ctw_u4 v = *reinterpret_cast<const ctw_u4*>(src + pass * 64 * OROW);
-            __builtin_amdgcn_raw_buffer_store_b128(v, ry, (int)(yv + (unsigned)pass * rowpair), 0, CTW_NT_ST);        // (vector offset: see above)
-        }
-    }
+    // the block's outputs: exchange buffer -> global memory, whole 128-byte (NHWC) / 512-byte (channel-quad planes) runs (lwg_convt_wino.h)
+    ctw_store_block<CTW_NT_ST>(a, smem, tide, eb, ex0, ey0, en0, [](int, int lx) { return ctw_slot(lx); });
     CTSB(1, 13);
     if (!more) break;
     blk = nblk;
@@ -504,24 +395,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd_kernel(const
 // Upk[4][Cin/8][4][2][9 N] ([N][4] products 0-3, [N][4] products 4-7, [N] product 8 per (parity 2 py + px, stage s, k-pair kk, k-half kh)): product 3 xi + nu of column n =
 // sgn * (G g G^T)[xi][nu] with g[r][q] = w[c][n][3 - py - 2 r][3 - px - 2 q] the parity's 2 x 2 sub-kernel of input channel c = 8 s + 2 kk + kh,
 // G = [[1,0],[1,1],[0,1]] and sgn = (py == 1 && xi == 0 ? -1 : 1) * (px == 1 && nu == 0 ? -1 : 1).
-extern "C" int lwg_conv_transpose4_winograd_f32(const LwgConvArgs* pa, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!pa) return (int)hipErrorInvalidValue;
-    const LwgConvArgs& a = *pa;
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 4 || a.stride != 1 || a.omul != 2 || a.C0 <= 0 || (a.C0 % (2 * KS)) != 0 || a.C1 != 0 ||
-        a.N <= 0 || (a.N % NBT) != 0 || a.OH != a.H || a.OW != a.W || a.YH != 2 * a.H || a.YW != 2 * a.W || a.xdt != LWG_DT_F32 ||
-        (a.ydt != LWG_DT_F32 && a.ydt != LWG_DT_F32_Q4) || a.M != a.B * a.H * a.W || a.epi != LWG_EPI_NONE || a.act == LWG_ACT_RELU_MASK ||
-        a.ycoff < 0 || (a.ycoff % 4) != 0 || (a.YC % 4) != 0 || a.ycoff + a.N > a.YC)
-        return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.H * a.W * a.C0 * 4ull >= (unsigned long long)WINO_OOB || 144ull * a.C0 * a.N >= 0xffffffffull) return (int)hipErrorInvalidValue;
-    // (an output image is one buffer of the store path: byte offsets + the sixteen row-pair offsets of a block stay below the out-of-range marker)
-    if ((unsigned long long)a.YH * a.YW * a.YC * 4ull + 32ull * a.YW * a.YC * 4ull >= (unsigned long long)WINO_OOB) return (int)hipErrorInvalidValue;
-    const size_t lds = (size_t)(BIAS_OFF + 32) * 4;
+extern "C" int lwg_conv_transpose4_winograd_f32(const LwgConvArgs* pa, lwg_stream_t stream) {
     static unsigned long long done = 0;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_convt_winograd_kernel), lds, done); e != hipSuccess) return (int)e;
-    const int bx = (a.W + 2 * TPB - 1) / (2 * TPB), by = (a.H + 2 * TPB - 1) / (2 * TPB);
-    const long total = (long)bx * by * a.B * (a.N / NBT);
-    const int cus = lwg_device_cus();                        // persistent workgroups: one per CU (LDS) at most
-    hipLaunchKernelGGL(lwg_convt_winograd_kernel, dim3((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total)), dim3(WG_THREADS), lds, stream, a);
-    return (int)hipGetLastError();
+    return ctw_launch(lwg_convt_winograd_kernel, pa, stream, 144ull, 0xffffffffull, (size_t)(BIAS_OFF + 32) * 4, done);
 }

@@ -1,5 +1,5 @@
 // nn.ConvTranspose2d(kernel 4, stride 2, padding 1) in fp32 as a fused F(2x4, 2x2) Winograd convolution on v_mfma_f32_32x32x2_f32 - the successor of
-// convt_winograd.hip's F(2x2, 2x2) form with the same block footprint, staging and store paths.
+// convt_winograd.hip's F(2x2, 2x2) form with the same block footprint, staging and store paths - lwg_convt_wino.h.
 //   Output parity (py, px) of the layer is a 2 x 2-tap convolution of the input: y[2i + py][2j + px] = sum_{r,q in {0,1}} x[i + py - 1 + r][j + px - 1 + q]
 //   g_p[r][q].  Along rows F(2, 2) as in convt_winograd.hip (3 products for 2 outputs: row forms R0 = r0 - r1, R1 = r1, R2 = r2 - r1, R3 = r2,
 //   R4 = r3 - r2 of the four staged rows; parity 0 uses R0 R1 R2, parity 1 -R2 R3 R4, the sign lives in the panel).  Along columns F(4, 2) with the
@@ -12,7 +12,7 @@
 // p = w % 4 and half h = w / 4: h = 0 owns the products (xi, nu), nu = 0..2 (9 accumulator tiles of 32 x 32, rows = output channels, columns =
 // the block's 32 patches), h = 1 owns nu = 3, 4 (6 tiles); waves p and p + 4 share SIMD p: 15 products per k-pair and SIMD (F(2x2, 2x2): 18).
 // The output transform over xi is register-local; the column transform has a partial sum in each half: h = 1 writes its partials into the epilogue's
-// exchange buffer, h = 0 adds its own, the bias and the activation in place - then the global stores of convt_winograd.hip.
+// exchange buffer, h = 0 adds its own, the bias and the activation in place - then the shared store phase (lwg_convt_wino.h).
 // A K stage is 8 input channels = four k-pairs; per k-pair a lane loads its weights (h = 0: two 16-byte loads and one 4-byte load, h = 1: one 16-byte
 // and two 4-byte loads) from the panel Upk[4][Cin/8][4][2][15 N] (contiguous per load instruction; two k-pairs ahead, four register sets) and reads its
 // V fragments (4 bytes each) from LDS.  The raw 18 x 18 x 8 halo goes global -> registers (three stages ahead) -> raw[s % 2]; each (patch, channel) is
@@ -22,27 +22,12 @@
 // fp32-grade, NOT the bits of the direct kernel or of convt_winograd.hip.
 #include <hip/hip_runtime.h>
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_convt_wino.h"       // the block footprint, the block walk, the halo staging, the store phase and the launch (shared with convt_winograd.hip)
 
-#define WG_THREADS 512
-#define TPBY 8           // patch rows per block (2 input rows each)
-#define TPBX 4           // patch columns per block (4 input columns each)
-#define NPATCH 32
-#define NBT 32           // output channels per block
-#define KS 8             // input channels per stage
-#define HALO 18
-#define PLANE (HALO * HALO)
-#define RAW_FLOATS (KS * PLANE)              // [c][py][px]
+#define NPATCH 32        // 8 x 4 patches of 2 x 4 input pixels per block
 #define VSTR NPATCH
 #define NFORM 45                             // [row form 0..4][column form 0..8]
 #define VS_FLOATS (NFORM * KS * VSTR)        // [form][k][patch]
-#define DUMP_OFF (2 * RAW_FLOATS + 2 * VS_FLOATS)                 // where the threads without a halo element store their zeros (dead LDS)
-#define DUMP_FLOATS (WG_THREADS + 3 * PLANE + RAW_FLOATS)
-#define LOOP_FLOATS (DUMP_OFF + DUMP_FLOATS)
-#define OROW 36                              // floats per pixel row of the epilogue's exchange buffer [32 x 32 output pixels][32 channels + 4]
-#define OUT_FLOATS (32 * 32 * OROW)
-#define BIAS_OFF (LOOP_FLOATS > OUT_FLOATS ? LOOP_FLOATS : OUT_FLOATS)    // the block's 32 bias values, behind both uses of the LDS
-#define WINO_OOB 0xC0000000u                 // >= any image's byte size (host: H * W * C * 4 < 3 GiB): the buffer load returns 0
 #define WSB() __builtin_amdgcn_sched_barrier(0)
 // Who transforms what (profiles/f24_transform_balance.txt: the three layers at 32 / 8 / 4 frames, best of 5 x 10 launches, A/B twice, bitwise equal):
 // h = 1 threads on rows 0..2 (R0..R2, 27 values) and h = 0 threads on rows 2, 3 (R3, R4, 18 values) 2.089 ms per pass; the heavier share on the
@@ -65,18 +50,12 @@
 
 namespace {
 
-template <int V> struct IntT { static constexpr int value = V; };
-
 // Where output pixel (ly, lx) of the block lies in row ly of the exchange buffer (rows of 32 pixel slots x 36 floats; the bank quad of slot s is
 // 9 s mod 16).  A ds_write_b128 of the epilogue: eight consecutive lanes are patches etx = 0..3 of two patch rows ety = 2 m, 2 m + 1 - pixels
 // lx = 8 etx + r (r fixed), ly = 4 ety + const: slots 4 r + etx and (4 r + etx) ^ 4, eight distinct bank quads.  The channel-quad-plane reader's 16-lane
 // groups of 32 consecutive pixels land on sixteen distinct slots mod 16 (tests/test_convt_winograd24_cpu.py enumerates both).
 __device__ __forceinline__ int ctw24_slot(int ly, int lx) {
     return ((lx & 7) * 4 + (lx >> 3)) ^ (((ly >> 2) & 1) << 2);
-}
-
-__device__ __forceinline__ floatx4 ctw24_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
 
 // the nine column forms of six staged columns (B^T above on c0..c4 and c1..c5; C4 is shared)
@@ -99,73 +78,29 @@ __device__ __forceinline__ void ctw24_cols(const float (&c)[6], float (&v)[9]) {
 __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(const LwgConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int H = a.H, W = a.W, Cin = a.C0, N = a.N;
+    const int Cin = a.C0, N = a.N;
     float* const raw0 = smem;                                // [2][RAW], then [2][VS] (45 planes of [k][patch])
     const int tid = threadIdx.x, lane = tid & 63;
-    const int bx = (W + 2 * TPBY - 1) / (2 * TPBY), by = (H + 2 * TPBY - 1) / (2 * TPBY);
-    // persistent workgroups and the XCD-aware block order exactly as convt_winograd.hip
-    const int tiles = bx * by * a.B;
-    const int total = tiles * (N / NBT);
     int blk = blockIdx.x;
     const int nst = Cin / KS;                                // even (host: Cin % 16 == 0)
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(240u * (unsigned)Cin * (unsigned)N), 0x00020000);
     const int par = wid & 3, py = par >> 1, px = par & 1;    // this wave's output parity
     const int hh = wid >> 2;                                 // ... and its half of the column products (0: nu = 0..2, 1: nu = 3, 4)
     floatx16 acc[9];                                         // h = 0: [3 xi + nu]; h = 1: [2 xi + nu - 3]
-    int b, x0, y0, n0;
-    __amdgpu_buffer_rsrc_t rx0;
-    unsigned voff0[2];
-    unsigned uvoff, uvoffc;                                  // this lane's column of the panel: the 16-byte part(s), the 4-byte part(s)
-    const int ncb = N / NBT;
-    const bool xcd = (gridDim.x & 7u) == 0 && (ncb == 2 || ncb == 4 || ncb == 8) && (int)gridDim.x < total && tiles >= (int)gridDim.x / ncb;
-    const int xg = (int)gridDim.x / ncb;
-    const int xr = (int)(((blockIdx.x & 7u) / (unsigned)ncb) * (gridDim.x >> 3) + (blockIdx.x >> 3));
-    auto has_block = [&](int id) -> bool {
-        return xcd ? (id / (int)gridDim.x) * xg + xr < tiles : id < total;
-    };
+    // the workgroup's walk over its blocks and the per-block state (lwg_convt_wino.h; the XCD-aware order always on) and this lane's column
+    // of the panel: the 16-byte part(s), the 4-byte part(s)
+    CtwBlock<true> bk(a, tid, DUMP_OFF);
+    unsigned uvoff, uvoffc;
     auto setup = [&](int id) {
-        int cb, t;
-        if (xcd) {
-            cb = (int)(blockIdx.x & 7u) & (ncb - 1);
-            t = __builtin_amdgcn_readfirstlane((id / (int)gridDim.x) * xg + xr);
-        } else {
-            cb = __builtin_amdgcn_readfirstlane(id / tiles);
-            t = __builtin_amdgcn_readfirstlane(id - cb * tiles);
-        }
-        b = __builtin_amdgcn_readfirstlane(t / (bx * by));
-        t -= b * bx * by;
-        x0 = (t % bx) * 2 * TPBY;
-        y0 = (t / bx) * 2 * TPBY;
-        n0 = cb * NBT;
-        rx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x0 + (size_t)b * H * W * Cin), 0, (int)((unsigned)(H * W) * (unsigned)Cin * 4u), 0x00020000);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = tid + WG_THREADS * q;
-            const int pix = i >> 1, half = i & 1, hy = pix / HALO, hx = pix - hy * HALO;
-            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const bool in = i < PLANE * 2 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            voff0[q] = in ? (unsigned)((gy * W + gx) * Cin + 4 * half) * 4u : WINO_OOB;
-        }
+        bk.setup(a, tid, id);
         // element (parity, stage, k-pair, k-half) = 15 N floats: [N][4] products 0-3, [N][4] products 4-7, [N] product 8 (h = 0), [N][4] products
         // 9-12, [N] product 13, [N] product 14 (h = 1)
-        const unsigned kh = (unsigned)(lane >> 5) * 15u * (unsigned)N, n = (unsigned)(n0 + (lane & 31));
+        const unsigned kh = (unsigned)(lane >> 5) * 15u * (unsigned)N, n = (unsigned)(bk.n0 + (lane & 31));
         uvoff = (kh + (hh ? 9u * N : 0u) + 4u * n) * 4u;
         uvoffc = (kh + (hh ? 13u : 8u) * N + n) * 4u;
     };
     setup(blk);
-    int wst[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = tid + WG_THREADS * q;
-        wst[q] = i < PLANE * 2 ? 4 * (i & 1) * PLANE + (i >> 1) : DUMP_OFF + tid;
-    }
     floatx4 rreg[2];
-    auto rld1 = [&](int st, int q) -> floatx4 { return ctw24_buf_load(rx0, voff0[q], (unsigned)(st * KS) * 4u); };
-    auto rst1 = [&](int buf, int q, floatx4 v) {
-        float* dst = raw0 + buf * RAW_FLOATS + wst[q];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k * PLANE] = v[k];
-    };
     floatx4 ufr[4][3];                                       // [register set = k-pair][16-byte parts | last part]: loaded TWO k-pairs ahead
     const unsigned ukk = (unsigned)N * 120u;                 // bytes between two k-pairs: [2][15 N] floats
     const unsigned upar = (unsigned)par * (unsigned)nst * 4u * ukk;
@@ -174,12 +109,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
         const unsigned so = upar + (unsigned)(st * 4 + kk) * ukk;
         floatx4 r;
         if (h == 0) {
-            if (j < 2) return ctw24_buf_load(ru, uvoff, so + (j ? ubo : 0u));
+            if (j < 2) return ctw_buf_load(ru, uvoff, so + (j ? ubo : 0u));
             r[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ru, (int)uvoffc, (int)so, 0));
             r[1] = r[2] = r[3] = 0.f;
             return r;
         }
-        if (j == 0) return ctw24_buf_load(ru, uvoff, so);
+        if (j == 0) return ctw_buf_load(ru, uvoff, so);
         r[0] = r[1] = r[2] = r[3] = 0.f;
         if (j == 1) {                                        // (two 4-byte loads: see DESIGN.md 3.12c on __builtin_amdgcn_raw_buffer_load_b64)
             r[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ru, (int)uvoffc, (int)so, 0));
@@ -266,10 +201,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
             fragread(set, 1);
             WSB();
             mf(0, 0);
-            if (nxt) { rst1(set, 0, rreg[0]); rreg[0] = rld1(s3, 0); }
+            if (nxt) { bk.rst1(raw0, set, 0, rreg[0]); rreg[0] = bk.rld1(s3, 0); }
             WSB();
             mf(0, 1);
-            if (nxt) { rst1(set, 1, rreg[1]); rreg[1] = rld1(s3, 1); }
+            if (nxt) { bk.rst1(raw0, set, 1, rreg[1]); rreg[1] = bk.rld1(s3, 1); }
             WSB();
 #pragma unroll
             for (int q = 2; q < NP; ++q) {
@@ -336,11 +271,11 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
     floatx4 r0[2], r1[2];
     float bq;
     auto issue_loads = [&]() {
-        bq = a.bias ? a.bias[n0 + (tid & 31)] : 0.f;
+        bq = a.bias ? a.bias[bk.n0 + (tid & 31)] : 0.f;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            r0[q] = rld1(0, q);
-            r1[q] = rld1(1, q);
+            r0[q] = bk.rld1(0, q);
+            r1[q] = bk.rld1(1, q);
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -348,7 +283,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
             ufr[1][j] = uld1(0, 1, j, hh);
         }
 #pragma unroll
-        for (int q = 0; q < 2; ++q) rreg[q] = rld1(nst > 2 ? 2 : 1, q);
+        for (int q = 0; q < 2; ++q) rreg[q] = bk.rld1(nst > 2 ? 2 : 1, q);
     };
     issue_loads();
 #ifdef LWG_CTW24_TS
@@ -357,8 +292,8 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
     for (;;) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        rst1(0, q, r0[q]);
-        rst1(1, q, r1[q]);
+        bk.rst1(raw0, 0, q, r0[q]);
+        bk.rst1(raw0, 1, q, r1[q]);
     }
     if (tid < 32) smem[BIAS_OFF + tid] = bq;
     __syncthreads();
@@ -366,7 +301,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
     CTS24(1, __builtin_readcyclecounter());
     if (hh == 0) kloop(IntT<0>()); else kloop(IntT<1>());
     CTS24(2, __builtin_readcyclecounter());
-    const int eb = b, ex0 = x0, ey0 = y0, en0 = n0;          // this block's coordinates (the state moves on to the next block below)
+    const int eb = bk.b, ex0 = bk.x0, ey0 = bk.y0, en0 = bk.n0;          // this block's coordinates (the state moves on to the next block below)
     // epilogue: per output row ia of the patch the xi sums S[nu] = M[ia][nu] + M[ia + 1][nu]; the column transform A^T S is split - h = 1 writes
     // (S3, S3 / 2, S3 / 4, S3 / 8 + S4) into the exchange buffer, h = 0 adds (S0 + S1 + S2, S1 - S2, S1 + S2, S1 - S2), the bias, the activation.
     // Lane: patch lane % 32 (ety = patch / 4, etx = patch % 4), per register group g the four channels 8 g + 4 (lane / 32) ..
@@ -435,43 +370,12 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
     }
     // the next block of this workgroup: its first loads go out here and land under the stores below (as convt_winograd.hip)
     const int nblk = blk + (int)gridDim.x;
-    const bool more = has_block(nblk);
+    const bool more = bk.has_block(nblk);
     setup(more ? nblk : blk);
     issue_loads();
     __syncthreads();
-    const int oy0 = 2 * ey0, ox0 = 2 * ex0;
-    const size_t plane = (size_t)a.YH * a.YW;
-    // buffer stores as convt_winograd.hip: the pass offset goes into the VECTOR offset, the scalar offset stays the constant 0
-    typedef unsigned int ctw_u4 __attribute__((ext_vector_type(4)));
-    if (a.ydt == LWG_DT_F32_Q4) {
-        // channel-quad planes (B, YC/4, YH, YW, 4): 32 lanes = one output row of the block in one plane, 512 contiguous bytes
-        const int lx = tide & 31, cq = (tide >> 5) & 7, lyh = tide >> 8;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * (size_t)(a.YC >> 2) * plane * 4, 0,
-                                                                            (int)((unsigned)(a.YC >> 2) * (unsigned)plane * 16u), 0x00020000);
-        const unsigned yv = ox0 + lx < a.YW ? (unsigned)((((a.ycoff + en0) >> 2) + cq) * (int)plane + (oy0 + lyh) * a.YW + ox0 + lx) * 16u : WINO_OOB;
-        const unsigned rowpair = (unsigned)a.YW * 32u;
-#pragma unroll
-        for (int pass = 0; pass < 16; ++pass) {
-            const int ly = lyh + 2 * pass;
-            const ctw_u4 v = *reinterpret_cast<const ctw_u4*>(smem + (ly * 32 + ctw24_slot(ly, lx)) * OROW + 4 * cq);
-            __builtin_amdgcn_raw_buffer_store_b128(v, ry, (int)(oy0 + 2 * pass < a.YH ? yv + (unsigned)pass * rowpair : WINO_OOB), 0, 0);
-        }
-    } else {
-        // NHWC: 8 lanes = the block's 32 channels of one pixel, 128 contiguous bytes
-        const int cq = tide & 7, lx = (tide >> 3) & 31, lyh = tide >> 8;
-        const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)eb * plane * a.YC, 0, (int)((unsigned)plane * (unsigned)a.YC * 4u), 0x00020000);
-        const bool in_x = ox0 + lx < a.YW;
-        const unsigned yv = in_x ? (unsigned)(((oy0 + lyh) * a.YW + ox0 + lx) * a.YC + a.ycoff + en0 + 4 * cq) * 4u : WINO_OOB;
-        // right of the image every pass keeps the marker: added to it, the pass offsets wrapped past 2^32 into the image once 15 rowpair
-        // reached 1 GiB (tests/test_conv_offsets_cpu.py); rows below the image lie beyond the buffer's end (host: 32 rows of slack)
-        const unsigned rowpair = in_x ? (unsigned)a.YW * (unsigned)a.YC * 8u : 0u;
-#pragma unroll
-        for (int pass = 0; pass < 16; ++pass) {
-            const int ly = lyh + 2 * pass;
-            const ctw_u4 v = *reinterpret_cast<const ctw_u4*>(smem + (ly * 32 + ctw24_slot(ly, lx)) * OROW + 4 * cq);
-            __builtin_amdgcn_raw_buffer_store_b128(v, ry, (int)(yv + (unsigned)pass * rowpair), 0, 0);        // (vector offset: see above)
-        }
-    }
+    // the block's outputs: exchange buffer -> global memory (lwg_convt_wino.h; default cache policy)
+    ctw_store_block<0>(a, smem, tide, eb, ex0, ey0, en0, [](int ly, int lx) { return ctw24_slot(ly, lx); });
     CTS24(4, __builtin_readcyclecounter());
     if (!more) break;
 #ifdef LWG_CTW24_TS
@@ -487,23 +391,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_convt_winograd24_kernel(con
 // [N][4] products 0-3, [N][4] products 4-7, [N] product 8, [N][4] products 9-12, [N] product 13, [N] product 14; product 3 xi + nu (nu < 3) / 9 + 2 xi + nu - 3
 // (nu >= 3) of column n = sgn * (G_y g G_x^T)[xi][nu] with g[r][q] = w[c][n][3 - py - 2 r][3 - px - 2 q] of input channel c = 8 s + 2 kk + kh,
 // G_y = [[1,0],[1,1],[0,1]], G_x = [[1,0],[1/2,1/2],[-1/6,1/6],[-8/3,-4/3],[0,1/2]] and sgn = (py == 1 && xi == 0 ? -1 : 1).
-extern "C" int lwg_conv_transpose4_winograd24_f32(const LwgConvArgs* pa, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!pa) return (int)hipErrorInvalidValue;
-    const LwgConvArgs& a = *pa;
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 4 || a.stride != 1 || a.omul != 2 || a.C0 <= 0 || (a.C0 % (2 * KS)) != 0 || a.C1 != 0 ||
-        a.N <= 0 || (a.N % NBT) != 0 || a.OH != a.H || a.OW != a.W || a.YH != 2 * a.H || a.YW != 2 * a.W || a.xdt != LWG_DT_F32 ||
-        (a.ydt != LWG_DT_F32 && a.ydt != LWG_DT_F32_Q4) || a.M != a.B * a.H * a.W || a.epi != LWG_EPI_NONE || a.act == LWG_ACT_RELU_MASK ||
-        a.ycoff < 0 || (a.ycoff % 4) != 0 || (a.YC % 4) != 0 || a.ycoff + a.N > a.YC)
-        return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.H * a.W * a.C0 * 4ull >= (unsigned long long)WINO_OOB || 240ull * a.C0 * a.N >= 0x7fffffffull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.YH * a.YW * a.YC * 4ull + 32ull * a.YW * a.YC * 4ull >= (unsigned long long)WINO_OOB) return (int)hipErrorInvalidValue;
-    const size_t lds = (size_t)(BIAS_OFF + 32) * 4;
+extern "C" int lwg_conv_transpose4_winograd24_f32(const LwgConvArgs* pa, lwg_stream_t stream) {
     static unsigned long long done = 0;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_convt_winograd24_kernel), lds, done); e != hipSuccess) return (int)e;
-    const int bx = (a.W + 2 * TPBY - 1) / (2 * TPBY), by = (a.H + 2 * TPBY - 1) / (2 * TPBY);
-    const long total = (long)bx * by * a.B * (a.N / NBT);
-    const int cus = lwg_device_cus();                        // persistent workgroups: one per CU (LDS) at most
-    hipLaunchKernelGGL(lwg_convt_winograd24_kernel, dim3((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total)), dim3(WG_THREADS), lds, stream, a);
-    return (int)hipGetLastError();
+    return ctw_launch(lwg_convt_winograd24_kernel, pa, stream, 240ull, 0x7fffffffull, (size_t)(BIAS_OFF + 32) * 4, done);
 }

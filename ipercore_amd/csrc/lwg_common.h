@@ -24,7 +24,7 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 #define LWG_CONV_SMALL_TILES 300   // conv_igemm.hip: launches with fewer 128 x 128 tiles than this use 64 x 64 tiles
 #endif
 #ifndef LWG_WINO_PERSIST
-#define LWG_WINO_PERSIST 1         // conv_winograd.hip / convt_winograd.hip: persistent workgroups (one per CU walks the blocks, the next block's first loads under the epilogue); 0 = one block per workgroup
+#define LWG_WINO_PERSIST 1         // conv_winograd.hip / lwg_convt_wino.h (both transposed Winograd kernels): persistent workgroups (one per CU walks the blocks, the next block's first loads under the epilogue); 0 = one block per workgroup
 #endif
 #ifndef LWG_CONV_DEEP
 #define LWG_CONV_DEEP 1            // conv_igemm.hip: the small-tile launches load two K-steps ahead (0 = one, as the large tiles)

@@ -491,8 +491,12 @@ def test_no_wide_buffer_store_with_register_soffset():
         pytest.skip("no hipcc")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "ipercore_amd", "csrc")
-    srcs = [f for f in sorted(glob.glob(os.path.join(csrc, "*.hip"))) if "raw_buffer_store" in open(f).read()]
-    assert srcs, "the Winograd kernels store through buffer instructions"
+    def stores(f, seen=()):                                  # the source itself or a header of this directory that it includes
+        text = open(f).read()
+        return "raw_buffer_store" in text or any(stores(os.path.join(csrc, h), seen + (f,)) for h in re.findall(r'#include "(\w+\.h)"', text)
+                                                 if os.path.join(csrc, h) not in seen + (f,) and os.path.exists(os.path.join(csrc, h)))
+    srcs = [f for f in sorted(glob.glob(os.path.join(csrc, "*.hip"))) if stores(f)]
+    assert {"convt_winograd.hip", "convt_winograd24.hip", "conv_winograd4.hip"} <= {os.path.basename(f) for f in srcs}, srcs
     pat = re.compile(r"buffer_store_(dwordx[34]|format_xyzw?)\s+v\[[0-9:]+\],\s*[^,]+,\s*s\[[0-9:]+\],\s*s[0-9]+\b")
     with tempfile.TemporaryDirectory() as d:
         for f in srcs:

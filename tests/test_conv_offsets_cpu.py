@@ -5,8 +5,9 @@ the image) gets the marker 0xC0000000 - at or beyond any image's size, so the ha
 while every offset the kernel forms - the marker plus a per-pass or per-stage increment included - stays within 32 bits, and while the C++
 expressions that form the offsets do not overflow their own types.
 
-The audit below compiles the offset expressions of csrc/*.hip VERBATIM (cut out of the kernel sources, so that it checks the kernels and not a copy)
-into a host program with signed-overflow traps, and evaluates them for the corner shapes the host contracts accept: the widest output rows at the
+The audit below compiles the kernels' own offset arithmetic into a host program with signed-overflow traps - the transposed kernels' by INCLUDING
+csrc/lwg_convt_wino.h, whose integer functions are what both kernels compile; the 3 x 3 kernels' expressions cut VERBATIM out of their sources -
+and evaluates it for the corner shapes the host contracts accept: the widest output rows at the
 fewest rows, the tallest images at one or two pixels of width, images just under the size limits, widths and heights that are not multiples of the
 tile.  Every kept access must land at its own pixel and channel; every dropped one at or beyond the buffer's size modulo 2^32.
 
@@ -68,22 +69,13 @@ def _call_args(text, fname):
             cur.append(ch)
 
 
-def _convt_store_branches(name):
-    """csrc/<name>: the two store paths of the transposed Winograd kernel - (set-up statements, per-pass statements, store offset, store soffset)
-    for the channel-quad-plane and the NHWC layout."""
-    s = _src(name)
-    i0 = s.index("if (a.ydt == LWG_DT_F32_Q4) {", s.index("ctw_u4 __attribute__"))
-    i1 = s.index("} else {", i0)
-    i2 = s.index("if (!more) break;", i1)
-    out = {}
-    for lay, body in (("q4", s[i0 + len("if (a.ydt == LWG_DT_F32_Q4) {"):i1]), ("nhwc", s[i1 + len("} else {"):i2])):
-        head, loop = body.split("for (int pass = 0; pass < 16; ++pass) {", 1)
-        setup = [t for t in _stmts(head) if t.startswith("const") and not re.search(r"make_buffer_rsrc|smem|src\b|pragma", t)]
-        setup = [t.replace("#pragma unroll", "").strip() for t in setup]
-        per = [t for t in _stmts(loop) if t.startswith("const int ly")]
-        args = _call_args(loop, "__builtin_amdgcn_raw_buffer_store_b128")
-        out[lay] = (setup, per, args[2], args[3])
-    return out
+def _code(name):
+    """csrc/<name> without its comments."""
+    return _src(name)
+
+
+CONVT_KERNELS = ("convt_winograd.hip", "convt_winograd24.hip")
+CONVT_HEADER = "lwg_convt_wino.h"
 
 
 def _w4_exprs():
@@ -95,9 +87,9 @@ def _w4_exprs():
 
 
 def _halo_exprs():
-    """(kernel, input 0 / 1, offset expression) of the four Winograd kernels' halo loads."""
+    """(kernel, input 0 / 1, offset expression) of the 3 x 3 Winograd kernels' halo loads (the transposed kernels': ctw_halo_voff of the header)."""
     out = []
-    for name, var in (("conv_winograd.hip", "q"), ("conv_winograd4.hip", "k"), ("convt_winograd.hip", "q"), ("convt_winograd24.hip", "q")):
+    for name, var in (("conv_winograd.hip", "q"), ("conv_winograd4.hip", "k")):
         s = _src(name)
         for inp in ("0", "1"):
             m = re.search(r"voff%s\[%s\] = (in \?.*?);" % (inp, var), s, re.S)
@@ -109,7 +101,7 @@ def _halo_exprs():
 def _halo_soffsets():
     """The stage's channel offset of every halo load: the scalar offset argument, as written in each kernel."""
     got = {}
-    for name in ("conv_winograd.hip", "conv_winograd4.hip", "convt_winograd.hip", "convt_winograd24.hip"):
+    for name in ("conv_winograd.hip", "conv_winograd4.hip"):
         s = _src(name)
         r = s[s.index("auto rld1"):]
         fn = re.search(r"(\w+_buf_load\w*)\(rx0, voff0\[\w\], ", r).group(1)
@@ -118,19 +110,28 @@ def _halo_soffsets():
 
 
 def test_offset_expressions_are_found():
-    """The audit below reads what it checks out of the kernels: the expressions it cuts out must be there, in the forms it knows how to drive."""
-    for name in ("convt_winograd.hip", "convt_winograd24.hip"):
-        br = _convt_store_branches(name)
-        for lay in ("q4", "nhwc"):
-            setup, per, off, soff = br[lay]
-            assert any(t.startswith("const unsigned yv =") for t in setup) and any(t.startswith("const unsigned rowpair =") for t in setup), (name, lay)
-            assert "pass" in off and soff == "0", (name, lay, off, soff)    # pass offsets in the VECTOR offset (test_no_wide_buffer_store_with_register_soffset)
+    """The audit below reads what it checks out of the kernels: the expressions it cuts out must be there, in the forms it knows how to drive.  The
+    transposed kernels are audited through the shared header, so the converse is checked here: neither kernel forms a store or halo offset of its
+    own, and both run the header's block walk, halo staging and store phase."""
+    h = _code(CONVT_HEADER)
+    st = _call_args(h, "__builtin_amdgcn_raw_buffer_store_b128")
+    assert st[2].startswith("(int)ctw_store_voff(") and "pass" in st[2] and st[3] == "0", st       # pass offsets in the VECTOR offset (test_no_wide_buffer_store_with_register_soffset)
+    assert "ctw_store_thread(q4, tide, ex0, ey0, a.ycoff, en0, a.YH, a.YW, a.YC)" in h
+    assert "ctw_buf_load(rx0, voff0[q], ctw_halo_soff(st))" in h and "voff0[q] = ctw_halo_voff(tid + WG_THREADS * q, x0, y0, a.H, a.W, a.C0)" in h
+    assert "ctw_has_block(o, id)" in h and "!ctw_contract_ok(*pa, pair_bytes, panel_limit)" in h
+    for name in CONVT_KERNELS:
+        k = _code(name)
+        for word in ("raw_buffer_store", "make_buffer_rsrc(a.y", "make_buffer_rsrc(const_cast<float*>(a.x0", "WINO_OOB", "auto has_block", "hipLaunchKernelGGL"):
+            assert word not in k, (name, word)
+        assert '#include "%s"' % CONVT_HEADER in k, name
+        for call in ("CtwBlock<", "bk.setup(a, tid, id)", "bk.has_block(nblk)", "bk.rld1(", "bk.rst1(raw0, ", "ctw_store_block<", "return ctw_launch("):
+            assert call in k, (name, call)
     vo, st_off, st_soff, ld_off, ld_soff = _w4_exprs()
     assert "W4_OOB" in vo and st_soff == "0" and ld_soff == "0"
-    assert len(_halo_exprs()) == 6                                       # two inputs in the two 3 x 3 kernels, one in the transposed ones
+    assert len(_halo_exprs()) == 4                                       # two inputs in each of the two 3 x 3 kernels
     so = _halo_soffsets()
-    assert so == {"conv_winograd.hip": "(unsigned)c * 4u", "conv_winograd4.hip": "(unsigned)c * 4u",
-                  "convt_winograd.hip": "(unsigned)(st * KS) * 4u", "convt_winograd24.hip": "(unsigned)(st * KS) * 4u"}, so
+    assert so == {"conv_winograd.hip": "(unsigned)c * 4u", "conv_winograd4.hip": "(unsigned)c * 4u"}, so
+    assert "CTW_FN unsigned ctw_halo_soff(int st) { return (unsigned)(st * KS) * 4u; }" in h
 
 
 # ---- host contracts (restated from the entry points; test_host_limits_at_the_boundary checks them against the library) ----
@@ -192,22 +193,83 @@ def _w4_shapes():
     return out
 
 
-# the store phase of a transposed Winograd block (32 x 32 output pixels x 32 channels; 512 threads x 16 passes), the kernel's statements inserted
-_CONVT_STORE = r"""
-static void @FN@(const Args& a, int ex0, int ey0, int en0) {
+# the transposed kernels through csrc/lwg_convt_wino.h: the store phase of a block (32 x 32 output pixels x 32 channels; 512 threads x 16 passes), its
+# halo (512 threads x 2 elements x every stage), the block walk of a launch, the host contract
+_CONVT = r"""
+#include "lwg_convt_wino.h"
+#include <vector>
+template <bool Q4>
+static void convt_store(const Args& a, int ex0, int ey0, int en0) {
     const int oy0 = 2 * ey0, ox0 = 2 * ex0;
     const size_t plane = (size_t)a.YH * a.YW;
     const u64 size = (u64)plane * a.YC * 4ull;
+    static unsigned char seen[32 * 32 * 8];
+    for (unsigned char& v : seen) v = 0;
     for (int tide = 0; tide < 512; ++tide) {
-        @SETUP@
+        const CtwStore s = ctw_store_thread(Q4, tide, ex0, ey0, a.ycoff, en0, a.YH, a.YW, a.YC);
         for (int pass = 0; pass < 16; ++pass) {
-            @PER@
-            const int row = oy0 + lyh + 2 * pass, col = ox0 + lx, ch = a.ycoff + en0 + 4 * cq;
+            const int ly = s.lyh + 2 * pass;
+            if (ly < 0 || ly >= 32 || s.lx < 0 || s.lx >= 32 || s.cq < 0 || s.cq >= 8 || seen[(ly * 32 + s.lx) * 8 + s.cq]++) {       // every output of the block once
+                if (bad++ < 8) printf("BAD %s tide=%d pass=%d: pixel (%d, %d) quad %d out of the block or stored twice\n", where, tide, pass, s.lx, ly, s.cq);
+                continue;
+            }
+            const int row = oy0 + ly, col = ox0 + s.lx, ch = a.ycoff + en0 + 4 * s.cq;
             const bool keep = row < a.YH && col < a.YW;
-            const u64 want = @Q4@ ? (((u64)(ch / 4) * plane + (u64)row * a.YW + col) * 16ull) : (((u64)row * a.YW + col) * a.YC + ch) * 4ull;
-            check(keep, (unsigned)(@OFF@), (unsigned)(@SOFF@), want, size, col, row, ch);
+            const u64 want = Q4 ? (((u64)(ch / 4) * plane + (u64)row * a.YW + col) * 16ull) : (((u64)row * a.YW + col) * a.YC + ch) * 4ull;
+            check(keep, ctw_store_voff(Q4, s, pass, ey0, a.YH), 0u, want, size, col, row, ch);       // (scalar offset: the constant 0 of ctw_store_block)
         }
     }
+}
+
+static void convt_halo(const Args& a, int x0, int y0, int) {
+    const u64 size = (u64)a.H * a.W * a.C0 * 4ull;
+    for (int i = 0; i < 2 * WG_THREADS; ++i) {
+        const unsigned v = ctw_halo_voff(i, x0, y0, a.H, a.W, a.C0);
+        const int half = i % 2, gy = y0 - 1 + (i / 2) / 18, gx = x0 - 1 + (i / 2) % 18;
+        const bool in = i < 2 * 18 * 18 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+        for (int st = 0; st < a.C0 / 8; ++st) {
+            const u64 want = in ? (((u64)gy * a.W + gx) * a.C0 + 4 * half + 8 * st) * 4ull : 0ull;
+            check(in, v, ctw_halo_soff(st), want, size, gx, gy, 8 * st + 4 * half);
+        }
+        // LDS: the element's four channels at slot + k PLANE inside raw[u]; the threads without one at their own dump slot
+        const int slot = ctw_halo_slot(i, 1 << 20);
+        if (i < 2 * 18 * 18 ? slot != 4 * half * 324 + (i / 2) || slot + 3 * 324 >= RAW_FLOATS : slot != 1 << 20)
+            if (bad++ < 8) printf("BAD %s halo slot of element %d: %d\n", where, i, slot);
+    }
+}
+
+// every workgroup's walk over a launch of nwg workgroups: each (column block, tile) exactly once, inside the grid; no block behind the last one
+static void convt_walk(int B, int H, int W, int N, unsigned nwg, bool xcd_on) {
+    const CtwGrid g = ctw_grid(B, H, W, N);
+    if ((long)nwg > ctw_total_blocks(B, H, W, N)) nwg = (unsigned)g.total;             // (the launch: min(blocks, CUs) workgroups)
+    std::vector<int> seen((size_t)g.total, 0);
+    u64 fails = 0;
+    for (unsigned wg = 0; wg < nwg; ++wg) {
+        const CtwOrder o = ctw_order(xcd_on, nwg, wg, N, g);
+        if (o.xcd != (xcd_on && ctw_xcd_applies(nwg, N / 32, g.tiles, g.total))) ++fails;
+        int id = (int)wg;
+        do {                                                                           // (the first block is taken unconditionally, as the kernels do)
+            const int cb = ctw_col_block(o, id), t = ctw_tile(o, id, cb), b = ctw_image(g, t);
+            int x0, y0, n0;
+            ctw_corner(g, t - b * g.bx * g.by, cb, x0, y0, n0);
+            if (cb < 0 || cb >= N / 32 || t < 0 || t >= g.tiles || b < 0 || b >= B || x0 < 0 || x0 >= W || y0 < 0 || y0 >= H || x0 % 16 || y0 % 16 || n0 != 32 * cb) ++fails;
+            else ++seen[(size_t)cb * g.tiles + t];
+            ++walked;
+            id += (int)nwg;
+        } while (ctw_has_block(o, id));
+        for (int k = 1; k < 4; ++k) if (ctw_has_block(o, id + k * (int)nwg)) ++fails;
+    }
+    for (int v : seen) if (v != 1) ++fails;
+    if (fails) { bad += fails; printf("BAD walk B=%d H=%d W=%d N=%d nwg=%u xcd=%d: %llu\n", B, H, W, N, nwg, (int)xcd_on, fails); }
+}
+
+static int convt_contract(int B, int H, int W, int C0, int N, int YC, int ydt, u64 pair_bytes, u64 panel_limit) {
+    static float dummy;
+    LwgConvArgs a = {};
+    a.x0 = a.w = &dummy; a.y = &dummy;
+    a.B = B; a.H = a.OH = H; a.W = a.OW = W; a.C0 = C0; a.N = N; a.M = B * H * W;
+    a.YH = 2 * H; a.YW = 2 * W; a.YC = YC; a.ntaps = 4; a.stride = 1; a.omul = 2; a.ydt = ydt;
+    return (int)ctw_contract_ok(a, pair_bytes, panel_limit);
 }
 """
 
@@ -216,14 +278,11 @@ _HARNESS = r"""
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
-#define WINO_OOB 0xC0000000u
 #define W4_OOB 0xC0000000u
-#define KS 8
 #define W4_KS 8
-enum { LWG_EPI_NONE = 0, LWG_EPI_RESIDUAL = 1, LWG_EPI_SPADE = 2 };
 struct Args { int H, W, C0, C1, N, YH, YW, YC, ycoff; };
 typedef unsigned long long u64;
-static u64 kept = 0, dropped = 0, bad = 0;
+static u64 kept = 0, dropped = 0, bad = 0, walked = 0;
 static const char* where = "";
 // every access: kept ones at want (inside the image); dropped ones at or beyond the buffer's size modulo 2^32
 static void check(bool keep, unsigned voff, unsigned soff, u64 want, u64 size, int x, int y, int c) {
@@ -301,28 +360,43 @@ static void run_w4(const Args& a) {
 
 int main() {
 @MAIN@
-    printf("kept %llu dropped %llu bad %llu\n", kept, dropped, bad);
+    printf("kept %llu dropped %llu bad %llu walked %llu\n", kept, dropped, bad, walked);
     return bad != 0;
 }
 """
 
 
+# block walks: the decoder's three up-sampling layers at 512 x 512 (B, H = W, N) for the benchmark's frame batches on 256 CUs, and ragged launches -
+# grids that are no multiple of 8, 1 / 2 / 4 / 8 column blocks, fewer tiles than workgroups per column block, fewer blocks than workgroups
+def _walk_cases():
+    out = [(B, S, S, N, 256) for S, N in ((64, 256), (128, 128), (256, 64)) for B in (300, 32, 2, 1)]
+    out += [(1, 40, 56, 32 * ncb, nwg) for ncb in (1, 2, 4, 8) for nwg in (8, 24, 64, 250, 256, 304)]
+    out += [(3, 17, 100, 32 * ncb, nwg) for ncb in (2, 3, 8) for nwg in (16, 40, 63)]
+    out += [(1, 16, 16 * 9, 256, 64), (1, 16, 16 * 8, 256, 64), (1, 16, 16 * 7, 256, 64), (5, 1, 1, 64, 8)]       # tiles = 9, 8, 7 against grid / ncb = 8
+    return out
+
+
+def _contract_cases():
+    """(entry point, B, H, W, C0, N, YC, ydt) of _limit_cases()'s transposed Winograd shapes, over and under each limit, and of _convt_shapes()."""
+    out = []
+    for _, fn, over, under in _limit_cases():
+        if "transpose4_winograd" in fn:
+            out += [(fn, kw["B"], kw["H"], kw["W"], kw["C0"], kw["N"], kw["YC"], kw.get("ydt", 0)) for kw in (over, under)]
+    for H, W, Cin, N, YC, _ in _convt_shapes():
+        out += [(fn, 1, H, W, Cin, N, YC, 0) for fn in ("lwg_conv_transpose4_winograd_f32", "lwg_conv_transpose4_winograd24_f32")]
+    return out
+
+
+_PANELS = {"lwg_conv_transpose4_winograd_f32": (144, 0xffffffff), "lwg_conv_transpose4_winograd24_f32": (240, 0x7fffffff)}      # bytes per (Cin, N) pair, size limit
+
+
 def _harness():
-    convt = []
-    fns = []
-    for name in ("convt_winograd.hip", "convt_winograd24.hip"):
-        for lay, (setup, per, off, soff) in _convt_store_branches(name).items():
-            fn = "%s_%s" % ("convt24" if "24" in name else "convt22", lay)
-            convt.append(_CONVT_STORE.replace("@FN@", fn).replace("@SETUP@", " ".join(t + ";" for t in setup))
-                         .replace("@PER@", " ".join(t + "; (void)ly;" for t in per)).replace("@OFF@", off).replace("@SOFF@", soff)
-                         .replace("@Q4@", "true" if lay == "q4" else "false"))
-            fns.append((name, lay, fn))
     vo, st_off, st_soff, ld_off, ld_soff = _w4_exprs()
     halo, hcalls = [], []
     soffs = _halo_soffsets()
     for j, (name, inp, expr) in enumerate(_halo_exprs()):
         cvar = "a.C" + inp if "a.C" + inp in expr else "Cin"
-        so = soffs[name].replace("(st * KS)", "c")
+        so = soffs[name]
         halo.append(textwrap.dedent("""
         static void halo_%d(const Args& a, int gx, int gy) {
             const int W = a.W, H = a.H, Cin = %s;
@@ -339,24 +413,24 @@ def _harness():
         }""") % (j, cvar, expr.replace("a.C0", "Cin").replace("a.C1", "Cin"), so))
         hcalls.append((name, j))
     main = []
+    who = "%s (%s)" % (CONVT_HEADER, ", ".join(CONVT_KERNELS))
     for sh in _convt_shapes():
         H, W, Cin, N, YC, ycoff = sh
         a = "Args{%d, %d, %d, 0, %d, %d, %d, %d, %d}" % (H, W, Cin, N, 2 * H, 2 * W, YC, ycoff)
-        for name, lay, fn in fns:
-            main.append('    run_convt(%s, "%s %s H=%d W=%d YC=%d ycoff=%d", %s);' % (fn, name, lay, H, W, YC, ycoff, a))
-        for name, j in hcalls:
-            if name.startswith("convt"):
-                main.append('    where = "%s halo H=%d W=%d"; for (int gy : {-1, 0, %d, %d, %d}) for (int gx : {-1, 0, %d, %d, %d}) halo_%d(%s, gx, gy);'
-                            % (name, H, W, H - 1, H, H + 16, W - 1, W, W + 16, j, a))
+        for lay, fn in (("q4", "convt_store<true>"), ("nhwc", "convt_store<false>"), ("halo", "convt_halo")):
+            main.append('    run_convt(%s, "%s %s H=%d W=%d YC=%d ycoff=%d", %s);' % (fn, who, lay, H, W, YC, ycoff, a))
+    for c in _walk_cases():
+        main.append("    convt_walk(%d, %d, %d, %d, %du, true); convt_walk(%d, %d, %d, %d, %du, false);" % (c + c))
+    for j, (fn, B, H, W, C0, N, YC, ydt) in enumerate(_contract_cases()):
+        main.append('    printf("contract %d %%d\\n", convt_contract(%d, %d, %d, %d, %d, %d, %d, %dull, %dull));' % ((j, B, H, W, C0, N, YC, ydt) + _PANELS[fn]))
     for sh in _w4_shapes():
         H, W, C, N, YC, ycoff = sh
         a = "Args{%d, %d, %d, %d, %d, %d, %d, %d, %d}" % (H, W, C, C, N, H, W, YC, ycoff)
         main.append("    run_w4(%s);" % a)
         for name, j in hcalls:
-            if not name.startswith("convt"):
-                main.append('    where = "%s halo H=%d W=%d"; for (int gy : {-1, 0, %d, %d}) for (int gx : {-1, 0, %d, %d}) halo_%d(%s, gx, gy);'
-                            % (name, H, W, H - 1, H, W - 1, W, j, a))
-    return (_HARNESS.replace("@CONVT@", "\n".join(convt)).replace("@VO@", vo).replace("@ST_OFF@", st_off).replace("@ST_SOFF@", st_soff)
+            main.append('    where = "%s halo H=%d W=%d"; for (int gy : {-1, 0, %d, %d}) for (int gx : {-1, 0, %d, %d}) halo_%d(%s, gx, gy);'
+                        % (name, H, W, H - 1, H, W - 1, W, j, a))
+    return (_HARNESS.replace("@CONVT@", _CONVT).replace("@VO@", vo).replace("@ST_OFF@", st_off).replace("@ST_SOFF@", st_soff)
             .replace("@LD_OFF@", ld_off).replace("@LD_SOFF@", ld_soff).replace("@HALO@", "\n".join(halo)).replace("@MAIN@", "\n".join(main)))
 
 
@@ -377,14 +451,23 @@ def test_buffer_offsets_stay_in_32_bits_at_the_contract_edges():
         cpp, exe = os.path.join(d, "audit.cpp"), os.path.join(d, "audit")
         open(cpp, "w").write(src)
         flags = ["-std=c++17", "-O1", "-fsanitize=signed-integer-overflow", "-fsanitize-trap=signed-integer-overflow", "-Wno-unused-variable"]
-        r = subprocess.run([_compiler(), *flags, cpp, "-o", exe], capture_output=True, text=True)
+        r = subprocess.run([_compiler(), *flags, "-I", CSRC, cpp, "-o", exe], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-3000:]
         r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    out = "\n".join(ln for ln in r.stdout.splitlines() if not ln.startswith("conv"))
+    out = "\n".join(ln for ln in r.stdout.splitlines() if not ln.startswith(("conv", "lwg_convt", "contract")))
     assert r.returncode >= 0, "signed overflow in an offset expression (trapped) at: " + r.stdout.strip().splitlines()[-1:].__repr__()
     assert r.returncode == 0, out[-3000:]
     kept, dropped = (int(v) for v in re.search(r"kept (\d+) dropped (\d+)", r.stdout).groups())
     assert kept > 10 ** 6 and dropped > 10 ** 6, r.stdout
+    # the block walks ran (every workgroup of every launch of _walk_cases(), XCD order on and off; their findings count as bad above)
+    assert int(re.search(r"walked (\d+)", r.stdout).group(1)) > 10 ** 5, r.stdout
+    # the entry points' contract (ctw_contract_ok with each kernel's panel) agrees with its restatement on both sides of every size limit
+    got = dict((int(i), int(v)) for i, v in re.findall(r"^contract (\d+) (\d)$", r.stdout, re.M))
+    cases = _contract_cases()
+    assert len(got) == len(cases)
+    for j, (fn, B, H, W, C0, N, YC, ydt) in enumerate(cases):
+        assert got[j] == int(_convt_ok(H, W, C0, YC)), (fn, B, H, W, C0, N, YC, ydt, got[j])
+    assert 0 < sum(got.values()) < len(cases)
 
 
 # ---- host limits ----
