@@ -157,6 +157,22 @@ int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, con
  * C -> C with C in {64, 128, 256}, no second input, LWG_EPI_NONE): the weights stay in registers and persistent workgroups
  * stream the rows - same panel layout with one step per 64-channel chunk. */
 int lwg_conv2d_nhwc_bf16_hr(const LwgConvArgs* args, lwg_stream_t stream);
+/* The 3 x 3 subset of the launches above (nine taps, stride = omul = 1, pad 1, OH = YH = H, OW = YW = W, ooy = oox = 0) as a fused F(2x2, 3x3)
+ * Winograd convolution on the bf16 matrix pipe (csrc/conv_winograd_bf16.hip; ops.conv_precision("bf16_winograd")): 4 multiplies per output instead
+ * of 9.  xdt = ydt = LWG_DT_BF16; one input or a skip concatenation (C0 % 64 == 0 and x1 given when C1 > 0); Cin % 64 == 0, N % 64 == 0,
+ * YC % 8 == 0, ycoff % 8 == 0, ycoff + N <= YC; any H, W and batch in ONE launch (per-image buffer descriptors: every IMAGE of an input < 3 GiB and
+ * the panel < 3 GiB, anything larger is refused - nothing is sliced and nothing wraps); dy / dx = the 3 x 3 grid ascending in (dy, dx);
+ * LWG_EPI_NONE, LWG_EPI_RESIDUAL or LWG_EPI_SPADE (N = 2 YC, ycoff = 0) with activation none / ReLU / tanh / sigmoid.  Anything else returns
+ * hipErrorInvalidValue before any launch.
+ * args->w = the bf16 fragment panel Upk[Cin/16][16][N][16]: element (ks, p, n, e) = bf16((G w G^T)[p / 4][p % 4]) for input channel 16 ks + e
+ * (concatenated order) and output column n, i.e. at element index ((ks * 16 + p) * N + n) * 16 + e, with G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
+ * and w[r][s] the weight of tap (dy, dx) = (r - 1, s - 1) (ipercore_amd.ops._wwino16 builds it from the fp32 GEMM panel in fp64, rounded once).
+ * LWG_EPI_SPADE: the columns (and args->bias) interleave gamma | beta in blocks of 4: column 8 m + r is gamma of output channel 4 m + r (r < 4)
+ * or beta of channel 4 m + r - 4 (r >= 4).
+ * Rounding points: V = B^T d B in fp32 from the bf16 halo, rounded once to bf16; U rounded once; accumulation, A^T M A, bias and epilogue in fp32;
+ * one rounding at the bf16 store.  Relative L2 error against fp64 1.2 - 1.9x the direct bf16 kernel's; not its bits: a precision mode of its own.
+ * A frame's result does not depend on the batch it is launched in (one kernel form, no split-K). */
+int lwg_conv2d_winograd_bf16(const LwgConvArgs* args, lwg_stream_t stream);
 /* First layer of a stream in bf16 mode (attlwb_spade_resunet.py:268-271 Encoder.0 on the 6-channel network input): x0 is the
  * fp32 NHWC-8 input (xdt = LWG_DT_F32, C0 = 8, C1 = 0), up to 10 taps, any stride, N = 64, bf16 output (ydt = LWG_DT_BF16),
  * bias + activation epilogue (LWG_EPI_NONE).  The input is rounded to bf16 in registers (one pixel's 8 channels = one MFMA

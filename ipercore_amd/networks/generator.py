@@ -233,6 +233,8 @@ class AttentionLWBGenerator(nn.Module):
         # "fp32": every layer on the direct kernel (the rounds 1-4 default; frames differ from "winograd" by ~3e-6);
         # "bf16": BASELINE configs[3] - every activation tensor of the engine is stored as bf16, the convs run on the bf16 MFMA kernel
         #   (fp32 accumulation), InstanceNorm statistics / attention / head read bf16; the first conv of a stream takes the fp32 input;
+        # "bf16_winograd": "bf16" in everything (storage, first layer, 1x1 / strided / transposed launches, fused head) except that the eligible
+        #   3x3 / stride 1 layers run the fused bf16 F(2x2,3x3) Winograd kernel (csrc/conv_winograd_bf16.hip): opt-in, not "bf16"'s bits;
         # "split": fp32 tensors, every product formed from six bf16 MFMAs (exact three-way operand split).
         self.conv_precision = "winograd"
 
@@ -285,7 +287,7 @@ class AttentionLWBGenerator(nn.Module):
             for f, st in zip(feats, sites):
                 if self.lwb_kind == "att":
                     n, h, w, _ = f.shape
-                    with ops.conv_precision("fp32" if self.conv_precision == "bf16" else self.conv_precision):     # the logit offset stays fp32
+                    with ops.conv_precision("fp32" if self.conv_precision in ("bf16", "bf16_winograd") else self.conv_precision):     # the logit offset stays fp32
                         kap = ops.conv2d(f.float(), st["fkap"], f.new_empty(n, h, w, 64, dtype=torch.float32))[..., 0].contiguous()
                     kv.append((ops.conv2d(f, st["fkq"], torch.empty_like(f)), ops.conv2d(f, st["fv"], torch.empty_like(f)), kap))
                 else:
@@ -379,8 +381,8 @@ class AttentionLWBGenerator(nn.Module):
         return ops.head_compose(x, head, bg, want_pred=want_pred and bg is not None, want_mask=want_mask, want_img=want_img, q4=q4)
 
     def _act_dtype(self):
-        """Storage type of the engine's activation tensors: bf16 in the "bf16" precision mode (BASELINE configs[3]), else fp32."""
-        return torch.bfloat16 if self.conv_precision == "bf16" else torch.float32
+        """Storage type of the engine's activation tensors: bf16 in the "bf16" and "bf16_winograd" precision modes (BASELINE configs[3]), else fp32."""
+        return torch.bfloat16 if self.conv_precision in ("bf16", "bf16_winograd") else torch.float32
 
     @torch.no_grad()
     def _run_bg_impl(self, bg4):
@@ -406,7 +408,7 @@ class AttentionLWBGenerator(nn.Module):
 
     def run_bg(self, *a, **k):
         # once per source, InstanceNorm after every conv: fp32 tensors in every mode ("split" still speeds up its products)
-        with ops.conv_precision("fp32" if self.conv_precision == "bf16" else self.conv_precision):
+        with ops.conv_precision("fp32" if self.conv_precision in ("bf16", "bf16_winograd") else self.conv_precision):
             return self._run_bg_impl(*a, **k)
 
     def run_src_decode(self, *a, **k):

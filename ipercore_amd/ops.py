@@ -32,6 +32,9 @@ def _ptr(t, dtype=torch.float32):
 # convolutions with Cin % 32 == 0 - one input or a skip concatenation (both channel counts % 8 == 0), plain / residual / SPADE (gamma | beta stacked)
 # epilogue, fp32 NHWC output - run as fused F(2x2, 3x3) Winograd convolutions on the fp32 matrix pipe (csrc/conv_winograd.hip: 16 multiplies per
 # 2x2 outputs instead of 36; fp32-grade, not bitwise the direct result); everything else exactly as "fp32" (same kernels, same head).
+# "bf16_winograd": "bf16" with the eligible 3x3 / stride 1 launches (_bf16_wino_eligible) on the fused bf16 F(2x2, 3x3) Winograd kernel
+# (csrc/conv_winograd_bf16.hip: 4 multiplies per output instead of 9; V and U rounded once to bf16 - 1.2-1.9x the direct bf16 kernel's error, not its
+# bits); every other bf16 launch exactly as in "bf16".
 CONV_PRECISION = "fp32"
 
 
@@ -41,7 +44,7 @@ class conv_precision(object):
     workgroups on a 64^2 layer: 3.6 against 2.4 ms per frame at frame batch 1), 20 % slower on frame batches.  Each engine is batch-invariant in itself."""
 
     def __init__(self, mode):
-        assert mode in ("fp32", "bf16", "split", "winograd", "winograd2x2")
+        assert mode in ("fp32", "bf16", "bf16_winograd", "split", "winograd", "winograd2x2")
         self.mode = mode
 
     def __enter__(self):
@@ -59,7 +62,7 @@ class conv_precision(object):
 
 # bench.py installs a callable(begin, M, spec, epi, info) to bracket conv entry-point calls with HIP events; info (the closing call only, else
 # None) = {"kernels": launches behind the call (lwg_conv_slice_count: batch slices), "kind": which kernel family ran ("direct", "winograd",
-# "split", "bf16", "up4")} - launch / executed-flop accounting only
+# "split", "bf16", "bf16_winograd", "up4")} - launch / executed-flop accounting only
 CONV_HOOK = None
 
 
@@ -69,7 +72,7 @@ def _stream():
 
 class ConvSpec:
     """Host description of one packed convolution (weights already in the kernel's layout)."""
-    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_w16v2", "_w16hr", "_w16x3", "_w16c8", "_w16up", "_w32up", "_wwino", "_wwino_t", "_wwino_t24", "_wwino4")
+    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_w16v2", "_w16hr", "_w16x3", "_w16c8", "_w16up", "_w32up", "_wwino", "_wwino_t", "_wwino_t24", "_wwino4", "_wwino16")
 
     def __init__(self, w, bias, N, Cin, taps, stride=1, omul=1, ooy=0, oox=0, algo_kn=None):
         self.w, self.bias, self.N, self.Cin = w, bias, int(N), int(Cin)
@@ -89,6 +92,7 @@ class ConvSpec:
         self._wwino_t = None
         self._wwino_t24 = None
         self._wwino4 = None
+        self._wwino16 = None
         self.cshift = 0
         if self.Cin % 32 != 0:
             q = self.Cin // 4
@@ -152,6 +156,70 @@ def _w16hr(spec, spade):
         panel = wk.reshape(cin // 64 * nt, 4, 16, N).permute(0, 1, 3, 2).contiguous().to(torch.bfloat16)
         spec._w16hr = (key, panel, bias)
     return spec._w16hr[1], spec._w16hr[2]
+
+
+BF16_WINO_MIN_CIN = 64  # "bf16_winograd": layers with fewer input channels stay on the direct kernel (a rule on the LAYER, never on the batch)
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def _bf16_wino_eligible(spec, x0, y, x1, epi, act, out_hw, ycoff=0):
+    """Launches of the "bf16_winograd" mode that run lwg_conv2d_winograd_bf16: the 3x3 subset of what _hr_eligible takes (stride 1, pad 1,
+    Cin % 64 == 0, N % 64 == 0, output grid = input grid) with a plain / residual / SPADE epilogue and Cin >= BF16_WINO_MIN_CIN - tested here
+    directly, so the lab switch BF16_HR does not reach this mode.  Never a rule on the batch."""
+    if spec.ntaps != 9 or spec.stride != 1 or spec.omul != 1 or spec.N % 64 != 0 or spec.Cin % 64 != 0 or spec.Cin < BF16_WINO_MIN_CIN:
+        return False
+    if (y.shape[1], y.shape[2]) != (x0.shape[1], x0.shape[2]) or (out_hw is not None and tuple(out_hw) != (x0.shape[1], x0.shape[2])):
+        return False
+    if sorted(zip(spec.dy, spec.dx)) != _WINO_TAPS or epi not in (EPI_NONE, EPI_RESIDUAL, EPI_SPADE):
+        return False
+    if act not in (ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID) or y.dtype != torch.bfloat16:
+        return False
+    if x1 is not None and (x1.dtype != torch.bfloat16 or x0.shape[3] % 64 != 0):
+        return False
+    if epi == EPI_SPADE:
+        return y.shape[3] * 2 == spec.N and ycoff == 0
+    return y.shape[3] % 8 == 0 and ycoff % 8 == 0 and ycoff + spec.N <= y.shape[3]
+
+
+def wwino16_index(ks, p, n, e, N):
+    """Element index of (k-step ks, product p = 4 xi + nu, output column n, channel e of the k-step) in lwg_conv2d_winograd_bf16's panel
+    Upk[Cin/16][16][N][16] (include/lwg_hip.h): the value there is bf16((G w G^T)[xi][nu]) of input channel 16 ks + e and column n."""
+    return ((ks * 16 + p) * N + n) * 16 + e
+
+
+def wwino16_spade_column(j):
+    """SPADE launches: (output channel, is_beta) of panel column j - gamma | beta interleaved in blocks of 4."""
+    return 4 * (j // 8) + j % 4, (j % 8) // 4
+
+
+def _wwino16(spec, spade):
+    """(panel, bias) of lwg_conv2d_winograd_bf16, built once per (spec, spade) from the fp32 GEMM panel with torch ops on whatever device spec.w
+    is on: U = G w G^T per (input channel, output column) in fp64, rounded ONCE to bf16, stored Upk[Cin/16][16][N][16] (wwino16_index); for the
+    SPADE epilogue the gamma | beta columns (and the bias) go from the GEMM panel's blocks of 32 to blocks of 4 (wwino16_spade_column)."""
+    key = bool(spade)
+    if spec._wwino16 is None or spec._wwino16[0] != key or spec._wwino16[1].device != spec.w.device:
+        K4, N, _ = spec.w.shape
+        cin, nt = spec.Cin, spec.ntaps
+        assert nt == 9 and cin % 64 == 0 and N % 64 == 0 and K4 * 4 == nt * cin, (cin, nt, K4, N)
+        dev = spec.w.device
+        # fp32 GEMM panel [K/4][N][4], k = ((c / 32) * 9 + tap) * 32 + c % 32  ->  w[tap][c][n]
+        wk = spec.w.permute(0, 2, 1).reshape(cin // 32, nt, 32, N).permute(1, 0, 2, 3).reshape(nt, cin, N)
+        order = [0] * 9
+        for t in range(nt):
+            order[3 * (spec.dy[t] + 1) + spec.dx[t] + 1] = t
+        w33 = wk[order].reshape(3, 3, cin, N).to(torch.float64)                                    # [r][s][c][n], tap (dy, dx) = (r - 1, s - 1)
+        G = torch.tensor(_WINO_G, dtype=torch.float64, device=dev)
+        U = torch.einsum("ar,rscn,bs->abcn", G, w33, G)                                            # [xi][nu][c][n]
+        bias = spec.bias
+        if spade:
+            j = torch.arange(N, device=dev)
+            ch, beta = 4 * (j // 8) + j % 4, (j % 8) // 4
+            old = 64 * (ch // 32) + (ch % 32) + 32 * beta
+            U = U[:, :, :, old]
+            bias = None if bias is None else bias[old].contiguous()
+        panel = U.reshape(16, cin // 16, 16, N).permute(1, 0, 3, 2).contiguous().to(torch.bfloat16)   # [ks][p][n][e]
+        spec._wwino16 = (key, panel, bias)
+    return spec._wwino16[1], spec._wwino16[2]
 
 
 BF16_HR = True          # lab switch: False routes every bf16 convolution to lwg_conv2d_nhwc_bf16 (LDS-DMA kernels)
@@ -349,7 +417,14 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         # bf16 activation storage (BASELINE configs[3]): bf16 in, bf16 out, bf16 MFMA operands, fp32 accumulation
         if y.dtype != torch.bfloat16 or spec.Cin % 64 != 0:
             raise ValueError("bf16 convolutions need bf16 outputs and Cin % 64 == 0")
-        if _hr_eligible(spec, x0, y, out_hw) or _pw_eligible(spec, x0, y, x1, epi, out_hw):
+        if CONV_PRECISION == "bf16_winograd" and _bf16_wino_eligible(spec, x0, y, x1, epi, act, out_hw, ycoff):
+            kind, sliced = "bf16_winograd", False       # per-image buffer descriptors: one launch at any batch size
+            panel, bias = _wwino16(spec, epi == EPI_SPADE)
+            a.w, a.bias = _ptr(panel, torch.bfloat16), _ptr(bias)
+            for i, (dy, dx) in enumerate(_WINO_TAPS):                # the panel's tap order
+                a.dy[i], a.dx[i] = dy, dx
+            _lib.check(_lib.lib().lwg_conv2d_winograd_bf16(a, _stream()), "lwg_conv2d_winograd_bf16")
+        elif _hr_eligible(spec, x0, y, out_hw) or _pw_eligible(spec, x0, y, x1, epi, out_hw):
             panel, bias = _w16hr(spec, epi == EPI_SPADE)
             a.w, a.bias = _ptr(panel, torch.bfloat16), _ptr(bias)
             for i, t in enumerate(_hr_tap_order(spec)):              # the panel's tap order
