@@ -29,7 +29,7 @@
 // the direct kernel's result - which is why it is a precision mode of its own.
 #include <hip/hip_runtime.h>
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_wino.h"
 
 #define WG_THREADS 512
 #define TPB 8            // patches per block edge: 8 x 8 patches = 16 x 16 output pixels
@@ -46,7 +46,6 @@
 #define LOOP_FLOATS (DUMP_OFF + DUMP_FLOATS)
 #define MS_FLOATS (8 * NPATCH * (NB + 4))    // the epilogue's exchange buffer [xi (4)][output column (2)][patch (64)][n (NBV) + 4]: rows of NBV + 4
                                              // floats - 16-byte accesses of eight consecutive patches then cover all banks once (68 j, 36 j = 4 j mod 32)
-#define WINO_OOB 0xC0000000u                 // >= any image's byte size (host: H * W * C * 4 < 3 GiB): the buffer load returns 0
 #define WSB() __builtin_amdgcn_sched_barrier(0)
 
 // lab instrumentation (compiled out of the product): tools/winoshapes.py --ts / --ts2 on -DLWG_WINO_TS / -DLWG_WINO_TS2 variant libraries
@@ -66,12 +65,6 @@
 #define WTS2(k) do { } while (0)
 #endif
 
-template <int V> struct IntC { static constexpr int value = V; };
-
-__device__ __forceinline__ floatx4 wino_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-
 // NBV = output channels per workgroup.  64: the form described above.  32 (small launches - a frame or two -, plain / residual epilogues): the
 // same 64 patches x 32 channels, wave w = (xi = w % 4, patch tile w / 4) with ONE accumulator tile per product: twice the workgroups of half the
 // matrix work each, so that a launch that would leave most of the chip idle fills it.  Every output element is accumulated over the stages and
@@ -79,9 +72,7 @@ __device__ __forceinline__ floatx4 wino_buf_load(__amdgpu_buffer_rsrc_t r, unsig
 // SPLIT (training launches that leave half the chip or more idle; NBV = 32, plain epilogue): blockIdx.z owns the stages [z a.cshift, (z + 1) a.cshift)
 // of the K loop (a.cshift - unused by convolutions with Cin >= 32 - carries the stages per slice here) and leaves raw sums in its dense (M, N) slab
 // a.y + z M N (the host passes YC = N, ycoff = 0, no bias, no activation); lwg_splitk_finish_kernel adds the slabs in slice order and finishes.
-// TWO (round 6): the launch has a second input (skip concatenation).  One-input launches - four fifths of the engine's time - carry no per-load choice
-// of the source tensor at all: as a uniform branch pair around every halo load it cost 1.9 % of the K loop and 700 cycles of every block's set-up
-// (profiles/r06_k_*); the two-input form selects the descriptor / offset (scalar selects + one v_cndmask per load) instead of branching.
+// TWO: the launch has a second input (skip concatenation; lwg_conv_wino.h: CwBlock).
 template <int EPI, int NBV, bool SPLIT = false, bool TWO = false>
 __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const LwgConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -95,46 +86,29 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const 
     float* const Vs0 = smem + 2 * RAW_FLOATS;                // [2][VS]
     float* Ms = smem;                                        // the epilogue's exchange buffer (after the K loop)
     const int tid = threadIdx.x, lane = tid & 63;
-    const int bx = (W + 2 * TPB - 1) / (2 * TPB), by = (H + 2 * TPB - 1) / (2 * TPB);
     // PERSISTENT WORKGROUPS (round 6): the grid is min(blocks, CUs) workgroups (the chip holds one per CU: LDS) and a workgroup walks the block ids
     // blockIdx.x, blockIdx.x + gridDim.x, ... (id = column block * tiles + tile: the order the 2-D grid of round 5 was dispatched in).  What that
     // buys: the first halo stages and weight fragments of block k + 1 are REQUESTED before block k's epilogue exchange and land under it (the
     // prologue's exposed global round trip, ~1/2 of its 6.3 k cycles, is gone), and the per-workgroup dispatch / descriptor set-up is paid once.
     // A block's arithmetic does not depend on which workgroup runs it: results are bitwise those of the one-block-per-workgroup form.
-    const int tiles = bx * by * a.B;
-    const int total = tiles * (N / NBV);
+    const CwGrid g = cw_grid(a.B, H, W, N, 2 * TPB, 2 * TPB, NBV);
+    const CwOrder o = cw_order(CW_COLMAJOR, gridDim.x, blockIdx.x, N / NBV, g);
     int blk = blockIdx.x;
     const int nst_all = Cin / KS;                            // even (host: Cin % 16 == 0)
     const int sbeg = SPLIT ? (int)blockIdx.z * a.cshift : 0; // this workgroup's first stage and its number of stages (even as well)
     const int nst = SPLIT ? (a.cshift < nst_all - sbeg ? a.cshift : nst_all - sbeg) : nst_all;
     WTS(0);
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(64u * (unsigned)Cin * (unsigned)N), 0x00020000);
-    // ---- per-block state (workgroup-uniform): image b, tile corner (x0, y0), first output column n0; this image of each input as a buffer
-    int b, x0, y0, n0;
-    __amdgpu_buffer_rsrc_t rx0, rx1;
-    unsigned voff0[2], voff1[2];                             // this thread's two halo elements (pixel, channel quad): byte offsets inside either input
+    // ---- per-block state (workgroup-uniform; lwg_conv_wino.h): image, tile corner, first output column, the inputs' buffers, the two halo offsets
+    CwBlock<2, TWO> bk;
     unsigned uvoff;                                          // this lane's column of the fragment panel
     const int nbw_ = (NBV / 32) == 2 ? wid >> 2 : 0;
     auto setup = [&](int id) {
-        const int cb = __builtin_amdgcn_readfirstlane(id / tiles);
-        int t = __builtin_amdgcn_readfirstlane(id - cb * tiles);
-        b = __builtin_amdgcn_readfirstlane(t / (bx * by));
-        t -= b * bx * by;
-        x0 = (t % bx) * 2 * TPB;
-        y0 = (t / bx) * 2 * TPB;
-        n0 = cb * NBV;
-        rx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x0 + (size_t)b * H * W * a.C0), 0, (int)((unsigned)(H * W) * (unsigned)a.C0 * 4u), 0x00020000);
-        if constexpr (TWO) rx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x1 + (size_t)b * H * W * a.C1), 0, (int)((unsigned)(H * W) * (unsigned)a.C1 * 4u), 0x00020000);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {                        // padding pixels / threads without a halo element: an out-of-range offset (zeros)
-            const int i = tid + WG_THREADS * q;
-            const int pix = i >> 1, half = i & 1, py = pix / HALO, px = pix - py * HALO;
-            const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-            const bool in = i < PLANE * 2 && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            voff0[q] = in ? (unsigned)((gy * W + gx) * a.C0 + 4 * half) * 4u : WINO_OOB;
-            if constexpr (TWO) voff1[q] = in ? (unsigned)((gy * W + gx) * a.C1 + 4 * half) * 4u : WINO_OOB;
-        }
-        uvoff = (unsigned)(((lane >> 5) * N + n0 + nbw_ * 32 + (lane & 31)) * 16);
+        int cb, t;
+        cw_block(o, id, cb, t);
+        bk.locate(a, g, t, 2 * TPB, 2 * TPB, cw_n0(cb, NBV));
+        bk.halo(a, tid, WG_THREADS, HALO, PLANE * 2);
+        uvoff = (unsigned)(((lane >> 5) * N + bk.n0 + nbw_ * 32 + (lane & 31)) * 16);
     };
     setup(blk);
     const int xi = wid & 3;                                   // this wave's row of the transformed patch
@@ -150,28 +124,14 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const 
         wst[q] = i < PLANE * 2 ? 4 * half * PLANE + pix : DUMP_OFF + tid;
     }
     floatx4 rreg[2];
-    auto rld1 = [&](int st, int q) -> floatx4 {              // a stage's 8 channels lie in ONE input (C0 % 8 == 0)
-        const int c = (st + sbeg) * KS;
-        if constexpr (!TWO) {
-            return wino_buf_load(rx0, voff0[q], (unsigned)c * 4u);
-        } else {
-            const bool first = c < a.C0;
-            const __amdgpu_buffer_rsrc_t r = first ? rx0 : rx1;
-            const unsigned v = first ? voff0[q] : voff1[q];
-            return wino_buf_load(r, v, (unsigned)(first ? c : c - a.C0) * 4u);
-        }
-    };
-    auto rst1 = [&](int buf, int q, floatx4 v) {
-        float* dst = raw0 + buf * RAW_FLOATS + wst[q];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k * PLANE] = v[k];
-    };
+    auto rld1 = [&](int st, int q) -> floatx4 { return bk.rld1(a, (st + sbeg) * KS, q); };      // a stage's 8 channels lie in ONE input (C0 % 8 == 0)
+    auto rst1 = [&](int buf, int q, floatx4 v) { cw_rst1(raw0 + buf * RAW_FLOATS + wst[q], PLANE, v); };
     floatx4 ufr[2][4];                                       // [register set][product nu]: the four k-pairs of this lane's row (channel)
     const unsigned ustage = (unsigned)N * 32u;               // bytes between two stages of a product: [2][N][4] floats
     unsigned usoff[4];
 #pragma unroll
     for (int nu = 0; nu < 4; ++nu) usoff[nu] = ((unsigned)(4 * xi + nu) * (unsigned)nst_all + (unsigned)sbeg) * ustage;
-    auto uld1 = [&](int st, int nu) -> floatx4 { return wino_buf_load(ru, uvoff, usoff[nu] + (unsigned)st * ustage); };
+    auto uld1 = [&](int st, int nu) -> floatx4 { return cw_buf_load(ru, uvoff, usoff[nu] + (unsigned)st * ustage); };
     const int patch = tid & 63, tc = tid >> 6;
     const int pty = patch >> 3, ptx = patch & 7;
     const float* const dbase = raw0 + tc * PLANE + (2 * pty) * HALO + 2 * ptx;      // this thread's 4 x 4 input patch inside raw[0]
@@ -390,7 +350,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const 
         for (int i = 0; i < 16; ++i)
             reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res))[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + wid) * 16 + i] = ts2[i];
 #endif
-    const int eb = b, ex0 = x0, ey0 = y0, en0 = n0;          // this block's coordinates (the state moves on to the next block below)
+    const int eb = bk.b, ex0 = bk.x0, ey0 = bk.y0, en0 = bk.n0;          // this block's coordinates (the state moves on to the next block below)
     // epilogue: M A in registers (two values per product row, patch, channel), ONE exchange through LDS [xi][column][patch][n], then a thread owns
     // one patch x the channel quads n4.. and 32 + n4..: 16 conflict-free 16-byte LDS reads, A^T (.) over xi, bias, (residual | SPADE modulation),
     // activation, 16-byte NHWC stores (the residual / xn values are fetched before the exchange).  LWG_EPI_SPADE: the block's 64 columns are
@@ -451,7 +411,7 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const 
     // 64-channel form does not have)
     WTSB(1, 54);
     const int nblk = blk + (int)gridDim.x;
-    const bool more = !SPLIT && nblk < total;
+    const bool more = !SPLIT && cw_has_block(o, nblk);
     if constexpr (!SPLIT) {
         setup(more ? nblk : blk);
         issue_loads();
@@ -515,12 +475,10 @@ __global__ __launch_bounds__(WG_THREADS, 1) void lwg_conv_winograd_kernel(const 
     WTS(42);
 }
 
-
 // The fragment panel from the fp32 GEMM panel of the same convolution (lwg_conv2d_nhwc_f32's w: [9 Cin / 4][N][4], k = ((c / 32) 9 + tap) 32 + c % 32):
 // U = G w G^T per (input channel, output column) in fp64, rounded once, written as Upk[16][Cin/8][2][N][4] - one thread per (c, n).  tap9[3 r + s] =
 // the tap index of kernel position (dy, dx) = (r - 1, s - 1) in that panel.  Inference builds it once per weight version; the personalization step
 // once per convolution call (the weights change every step).
-struct LwgWinoTaps { int t[9]; };
 
 // one thread = one output column n x the FOUR input channels 8 s + kh + {0, 2, 4, 6} that share a 16-byte element of the panel: sixteen coalesced
 // 16-byte stores per thread (a thread per channel wrote 4 bytes of each: 2.2 TB/s, r05_g)
@@ -578,12 +536,8 @@ __global__ __launch_bounds__(256) void lwg_winograd_panels_kernel(const LwgWinoD
 }
 
 extern "C" int lwg_winograd_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream_) {
-    if (!wpanel || !upk || !tap9 || Cin <= 0 || (Cin % 32) != 0 || N <= 0) return (int)hipErrorInvalidValue;
     LwgWinoTaps taps;
-    for (int i = 0; i < 9; ++i) {
-        if (tap9[i] < 0 || tap9[i] > 8) return (int)hipErrorInvalidValue;
-        taps.t[i] = tap9[i];
-    }
+    if (!cw_panel_args_ok(wpanel, upk, Cin, N, tap9, taps)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(lwg_winograd_panel_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((Cin + 15) / 16)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream_), wpanel, upk, Cin, N, taps);
     return (int)hipGetLastError();
@@ -595,13 +549,10 @@ extern "C" int lwg_winograd_panels_f32(const LwgWinoDesc* descs_dev, int ndesc, 
     return (int)hipGetLastError();
 }
 
-
-// args: the launch description of the 3 x 3 / stride 1 / pad 1 convolution as lwg_conv2d_nhwc_f32 takes it (nine taps, omul = 1, OH = H, OW = W,
-// one or two inputs with C0 % 8 == 0, C1 % 8 == 0 and (C0 + C1) % 16 == 0, N % 64 == 0, YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL (ycoff % 4 == 0)
-// or LWG_EPI_SPADE (N = 2 YC, columns gamma | beta interleaved in blocks of 32, ycoff = 0); any activation of lwg_act; every image of an input
-// < 3 GiB) EXCEPT args->w = the Winograd fragment panel Upk[16][Cin/8][2][N][4]: element (p, s, kh, n, kk) = (G w G^T)[xi = p / 4][nu = p % 4] of
-// input channel 8 s + 2 kk + kh (concatenated order) and output column n.
-static bool lwg_wino_contract(const LwgConvArgs& a);
+// args: lwg_conv_wino.h's fp32 contract with args->w = the Winograd fragment panel Upk[16][Cin/8][2][N][4], 64 bytes per (input channel, output
+// column); the outputs are stored through 64-bit pointers
+static bool lwg_wino_contract(const LwgConvArgs& a) { return cw_contract_ok(a, 64ull, CW_NO_OUT_BUFFER); }
+static long long lwg_wino_blocks(const LwgConvArgs& a, int nbv) { return cw_total_blocks(a.B, a.H, a.W, a.N, 2 * TPB, 2 * TPB, nbv); }
 
 // Split plan of a training launch (0 = run it whole): a launch whose 64-patch x 32-channel workgroups cover half the CUs or less runs its K loop
 // in 2 .. 8 slices of >= 8 stages (64 input channels; each slice pays the prologue and the epilogue again) - twice to eight times the workgroups.
@@ -609,8 +560,7 @@ static bool lwg_wino_contract(const LwgConvArgs& a);
 static int lwg_wino_split_plan(const LwgConvArgs& a, int* stages_per_slice) {
     const bool mask = a.epi == LWG_EPI_RESIDUAL && a.act == LWG_ACT_RELU_MASK;
     if (!LWG_WINO_SPLITK || (a.epi != LWG_EPI_NONE && !mask)) return 0;
-    const int bx = (a.W + 2 * TPB - 1) / (2 * TPB), by = (a.H + 2 * TPB - 1) / (2 * TPB);
-    const long blocks32 = (long)bx * by * a.B * (a.N / 32);
+    const long long blocks32 = lwg_wino_blocks(a, 32);
     if (blocks32 > 128) return 0;
     const int nst = (a.C0 + a.C1) / KS;
     int want = (int)(256 / blocks32);
@@ -630,33 +580,11 @@ extern "C" size_t lwg_conv2d_winograd_ws_floats(const LwgConvArgs* pa) {
     return (size_t)lwg_wino_split_plan(*pa, &sps) * (size_t)pa->M * (size_t)pa->N;
 }
 
-extern "C" int lwg_conv2d_winograd_f32_ws(const LwgConvArgs* pa, float* ws, lwg_stream_t stream_);
-extern "C" int lwg_conv2d_winograd_f32(const LwgConvArgs* pa, lwg_stream_t stream_) { return lwg_conv2d_winograd_f32_ws(pa, nullptr, stream_); }
-
-static bool lwg_wino_contract(const LwgConvArgs& a) {
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 9 || a.stride != 1 || a.omul != 1 || a.C0 <= 0 || (a.C0 % KS) != 0 || a.C1 < 0 ||
-        (a.C1 % KS) != 0 || ((a.C0 + a.C1) % (2 * KS)) != 0 || (a.C1 > 0 && !a.x1) || a.N <= 0 || (a.N % NB) != 0 || a.OH != a.H || a.OW != a.W ||
-        a.YH != a.H || a.YW != a.W || a.xdt != LWG_DT_F32 || a.ydt != LWG_DT_F32 || a.M != a.B * a.H * a.W || a.ycoff < 0 || (a.ycoff % 4) != 0 ||
-        (a.YC % 4) != 0 || (a.act == LWG_ACT_RELU_MASK && a.epi != LWG_EPI_RESIDUAL))
-        return false;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.YC * 2 != a.N || a.ycoff != 0) return false;
-    } else {
-        if (a.ycoff + a.N > a.YC) return false;
-        if (a.epi != LWG_EPI_NONE && (a.epi != LWG_EPI_RESIDUAL || !a.res)) return false;
-    }
-    const unsigned long long cmax = (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1);
-    if ((unsigned long long)a.H * a.W * cmax * 4ull >= (unsigned long long)WINO_OOB || 64ull * (a.C0 + a.C1) * a.N >= 0xffffffffull)
-        return false;
-    return true;
-}
-
 // small launches (a frame or two): blocks of 64 patches x 32 channels when that shortens the launch - the chip holds one workgroup per CU (LDS), a
 // launch is ceil(blocks / CUs) rounds, and a half-size block costs ~0.55 of a full one (same per-stage overheads on half the MFMAs).  Same bits.
 static bool lwg_wino_small(const LwgConvArgs& a, int cus) {
-    const int bx = (a.W + 2 * TPB - 1) / (2 * TPB), by = (a.H + 2 * TPB - 1) / (2 * TPB);
-    const long blocks64 = (long)bx * by * a.B * (a.N / NB);
-    const long rounds64 = (blocks64 + cus - 1) / cus, rounds32 = (2 * blocks64 + cus - 1) / cus;
+    const long long blocks64 = lwg_wino_blocks(a, NB);
+    const long long rounds64 = (blocks64 + cus - 1) / cus, rounds32 = (2 * blocks64 + cus - 1) / cus;
     return a.epi != LWG_EPI_SPADE && (double)rounds32 * 0.55 < (double)rounds64;
 }
 
@@ -666,18 +594,23 @@ static bool lwg_wino_small(const LwgConvArgs& a, int cus) {
 extern "C" int lwg_conv2d_winograd_plan(const LwgConvArgs* pa, int with_ws, long long* blocks, int* slices, int* nbv, int* workgroups) {
     if (!pa || !lwg_wino_contract(*pa)) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    const int bx = (a.W + 2 * TPB - 1) / (2 * TPB), by = (a.H + 2 * TPB - 1) / (2 * TPB);
-    const long tiles = (long)bx * by * a.B;
     int sps = 0;
     const int sl = with_ws ? lwg_wino_split_plan(a, &sps) : 0;
     const int cus = lwg_device_cus();
     const int v = sl > 1 ? 32 : (lwg_wino_small(a, cus) ? 32 : NB);
-    const long long nb = (long long)tiles * (a.N / v) * (sl > 1 ? sl : 1);
+    const long long nb = lwg_wino_blocks(a, v) * (sl > 1 ? sl : 1);
     if (blocks) *blocks = nb;
     if (slices) *slices = sl > 1 ? sl : 0;
     if (nbv) *nbv = v;
     if (workgroups) *workgroups = (int)(sl > 1 ? nb : (nb < cus ? nb : cus));
     return 0;
+}
+
+// one epilogue / block width of the whole-K form, with one or two inputs
+template <int EPI, int NBV>
+static int lwg_wino_go(const LwgConvArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
+    return a.C1 > 0 ? cw_launch<lwg_conv_winograd_kernel<EPI, NBV, false, true>>(grid, WG_THREADS, lds, stream, a)
+                    : cw_launch<lwg_conv_winograd_kernel<EPI, NBV, false, false>>(grid, WG_THREADS, lds, stream, a);
 }
 
 // ws: NULL, or lwg_conv2d_winograd_ws_floats(args) floats - a launch that would leave half the chip idle then runs split over K through it.
@@ -687,16 +620,10 @@ extern "C" int lwg_conv2d_winograd_f32_ws(const LwgConvArgs* pa, float* ws, lwg_
     const LwgConvArgs& a = *pa;
     const size_t loop = (size_t)LOOP_FLOATS * 4, epi = (size_t)MS_FLOATS * 4;
     const size_t lds = loop > epi ? loop : epi;
-    const int bx = (a.W + 2 * TPB - 1) / (2 * TPB), by = (a.H + 2 * TPB - 1) / (2 * TPB);
     const int cus = lwg_device_cus();
-    const bool small = lwg_wino_small(a, cus);
-    static unsigned long long done[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool two = a.C1 > 0;
     int sps = 0;
     const int slices = ws ? lwg_wino_split_plan(a, &sps) : 0;
     if (slices > 1) {
-        auto kern = two ? lwg_conv_winograd_kernel<LWG_EPI_NONE, 32, true, true> : lwg_conv_winograd_kernel<LWG_EPI_NONE, 32, true, false>;
-        if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, done[two ? 11 : 5]); e != hipSuccess) return (int)e;
         LwgConvArgs part = a;                                // raw sums into the slabs: dense (M, N) rows, no bias / residual / activation
         part.y = ws;
         part.YC = a.N;
@@ -706,31 +633,15 @@ extern "C" int lwg_conv2d_winograd_f32_ws(const LwgConvArgs* pa, float* ws, lwg_
         part.act = LWG_ACT_NONE;
         part.res = nullptr;
         part.cshift = sps;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(bx * by * a.B * (a.N / 32)), 1u, (unsigned)slices), dim3(WG_THREADS), lds, stream, part);
-        return (int)lwg_splitk_finish_launch(a, ws, slices, stream);
+        const dim3 grid((unsigned)lwg_wino_blocks(a, 32), 1u, (unsigned)slices);
+        const int e = a.C1 > 0 ? cw_launch<lwg_conv_winograd_kernel<LWG_EPI_NONE, 32, true, true>>(grid, WG_THREADS, lds, stream, part)
+                               : cw_launch<lwg_conv_winograd_kernel<LWG_EPI_NONE, 32, true, false>>(grid, WG_THREADS, lds, stream, part);
+        return e != (int)hipSuccess ? e : (int)lwg_splitk_finish_launch(a, ws, slices, stream);
     }
-    // persistent workgroups: one per CU (LDS) at most, each walking block ids blockIdx.x + k gridDim.x (LWG_WINO_PERSIST = 0: one block per workgroup)
-    const long total = (long)bx * by * a.B * (a.N / (small ? 32 : NB));
-    const dim3 grid((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total));
-#define LWG_WINO_GO2(E, V, T, SLOT)                                                                                                   \
-    {                                                                                                                                 \
-        if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_conv_winograd_kernel<E, V, false, T>), lds, done[SLOT]); e != hipSuccess) \
-            return (int)e;                                                                                                            \
-        hipLaunchKernelGGL((lwg_conv_winograd_kernel<E, V, false, T>), grid, dim3(WG_THREADS), lds, stream, a);                       \
-    }
-#define LWG_WINO_GO(E, V, SLOT)                                                                                                       \
-    {                                                                                                                                 \
-        if (two) LWG_WINO_GO2(E, V, true, SLOT + 6) else LWG_WINO_GO2(E, V, false, SLOT)                                              \
-    }
-    if (a.epi == LWG_EPI_SPADE) LWG_WINO_GO(LWG_EPI_SPADE, 64, 2)
-    else if (a.epi == LWG_EPI_RESIDUAL) {
-        if (small) LWG_WINO_GO(LWG_EPI_RESIDUAL, 32, 3)
-        else LWG_WINO_GO(LWG_EPI_RESIDUAL, 64, 1)
-    } else {
-        if (small) LWG_WINO_GO(LWG_EPI_NONE, 32, 4)
-        else LWG_WINO_GO(LWG_EPI_NONE, 64, 0)
-    }
-#undef LWG_WINO_GO
-#undef LWG_WINO_GO2
-    return (int)hipGetLastError();
+    const bool small = lwg_wino_small(a, cus);
+    const dim3 grid = cw_persistent_grid(lwg_wino_blocks(a, small ? 32 : NB), cus);
+    if (a.epi == LWG_EPI_SPADE) return lwg_wino_go<LWG_EPI_SPADE, 64>(a, grid, lds, stream);
+    if (a.epi == LWG_EPI_RESIDUAL) return small ? lwg_wino_go<LWG_EPI_RESIDUAL, 32>(a, grid, lds, stream) : lwg_wino_go<LWG_EPI_RESIDUAL, 64>(a, grid, lds, stream);
+    return small ? lwg_wino_go<LWG_EPI_NONE, 32>(a, grid, lds, stream) : lwg_wino_go<LWG_EPI_NONE, 64>(a, grid, lds, stream);
 }
+extern "C" int lwg_conv2d_winograd_f32(const LwgConvArgs* pa, lwg_stream_t stream_) { return lwg_conv2d_winograd_f32_ws(pa, nullptr, stream_); }

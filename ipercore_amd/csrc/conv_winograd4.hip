@@ -20,7 +20,7 @@
 // and not the F(2x2, 3x3) kernel's bits.  A frame's result does not depend on the batch it is launched in (per-image work in a fixed order).
 #include <hip/hip_runtime.h>
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_wino.h"
 
 #define W4_THREADS 512
 #define W4_PBX 8             // patches per block row: 32 output pixels
@@ -48,7 +48,6 @@
 #define W4_NPL 28                                // planes: rows 0..3 x 4 output columns, rows 4 / 5: 2 halves x 3 partial sums
 #define W4_MS (W4_NPL * 16 * W4_MSR)             // one pass = 16 patches
 #define W4_BIAS_OFF (W4_LOOP > W4_MS ? W4_LOOP : W4_MS)          // the block's 64 bias values, behind both uses of the LDS
-#define W4_OOB 0xC0000000u
 #ifndef LWG_W4_XCD
 #define LWG_W4_XCD 1         // XCD-aware block order (see the kernel): 0 = off (lab)
 #endif
@@ -72,11 +71,6 @@
 #define W4TSA(i) do { } while (0)
 #endif
 
-template <int V> struct W4Int { static constexpr int value = V; };
-
-__device__ __forceinline__ floatx4 w4_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
 #ifndef W4_NT
 #define W4_NT 0              // cache policy of the activation traffic (halo loads, output stores): 0 = default; 2 = non-temporal: measured 20 % SLOWER (profiles/r06_w_*)
 #endif
@@ -91,9 +85,6 @@ __device__ __forceinline__ floatx4 w4_buf_load(__amdgpu_buffer_rsrc_t r, unsigne
                              // panel and halo lines out of the XCD's L2: +0.4-0.6 % in the step (A/B/A/B and five policies, profiles/r06_ay_*; the halo LOADS
                              // non-temporal were the 20 % loss of r06_w)
 #endif
-__device__ __forceinline__ floatx4 w4_buf_load_nt(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, W4_NT_LD));
-}
 
 // the 1-D input transform B^T (.) of six values
 __device__ __forceinline__ void w4_bt6(const float (&r)[6], float (&v)[6]) {
@@ -114,9 +105,7 @@ __device__ __forceinline__ void w4_bt6(const float (&r)[6], float (&v)[6]) {
 // its batch (check_winograd4: frame n of a 40-frame launch = the frame alone, across the forms).
 template <int EPI, bool TWO, bool SM = false>
 __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_kernel(const LwgConvArgs a) {
-    // (SM with the SPADE epilogue: the block's 32 accumulator rows are gamma | beta of the SAME 16 channels - columns n0 .. + 15 and n0 + 32 .. + 47 of the
-    // stacked panel, n0 = 64 (block / 2) + 16 (block % 2) - so the modulation still finds both in one block)
-    constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;
+    constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;          // (its 32 accumulator rows: gamma | beta of the SAME 16 channels, cw4_n0_spade_small)
     constexpr int NVP = SM && !SMS ? 2 : 1;                  // patches per reader thread and pass
     constexpr int NTH = SM ? 256 : W4_THREADS;               // threads per workgroup
     constexpr int NQ = SM ? 5 : W4_NQ;                       // halo pieces per thread and stage
@@ -131,74 +120,26 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
     float* const raw0 = smem;                                // [2][RAW], then [2][VS]
     float* const Ms = smem;                                  // the epilogue's exchange buffer (after the K loop)
     const int tid = threadIdx.x, lane = tid & 63;
-    const int bx = (W + 4 * W4_PBX - 1) / (4 * W4_PBX), by = (H + 4 * W4_PBY - 1) / (4 * W4_PBY);
-    // persistent workgroups (as conv_winograd.hip): min(blocks, CUs) workgroups walk the block ids blockIdx.x + k gridDim.x (id = column block * tiles + tile)
-    const int tiles = bx * by * a.B;
-    const int total = tiles * (N / NBV);
+    // persistent workgroups (as conv_winograd.hip): min(blocks, CUs) workgroups walk the block ids blockIdx.x + k gridDim.x in one of three block
+    // orders - XCD-aware, chunked, column-block-major (lwg_conv_wino.h: cw4_order_kind)
+    const CwGrid g = cw_grid(a.B, H, W, N, 4 * W4_PBX, 4 * W4_PBY, NBV);
+    const CwOrder o = cw_order(cw4_order_kind(LWG_W4_XCD, LWG_W4_CHUNK, SM, gridDim.x, N / NBV, Cin, N, g.tiles, g.total), gridDim.x, blockIdx.x, N / NBV, g);
     int blk = blockIdx.x;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(144u * (unsigned)Cin * (unsigned)N), 0x00020000);
     const int q = wid & 3, ct = SM ? 0 : wid >> 2;           // this wave's product set and 32-channel tile
     const int half = SM ? 0 : wid >> 2;                      // ... and its half of the input transform (rows 3 half .. 3 half + 2 of B^T d B; SM: both)
     floatx16 acc[9];                                         // products 0..5: (xi = q, nu); 6..8: (xi = 4 + q / 2, nu = 3 (q % 2) + 0..2)
-    int b, x0, y0, n0;
-    __amdgpu_buffer_rsrc_t rx0, rx1;
-    unsigned voff0[NQ], voff1[NQ];                     // this thread's halo elements (pixel, channel quad): byte offsets inside either input
+    CwBlock<NQ, TWO> bk;                                     // the per-block state (lwg_conv_wino.h), this thread's NQ halo offsets in it
     unsigned uvoff, uvoffc;                                  // this lane's column of the fragment panel: the 16-byte parts, the ninth product
-    // XCD-aware block order (8-wave form, persistent grids of a multiple of 8 workgroups, N / 64 = 2, 4 or 8 column blocks): workgroup w runs on XCD w % 8
-    // (round-robin dispatch) and keeps ONE column block, (w % 8) % ncb, for the whole launch - an XCD's 4 MB L2 holds that column block's panel only and
-    // never turns it over -, while the ncb workgroups (w % 8) / ncb, w / 8 of adjacent XCDs walk the SAME tile sequence in step: a tile's halo is fetched
-    // by ncb XCDs at about the same time - once from HBM, the rest out of the memory-side cache - instead of ncb times a whole pass over the batch apart
-    const int ncb = N / NBV;
-    // Measured inside the 300-frame step (profiles/r06_am_*): 2-7 % per launch for N >= 256 and for N = 128 with Cin >= 192; the N = 128 layers with
-    // Cin <= 128 keep the chunked order below (1-4 % faster there)
-    const bool xcd = LWG_W4_XCD && !SM && (gridDim.x & 7u) == 0 && (ncb == 4 || ncb == 8 || (ncb == 2 && (Cin >= 192 || LWG_W4_XCD == 2))) &&
-                     (int)gridDim.x < total && tiles >= (int)gridDim.x / ncb;
-    const int xg = (int)gridDim.x / ncb;                     // workgroups per column block = tiles per round
-    const int xr = (int)(((blockIdx.x & 7u) / (unsigned)ncb) * (gridDim.x >> 3) + (blockIdx.x >> 3));      // this workgroup's place among them
-    auto has_block = [&](int id) -> bool {                   // (id = blockIdx.x + k gridDim.x)
-        return xcd ? (id / (int)gridDim.x) * xg + xr < tiles : id < total;
-    };
     auto setup = [&](int id) {
-        // block id -> (column block, tile).  Chunked order (layers whose WHOLE fragment panel stays in an XCD's 4 MB L2 - in the generator N = 128): the
-        // grid's G persistent workgroups walk a chunk of G tiles through ALL column blocks before the next chunk (workgroup w: tile ch G + w in N / 64
-        // consecutive blocks) - a tile's halo is re-read one round after its first read instead of a whole pass over the batch apart.  Measured inside the
-        // 300-frame step (profiles/r06_ag_*): 2-3.4 % faster per launch for N = 128, 2-5 % SLOWER for N >= 256 (every round then pulls another column
-        // block's panel through L2): those keep the column-block-major order
         int cb, t;
-        if (xcd) {
-            cb = (int)(blockIdx.x & 7u) & (ncb - 1);
-            t = __builtin_amdgcn_readfirstlane((id / (int)gridDim.x) * xg + xr);
-        } else if (LWG_W4_CHUNK == 2 || (LWG_W4_CHUNK == 1 && 144u * (unsigned)Cin * (unsigned)N <= (5u << 20))) {
-            const int G = (int)gridDim.x, per = G * (N / NBV);
-            const int ch = __builtin_amdgcn_readfirstlane(id / per);
-            const int r = id - ch * per, base = ch * G;
-            const int nt = tiles - base < G ? tiles - base : G;
-            cb = __builtin_amdgcn_readfirstlane(r / nt);
-            t = __builtin_amdgcn_readfirstlane(base + r - cb * nt);
-        } else {
-            cb = __builtin_amdgcn_readfirstlane(id / tiles);
-            t = __builtin_amdgcn_readfirstlane(id - cb * tiles);
-        }
-        b = __builtin_amdgcn_readfirstlane(t / (bx * by));
-        t -= b * bx * by;
-        x0 = (t % bx) * 4 * W4_PBX;
-        y0 = (t / bx) * 4 * W4_PBY;
-        n0 = SMS ? (cb >> 1) * 64 + (cb & 1) * 16 : cb * NBV;
-        rx0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x0 + (size_t)b * H * W * a.C0), 0, (int)((unsigned)(H * W) * (unsigned)a.C0 * 4u), 0x00020000);
-        if constexpr (TWO) rx1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x1 + (size_t)b * H * W * a.C1), 0, (int)((unsigned)(H * W) * (unsigned)a.C1 * 4u), 0x00020000);
+        cw_block(o, id, cb, t);
+        bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV));
         int tids = tid;                                      // (through an empty asm: the halo geometry is recomputed per block - hoisted out of the block
         asm volatile("" : "+v"(tids));                       //  loop it would sit in registers through the K loop)
-#pragma unroll
-        for (int k = 0; k < NQ; ++k) {                       // padding pixels / threads without an element: an out-of-range offset (the hardware returns zeros)
-            const int i = tids + NTH * k;
-            const int pix = i >> 1, hq = i & 1, hy = pix / W4_HW, hx = pix - hy * W4_HW;
-            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-            const bool in = i < W4_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W;
-            voff0[k] = in ? (unsigned)((gy * W + gx) * a.C0 + 4 * hq) * 4u : W4_OOB;
-            if constexpr (TWO) voff1[k] = in ? (unsigned)((gy * W + gx) * a.C1 + 4 * hq) * 4u : W4_OOB;
-        }
-        const int col = SMS ? n0 + (((lane & 31) >> 4) << 5) + (lane & 15) : n0 + ct * 32 + (lane & 31);      // this lane's accumulator row = panel column
+        bk.halo(a, tids, NTH, W4_HW, W4_NEL);
+        const int col = SMS ? bk.n0 + (((lane & 31) >> 4) << 5) + (lane & 15) : bk.n0 + ct * 32 + (lane & 31);      // this lane's accumulator row = panel column
         uvoff = (unsigned)(((lane >> 5) * 9 * N + 4 * col) * 4);
         uvoffc = (unsigned)(((lane >> 5) * 9 * N + 8 * N + col) * 4);
     };
@@ -217,21 +158,9 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #else
         const int c = st * W4_KS;
 #endif
-        if constexpr (!TWO) {
-            return w4_buf_load_nt(rx0, voff0[k], (unsigned)c * 4u);
-        } else {
-            const bool first = c < a.C0;
-            const __amdgpu_buffer_rsrc_t r = first ? rx0 : rx1;
-            const unsigned v = first ? voff0[k] : voff1[k];
-            return w4_buf_load_nt(r, v, (unsigned)(first ? c : c - a.C0) * 4u);
-        }
+        return bk.template rld1<W4_NT_LD>(a, c, k);
     };
-    auto rst1 = [&](int buf, int k, floatx4 v) {
-        float* dst = raw0 + buf * W4_RAW + wst[k];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dst[c * W4_PLANE] = v[c];
-    };
-    // weights: lane = (k-half lane / 32, channel lane % 32); element (q, stage, k-pair, k-half, n) = twelve floats (nine products + padding)
+    auto rst1 = [&](int buf, int k, floatx4 v) { cw_rst1(raw0 + buf * W4_RAW + wst[k], W4_PLANE, v); };
     // weights: lane = (k-half lane / 32, channel lane % 32); element (q, stage, k-pair, k-half) = 9 N floats: [N][4] products 0-3, [N][4] products 4-7, [N] product 8 -
     // every load instruction reads contiguous memory (32 lanes x 16 bytes), nothing is padding
     floatx4 ufa[4], ufb[4];                                  // [register set = k-pair]: loaded TWO k-pairs ahead
@@ -245,8 +174,8 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #else
         const unsigned so = uq + (unsigned)(st * 4 + kk) * ukk;
 #endif
-        if (part == 0) ufa[set] = w4_buf_load(ru, uvoff, so);
-        else if (part == 1) ufb[set] = w4_buf_load(ru, uvoff, so + ubo);
+        if (part == 0) ufa[set] = cw_buf_load(ru, uvoff, so);
+        else if (part == 1) ufb[set] = cw_buf_load(ru, uvoff, so + ubo);
         else ufc[set] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ru, (int)uvoffc, (int)so, 0));
     };
     auto uldset = [&](int set, int st, int kk) {
@@ -255,8 +184,8 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #else
         const unsigned so = uq + (unsigned)(st * 4 + kk) * ukk;
 #endif
-        ufa[set] = w4_buf_load(ru, uvoff, so);
-        ufb[set] = w4_buf_load(ru, uvoff, so + ubo);
+        ufa[set] = cw_buf_load(ru, uvoff, so);
+        ufb[set] = cw_buf_load(ru, uvoff, so + ubo);
         ufc[set] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ru, (int)uvoffc, (int)so, 0));
     };
     // the input transform's thread: patch tid % 32, channel (tid / 32) % 8, rows 3 half .. 3 half + 2
@@ -477,7 +406,7 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
     floatx4 r0[NQ], r1[NQ];
     float bq;                                                // the block's bias, one value per lane of wave 0: requested with the first loads, parked in LDS by the prologue
     auto issue_loads = [&]() {
-        bq = bias ? bias[SMS ? n0 + (((tid & 31) >> 4) << 5) + (tid & 15) : n0 + (tid & (NBV - 1))] : 0.f;
+        bq = bias ? bias[SMS ? bk.n0 + (((tid & 31) >> 4) << 5) + (tid & 15) : bk.n0 + (tid & (NBV - 1))] : 0.f;
 #pragma unroll
         for (int k = 0; k < NQ; ++k) {
             r0[k] = rld1(0, k);
@@ -524,14 +453,14 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
     {
         int s = 0;
         for (; s + 2 < nst; s += 2) {
-            iteration(s, W4Int<0>(), W4Int<1>());
-            iteration(s + 1, W4Int<1>(), W4Int<1>());
+            iteration(s, IntC<0>(), IntC<1>());
+            iteration(s + 1, IntC<1>(), IntC<1>());
         }
-        iteration(s, W4Int<0>(), W4Int<1>());
-        iteration(s + 1, W4Int<1>(), W4Int<0>());
+        iteration(s, IntC<0>(), IntC<1>());
+        iteration(s + 1, IntC<1>(), IntC<0>());
     }
     W4TS(2);
-    const int eb = b, ex0 = x0, ey0 = y0, en0 = n0;          // this block's coordinates (the state moves on to the next block below)
+    const int eb = bk.b, ex0 = bk.x0, ey0 = bk.y0, en0 = bk.n0;          // this block's coordinates (the state moves on to the next block below)
     // epilogue.  (1) M A in registers: row q -> F[b] (b = 0..3, into acc[0..3]); the half row -> three partial sums (into acc[6..8]):
     //   nu 0..2: a0 = m0 + m1 + m2, a1 = m1 - m2, a2 = m1 + m2;  nu 3..5: b0 = m3 + m4, b1 = m3 - m4, b2 = m5
     //   (F[0] = a0 + b0, F[1] = a1 + 2 b1, F[2] = a2 + 4 b0, F[3] = a1 + 8 b1 + b2: finished by the reader)
@@ -618,21 +547,21 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
             const int ox = ex0 + 4 * (p & 7) + rb, oyb = ey0 + 4 * (p >> 3);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                vo[hp][i] = ox < W && oyb + i < H ? (unsigned)(((oyb + i) * W + ox) * a.YC + chan) * 4u : W4_OOB;
+                vo[hp][i] = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan);
         }
         floatx4 ext[2][4];                                   // residual (both channel groups | SM: both patches) | xn (group 0)
         if (EPI != LWG_EPI_NONE) {
 #pragma unroll
             for (int h = 0; h < (EPI == LWG_EPI_SPADE ? 1 : 2); ++h)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ext[h][i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(re, (int)(vo[NVP == 2 ? h : 0][i] + (SM ? 0u : 128u * h)), 0, W4_NT_RES));
+                for (int i = 0; i < 4; ++i) ext[h][i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(re, (int)cw4_out_group(vo[NVP == 2 ? h : 0][i], h, !SM), 0, W4_NT_RES));
         }
         if (ph == 1) {
             // the next block of this workgroup: its first loads go out here - the accumulators are dead - and land under the second pass's output
             // (unconditional: the last block re-requests its own first stages, nobody waits for them; see conv_winograd.hip)
             W4TS(8);
             nblk = blk + (int)gridDim.x;
-            more = has_block(nblk);
+            more = cw_has_block(o, nblk);
             setup(more ? nblk : blk);
             W4TS(9);
             issue_loads();
@@ -701,7 +630,7 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
             });
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)(vo[NVP == 2 ? h : 0][i] + (EPI == LWG_EPI_SPADE || SM ? 0u : 128u * h)), 0, W4_NT_ST);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)cw4_out_group(vo[NVP == 2 ? h : 0][i], h, EPI != LWG_EPI_SPADE && !SM), 0, W4_NT_ST);
         }
         if (ph == 0) W4TS(6);
     }
@@ -719,14 +648,12 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #endif
 }
 
-
 // The fragment panel from the fp32 GEMM panel of the same convolution (lwg_conv2d_nhwc_f32's w: [9 Cin / 4][N][4], k = ((c / 32) 9 + tap) 32 + c % 32):
 // U = G w G^T (6 x 6) per (input channel, output column) in fp64, rounded once, written as Upk[4][Cin/8][4][2][9 N]: block (q, s, kk, kh) of input channel
 // c = 8 s + 2 kk + kh holds product j of column n at [n][j] (j = 0..3), 4 N + [n][j - 4] (j = 4..7), 8 N + [n] (j = 8); j < 6: U[q][j]; j = 6..8: U[4 + q / 2][3 (q % 2) + j - 6].  tap9[3 r + s] = the tap index of kernel
 // position (dy, dx) = (r - 1, s - 1) in the GEMM panel.  One thread per (c, n).
-struct LwgWino4Taps { int t[9]; };
 
-__global__ __launch_bounds__(256) void lwg_winograd4_panel_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cin, int N, LwgWino4Taps taps) {
+__global__ __launch_bounds__(256) void lwg_winograd4_panel_kernel(const float* __restrict__ wp, float* __restrict__ U, int Cin, int N, LwgWinoTaps taps) {
     const int n = blockIdx.x * 64 + (threadIdx.x & 63), c = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (n >= N || c >= Cin) return;
     double g[3][3];
@@ -760,77 +687,34 @@ __global__ __launch_bounds__(256) void lwg_winograd4_panel_kernel(const float* _
 }
 
 extern "C" int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream_) {
-    if (!wpanel || !upk || !tap9 || Cin <= 0 || (Cin % 32) != 0 || N <= 0) return (int)hipErrorInvalidValue;
-    LwgWino4Taps taps;
-    for (int i = 0; i < 9; ++i) {
-        if (tap9[i] < 0 || tap9[i] > 8) return (int)hipErrorInvalidValue;
-        taps.t[i] = tap9[i];
-    }
+    LwgWinoTaps taps;
+    if (!cw_panel_args_ok(wpanel, upk, Cin, N, tap9, taps)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(lwg_winograd4_panel_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((Cin + 3) / 4)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream_), wpanel, upk, Cin, N, taps);
     return (int)hipGetLastError();
 }
 
-// args: lwg_conv2d_winograd_f32's launch description (3 x 3 / stride 1 / pad 1, one or two inputs with C0 % 8 == 0, C1 % 8 == 0, (C0 + C1) % 16 == 0, N % 64 == 0,
-// YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL or LWG_EPI_SPADE; any activation of lwg_act) EXCEPT args->w = the F(4x4, 3x3) fragment panel of
-// lwg_winograd4_panel_f32, 144 Cin N bytes.
-static bool lwg_wino4_contract(const LwgConvArgs& a) {
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 9 || a.stride != 1 || a.omul != 1 || a.C0 <= 0 || (a.C0 % W4_KS) != 0 || a.C1 < 0 ||
-        (a.C1 % W4_KS) != 0 || ((a.C0 + a.C1) % (2 * W4_KS)) != 0 || (a.C1 > 0 && !a.x1) || a.N <= 0 || (a.N % W4_NB) != 0 || a.OH != a.H || a.OW != a.W ||
-        a.YH != a.H || a.YW != a.W || a.xdt != LWG_DT_F32 || a.ydt != LWG_DT_F32 || a.M != a.B * a.H * a.W || a.ycoff < 0 || (a.ycoff % 4) != 0 ||
-        (a.YC % 4) != 0 || (a.act == LWG_ACT_RELU_MASK && a.epi != LWG_EPI_RESIDUAL))
-        return false;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.YC * 2 != a.N || a.ycoff != 0) return false;
-    } else {
-        if (a.ycoff + a.N > a.YC) return false;
-        if (a.epi != LWG_EPI_NONE && (a.epi != LWG_EPI_RESIDUAL || !a.res)) return false;
-    }
-    const unsigned long long cmax = (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1);
-    if ((unsigned long long)a.H * a.W * cmax * 4ull >= (unsigned long long)W4_OOB || 144ull * (a.C0 + a.C1) * a.N >= 0xffffffffull) return false;
-    if ((unsigned long long)a.H * a.W * a.YC * 4ull + 256ull >= (unsigned long long)W4_OOB) return false;      // (an output image is one buffer of the store path)
-    return true;
+// args: lwg_conv_wino.h's fp32 contract (lwg_conv2d_winograd_f32's launch description) with args->w = the F(4x4, 3x3) fragment panel of
+// lwg_winograd4_panel_f32, 144 Cin N bytes; an output image is one buffer of the store path, with 256 bytes of slack for the second channel group
+template <int EPI, bool SM>
+static int lwg_wino4_go(const LwgConvArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
+    return a.C1 > 0 ? cw_launch<lwg_conv_winograd4_kernel<EPI, true, SM>>(grid, SM ? 256 : W4_THREADS, lds, stream, a)
+                    : cw_launch<lwg_conv_winograd4_kernel<EPI, false, SM>>(grid, SM ? 256 : W4_THREADS, lds, stream, a);
 }
 
 extern "C" int lwg_conv2d_winograd4_f32(const LwgConvArgs* pa, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!pa || !lwg_wino4_contract(*pa)) return (int)hipErrorInvalidValue;
+    if (!pa || !cw_contract_ok(*pa, 144ull, 256ll)) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
     const size_t lds = (size_t)(W4_BIAS_OFF + 64) * 4;
-    const int bx = (a.W + 4 * W4_PBX - 1) / (4 * W4_PBX), by = (a.H + 4 * W4_PBY - 1) / (4 * W4_PBY);
     const int cus = lwg_device_cus();
-    long total = (long)bx * by * a.B * (a.N / W4_NB);
+    long long total = cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB);
     // small launches (the 8-wave blocks would leave half the chip or more without a workgroup): the 4-wave form, 32 channels per block (SPADE: gamma | beta
     // of 16 channels) - bitwise the same result (see the kernel), so the choice may depend on the batch
     const bool sm = LWG_W4_SMALL && 2 * total <= cus;
     if (sm) total *= 2;
-    const dim3 grid((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total));
-    static unsigned long long done[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool two = a.C1 > 0;
-#define LWG_W4_GO2(E, T, S, SLOT)                                                                                                       \
-    {                                                                                                                                   \
-        if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_conv_winograd4_kernel<E, T, S>), lds, done[SLOT]); e != hipSuccess) \
-            return (int)e;                                                                                                              \
-        hipLaunchKernelGGL((lwg_conv_winograd4_kernel<E, T, S>), grid, dim3(S ? 256 : W4_THREADS), lds, stream, a);                     \
-    }
-#define LWG_W4_GO(E, SLOT)                                                                                                              \
-    {                                                                                                                                   \
-        if (two) LWG_W4_GO2(E, true, false, SLOT + 3) else LWG_W4_GO2(E, false, false, SLOT)                                            \
-    }
-#define LWG_W4_GOS(E, SLOT)                                                                                                             \
-    {                                                                                                                                   \
-        if (two) LWG_W4_GO2(E, true, true, SLOT + 2) else LWG_W4_GO2(E, false, true, SLOT)                                              \
-    }
-    if (sm) {
-        if (a.epi == LWG_EPI_SPADE) {
-            if (two) LWG_W4_GO2(LWG_EPI_SPADE, true, true, 11) else LWG_W4_GO2(LWG_EPI_SPADE, false, true, 10)
-        } else if (a.epi == LWG_EPI_RESIDUAL) LWG_W4_GOS(LWG_EPI_RESIDUAL, 7)
-        else LWG_W4_GOS(LWG_EPI_NONE, 6)
-    } else if (a.epi == LWG_EPI_SPADE) LWG_W4_GO(LWG_EPI_SPADE, 2)
-    else if (a.epi == LWG_EPI_RESIDUAL) LWG_W4_GO(LWG_EPI_RESIDUAL, 1)
-    else LWG_W4_GO(LWG_EPI_NONE, 0)
-#undef LWG_W4_GOS
-#undef LWG_W4_GO
-#undef LWG_W4_GO2
-    return (int)hipGetLastError();
+    const dim3 grid = cw_persistent_grid(total, cus);
+    if (a.epi == LWG_EPI_SPADE) return sm ? lwg_wino4_go<LWG_EPI_SPADE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_SPADE, false>(a, grid, lds, stream);
+    if (a.epi == LWG_EPI_RESIDUAL) return sm ? lwg_wino4_go<LWG_EPI_RESIDUAL, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_RESIDUAL, false>(a, grid, lds, stream);
+    return sm ? lwg_wino4_go<LWG_EPI_NONE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_NONE, false>(a, grid, lds, stream);
 }

@@ -44,7 +44,7 @@
 // Batch invariance: a block's arithmetic depends on its own image only (per-image buffer descriptors: any batch in one launch); every output
 // element is accumulated over the stages and k-steps in the same order whatever B; there is one form and no split-K.
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_wino.h"
 
 typedef __bf16 wb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int wb_uintx4 __attribute__((ext_vector_type(4)));
@@ -60,7 +60,6 @@ typedef unsigned int wb_uintx2 __attribute__((ext_vector_type(2)));
 #define WB_MS_ROW 68                               // floats per (xi, j, patch) row of the exchange buffer
 #define WB_MS_BYTES (8 * 64 * WB_MS_ROW * 4)
 #define WB_LDS_BYTES (WB_LOOP_BYTES > WB_MS_BYTES ? WB_LOOP_BYTES : WB_MS_BYTES)
-#define WB_OOB 0xC0000000u                         // >= any image's byte size (host check): the buffer load returns 0
 #define WB_HALO_LOADS 3                            // 18 * 18 pixels * 4 sixteen-byte pieces = 1296 <= 3 * 512
 
 __device__ __forceinline__ unsigned wb_pack2(float lo, float hi) {
@@ -86,9 +85,7 @@ __global__ __launch_bounds__(WB_THREADS, 1) void lwg_conv_winograd_bf16_kernel(c
     const int khalf = lane >> 5, l31 = lane & 31;
     const int H = a.H, W = a.W, N = a.N, Cin = a.C0 + a.C1;
     const int nst = Cin / WB_KS;                           // even (host: Cin % 64 == 0)
-    const int bx = (W + 15) >> 4, by = (H + 15) >> 4;
-    const int tiles = bx * by * a.B;
-    const int total = tiles * (N >> 6);
+    const CwGrid g = cw_grid(a.B, H, W, N, 16, 16, 64);    // (lwg_conv_wino.h: the grid, the halo offsets, the image descriptors, the contract)
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(32u * (unsigned)Cin * (unsigned)N), 0x00020000);
 
     // ---- thread roles that do not depend on the block
@@ -115,38 +112,27 @@ __global__ __launch_bounds__(WB_THREADS, 1) void lwg_conv_winograd_bf16_kernel(c
             vsrc[pt][ks] = (unsigned)(p * 64 + (((2 * ks + khalf) ^ ((p >> 2) & 3)) << 4));
         }
 
-    for (int blk = lwg_xcd_remap(blockIdx.x, gridDim.x); blk < total; blk += gridDim.x) {
-        const int cb = blk / tiles;
-        int t = blk - cb * tiles;
-        const int b = t / (bx * by);
-        t -= b * bx * by;
-        const int x0 = (t % bx) * 16, y0 = (t / bx) * 16;
-        const int n0 = cb * 64;
-        const unsigned img = (unsigned)(H * W);
-        const __amdgpu_buffer_rsrc_t rx0 =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(reinterpret_cast<const __bf16*>(a.x0) + (size_t)b * img * a.C0), 0, (int)(img * (unsigned)a.C0 * 2u), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx1 = TWO
-            ? __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(reinterpret_cast<const __bf16*>(a.x1) + (size_t)b * img * a.C1), 0, (int)(img * (unsigned)a.C1 * 2u), 0x00020000)
-            : rx0;
+    for (int blk = lwg_xcd_remap(blockIdx.x, gridDim.x); blk < g.total; blk += gridDim.x) {
+        const int cb = blk / g.tiles;
+        const int t = blk - cb * g.tiles, b = cw_image(g, t);
+        int x0, y0;
+        cw_corner(g, t - b * g.bx * g.by, 16, 16, x0, y0);
+        const int n0 = cw_n0(cb, 64);
+        const __amdgpu_buffer_rsrc_t rx0 = cw_image_rsrc(a.x0, b, H, W, a.C0, 2u);
+        const __amdgpu_buffer_rsrc_t rx1 = TWO ? cw_image_rsrc(a.x1, b, H, W, a.C1, 2u) : rx0;
         int hlin[WB_HALO_LOADS];                           // pixel index inside the image, -1 = padding / no piece
 #pragma unroll
-        for (int q = 0; q < WB_HALO_LOADS; ++q) {
-            const int pix = (tid + WB_THREADS * q) >> 2;
-            const int py = pix / WB_HALO, px = pix - py * WB_HALO;
-            const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-            hlin[q] = (pix < WB_HALO_PIX && gy >= 0 && gy < H && gx >= 0 && gx < W) ? gy * W + gx : -1;
-        }
+        for (int q = 0; q < WB_HALO_LOADS; ++q) hlin[q] = cw_halo_pixel(tid + WB_THREADS * q, WB_HALO, 4 * WB_HALO_PIX, 2, x0, y0, H, W);
         const unsigned uvoff = (unsigned)((n0 + nt * 32 + l31) * 32 + khalf * 16);
 
         wb_uintx4 hreg[WB_HALO_LOADS];
         auto load_halo = [&](int s) {
             const int cc = s * WB_KS;
-            const bool use1 = TWO && cc >= a.C0;
-            const unsigned cs = (unsigned)(use1 ? a.C1 : a.C0);
-            const unsigned soff = (unsigned)(cc - (use1 ? a.C0 : 0)) * 2u;
+            const bool use1 = cw_stage_second(cc, a.C0, TWO);
+            const unsigned soff = cw_stage_soff(cc, a.C0, TWO, 2);
 #pragma unroll
             for (int q = 0; q < WB_HALO_LOADS; ++q) {
-                const unsigned voff = hlin[q] >= 0 ? (unsigned)hlin[q] * cs * 2u + (unsigned)((tid + WB_THREADS * q) & 3) * 16u : WB_OOB;
+                const unsigned voff = cw_halo_pixel_voff(hlin[q], tid + WB_THREADS * q, 2, use1 ? a.C1 : a.C0, 2);
                 hreg[q] = __builtin_bit_cast(wb_uintx4, use1 ? __builtin_amdgcn_raw_buffer_load_b128(rx1, (int)voff, (int)soff, 0)
                                                              : __builtin_amdgcn_raw_buffer_load_b128(rx0, (int)voff, (int)soff, 0));
             }
@@ -337,51 +323,19 @@ __global__ __launch_bounds__(WB_THREADS, 1) void lwg_conv_winograd_bf16_kernel(c
     }
 }
 
-template <int EPI, bool TWO>
-static hipError_t wb_launch(const LwgConvArgs& a, hipStream_t stream) {
-    auto kern = lwg_conv_winograd_bf16_kernel<EPI, TWO>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), WB_LDS_BYTES, attr_done); e != hipSuccess) return e;
-    const long long total = (long long)a.B * ((a.H + 15) / 16) * ((a.W + 15) / 16) * (a.N / 64);
-    const long long cus = lwg_device_cus();
-    hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(WB_THREADS), WB_LDS_BYTES, stream, a);
-    return hipGetLastError();
-}
-
 template <int EPI>
-static hipError_t wb_launch_epi(const LwgConvArgs& a, hipStream_t stream) {
-    return a.C1 > 0 ? wb_launch<EPI, true>(a, stream) : wb_launch<EPI, false>(a, stream);
+static int wb_launch_epi(const LwgConvArgs& a, hipStream_t stream) {
+    const long long total = cw_total_blocks(a.B, a.H, a.W, a.N, 16, 16, 64), cus = lwg_device_cus();
+    const dim3 grid((unsigned)(total < cus ? total : cus));
+    return a.C1 > 0 ? cw_launch<lwg_conv_winograd_bf16_kernel<EPI, true>>(grid, WB_THREADS, WB_LDS_BYTES, stream, a)
+                    : cw_launch<lwg_conv_winograd_bf16_kernel<EPI, false>>(grid, WB_THREADS, WB_LDS_BYTES, stream, a);
 }
 
-// Contract: include/lwg_hip.h.  Everything outside it is refused here, before any launch.
+// Contract: include/lwg_hip.h, cwb_contract_ok (lwg_conv_wino.h).  Everything outside it is refused here, before any launch.
 extern "C" int lwg_conv2d_winograd_bf16(const LwgConvArgs* pa, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!pa) return (int)hipErrorInvalidValue;
-    const LwgConvArgs& a = *pa;
-    if (!a.x0 || !a.w || !a.y || a.B <= 0 || a.H <= 0 || a.W <= 0 || a.C0 <= 0 || a.C1 < 0 || a.N <= 0) return (int)hipErrorInvalidValue;
-    if (a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16) return (int)hipErrorInvalidValue;
-    if (a.ntaps != 9 || a.stride != 1 || a.omul != 1 || a.ooy != 0 || a.oox != 0) return (int)hipErrorInvalidValue;
-    for (int t = 0; t < 9; ++t)                            // the 3 x 3 grid ascending in (dy, dx): the order the panel was built in
-        if (a.dy[t] != t / 3 - 1 || a.dx[t] != t % 3 - 1) return (int)hipErrorInvalidValue;
-    if (a.OH != a.H || a.OW != a.W || a.YH != a.H || a.YW != a.W) return (int)hipErrorInvalidValue;
-    if ((long long)a.M != (long long)a.B * a.H * a.W) return (int)hipErrorInvalidValue;
-    const int Cin = a.C0 + a.C1;
-    if (a.N % 64 != 0 || Cin % 64 != 0 || (a.YC & 7) != 0 || (a.ycoff & 7) != 0 || a.ycoff < 0) return (int)hipErrorInvalidValue;
-    if (a.C1 != 0 && (a.C0 % 64 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
-    if (a.act != LWG_ACT_NONE && a.act != LWG_ACT_RELU && a.act != LWG_ACT_TANH && a.act != LWG_ACT_SIGMOID) return (int)hipErrorInvalidValue;
-    // 32-bit offsets: one IMAGE of either input (per-image buffer descriptors, so any batch) and the panel; nothing wraps - larger is refused
-    if ((unsigned long long)a.H * a.W * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if (32ull * (unsigned long long)Cin * (unsigned long long)a.N >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((long long)a.B * ((a.H + 15) / 16) * ((a.W + 15) / 16) * (a.N / 64) >= 0x7fffffffll) return (int)hipErrorInvalidValue;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.YC * 2 != a.N || a.ycoff != 0) return (int)hipErrorInvalidValue;
-        return (int)wb_launch_epi<LWG_EPI_SPADE>(a, stream);
-    }
-    if (a.ycoff + a.N > a.YC) return (int)hipErrorInvalidValue;
-    if (a.epi == LWG_EPI_RESIDUAL) {
-        if (!a.res) return (int)hipErrorInvalidValue;
-        return (int)wb_launch_epi<LWG_EPI_RESIDUAL>(a, stream);
-    }
-    if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    return (int)wb_launch_epi<LWG_EPI_NONE>(a, stream);
+    if (!pa || !cwb_contract_ok(*pa)) return (int)hipErrorInvalidValue;
+    if (pa->epi == LWG_EPI_SPADE) return wb_launch_epi<LWG_EPI_SPADE>(*pa, stream);
+    if (pa->epi == LWG_EPI_RESIDUAL) return wb_launch_epi<LWG_EPI_RESIDUAL>(*pa, stream);
+    return wb_launch_epi<LWG_EPI_NONE>(*pa, stream);
 }

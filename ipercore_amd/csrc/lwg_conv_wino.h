@@ -1,0 +1,249 @@
+// What the three fused Winograd forms of the 3 x 3 / stride 1 / pad 1 convolution share - conv_winograd.hip (fp32 F(2x2, 3x3)), conv_winograd4.hip
+// (fp32 F(4x4, 3x3)) and conv_winograd_bf16.hip (bf16 F(2x2, 3x3)): the block grid, the persistent-workgroup walk and its block orders, the halo
+// offsets with their out-of-range marker, the per-image buffer descriptors, the one / two-input halo loads, F(4x4)'s output offsets, the host
+// contracts, the panel entry points' tap check and the launch.  Each kernel keeps its tile and LDS constants, its K loop and slot plan, its
+// transforms, fragment loads, LDS slot map, exchange buffer, output transform and lab switches.  The bf16 kernel takes the grid,
+// the halo offsets, the image descriptor and the contract only: its body holds the halo as pixel indices (three registers, not six offsets).
+//   Part 1 is plain integer arithmetic that a host compiler can include: tests/test_conv_offsets_cpu.py compiles these very functions with
+// signed-overflow traps and drives them over the corner shapes of the contracts.  Part 2 (hipcc only) is the device code around them.
+// Not merged with lwg_convt_wino.h: the block orders' rules differ (F(4x4) takes the XCD-aware order at two column blocks only for Cin >= 192, and
+// has a chunked order besides), and so does the rest of the device code.
+#pragma once
+#include <stddef.h>
+#include "lwg_conv_args.h"
+
+#ifdef __HIPCC__
+#define CW_FN __host__ __device__ __forceinline__
+#else
+#define CW_FN static inline
+#endif
+#ifdef __HIP_DEVICE_COMPILE__
+#define CW_UNIFORM(v) __builtin_amdgcn_readfirstlane(v)   // a workgroup-uniform value, into a scalar register (host: the value)
+#else
+#define CW_UNIFORM(v) (v)
+#endif
+#define CW_OOB 0xC0000000u                   // >= any image's byte size (host: H * W * C * bytes < 3 GiB): the buffer load returns 0, the store is dropped
+#define CW_KS 8                              // input channels per stage of the fp32 kernels
+#define CW_NB 64                             // output channels per block (fp32 small forms: 32)
+// ---- part 1: integer arithmetic, host-compilable ----
+// The block grid of a launch: blocks of ex x ey output pixels (16 x 16: F(2x2) and bf16, 32 x 16: F(4x4)) x nbv output channels; bx x by
+// blocks per image, tiles = blocks of all images, total = tiles x column blocks
+struct CwGrid { int bx, by, tiles, total; };
+CW_FN CwGrid cw_grid(int B, int H, int W, int N, int ex, int ey, int nbv) {
+    const int bx = (W + ex - 1) / ex, by = (H + ey - 1) / ey, tiles = bx * by * B;
+    return CwGrid{bx, by, tiles, tiles * (N / nbv)};
+}
+CW_FN long long cw_total_blocks(int B, int H, int W, int N, int ex, int ey, int nbv) {      // (the host's count: 64 bits, before the grid is cut to the CUs)
+    return (long long)((W + ex - 1) / ex) * ((H + ey - 1) / ey) * B * (N / nbv);
+}
+
+// ---- the block order: nwg persistent workgroups, workgroup wg walks the block ids wg + k nwg.
+//   CW_COLMAJOR (F(2x2); bf16 behind its lwg_xcd_remap; F(4x4) otherwise): id = column block * tiles + tile.
+//   CW_CHUNK (F(4x4), layers whose WHOLE fragment panel stays in an XCD's 4 MB L2 - in the generator N = 128): the grid's G persistent workgroups walk
+// a chunk of G tiles through ALL column blocks before the next chunk (workgroup w: tile ch G + w in N / 64 consecutive blocks) - a tile's halo is
+// re-read one round after its first read instead of a whole pass over the batch apart.  Measured inside the 300-frame step (profiles/r06_ag_*):
+// 2-3.4 % faster per launch for N = 128, 2-5 % SLOWER for N >= 256 (every round then pulls another column block's panel through L2): those keep
+// the column-block-major order.
+//   CW_XCD (F(4x4), 8-wave form, persistent grids of a multiple of 8 workgroups, N / 64 = 2, 4 or 8 column blocks): workgroup w runs on XCD w % 8
+// (round-robin dispatch) and keeps ONE column block, (w % 8) % ncb, for the whole launch - an XCD's 4 MB L2 holds that column block's panel only and
+// never turns it over -, while the ncb workgroups (w % 8) / ncb, w / 8 of adjacent XCDs walk the SAME tile sequence in step: a tile's halo is fetched
+// by ncb XCDs at about the same time - once from HBM, the rest out of the memory-side cache - instead of ncb times a whole pass over the batch apart.
+// Measured inside the 300-frame step (profiles/r06_am_*): 2-7 % per launch for N >= 256 and for N = 128 with Cin >= 192; the N = 128 layers with
+// Cin <= 128 keep the chunked order (1-4 % faster there).
+enum { CW_COLMAJOR = 0, CW_CHUNK = 1, CW_XCD = 2 };
+struct CwOrder { int kind, nwg, wg, ncb, tiles, total, xg, xr; };    // xg, xr (CW_XCD): workgroups per column block = tiles per round, this one's place among them
+
+// F(4x4)'s rule.  xcd_sw / chunk_sw: the lab switches LWG_W4_XCD (0 off, 1 the rule, 2 two column blocks at any Cin) / LWG_W4_CHUNK (0 never, 1 where
+// the 144-byte-per-pair panel is at most 5 MiB, 2 always); sm: the 4-wave form (never XCD-aware)
+CW_FN int cw4_order_kind(int xcd_sw, int chunk_sw, bool sm, unsigned nwg, int ncb, int Cin, int N, int tiles, int total) {
+    const bool xcd = xcd_sw && !sm && (nwg & 7u) == 0 && (ncb == 4 || ncb == 8 || (ncb == 2 && (Cin >= 192 || xcd_sw == 2))) && (int)nwg < total && tiles >= (int)nwg / ncb;
+    return xcd ? CW_XCD : chunk_sw == 2 || (chunk_sw == 1 && 144u * (unsigned)Cin * (unsigned)N <= (5u << 20)) ? CW_CHUNK : CW_COLMAJOR;
+}
+CW_FN CwOrder cw_order(int kind, unsigned nwg, unsigned wg, int ncb, const CwGrid& g) {
+    return CwOrder{kind, (int)nwg, (int)wg, ncb, g.tiles, g.total, (int)nwg / ncb, (int)(((wg & 7u) / (unsigned)ncb) * (nwg >> 3) + (wg >> 3))};
+}
+CW_FN bool cw_has_block(const CwOrder& o, int id) {            // (id = wg + k nwg)
+    return o.kind == CW_XCD ? (id / o.nwg) * o.xg + o.xr < o.tiles : id < o.total;
+}
+// block id -> column block and tile (the XCD order's column block is scalar arithmetic on the workgroup id already)
+CW_FN void cw_block(const CwOrder& o, int id, int& cb, int& t) {
+    if (o.kind == CW_XCD) {
+        cb = (int)((unsigned)o.wg & 7u) & (o.ncb - 1);
+        t = CW_UNIFORM((id / o.nwg) * o.xg + o.xr);
+    } else if (o.kind == CW_CHUNK) {
+        const int G = o.nwg, per = G * o.ncb;
+        const int ch = CW_UNIFORM(id / per);
+        const int r = id - ch * per, base = ch * G;
+        const int nt = o.tiles - base < G ? o.tiles - base : G;
+        cb = CW_UNIFORM(r / nt);
+        t = CW_UNIFORM(base + r - cb * nt);
+    } else {
+        cb = CW_UNIFORM(id / o.tiles);
+        t = CW_UNIFORM(id - cb * o.tiles);
+    }
+}
+CW_FN int cw_image(const CwGrid& g, int t) { return t / (g.bx * g.by); }
+// the block's corner (x0, y0) from its tile inside image b (t - b bx by); its first output column from its column block
+CW_FN void cw_corner(const CwGrid& g, int t_in_image, int ex, int ey, int& x0, int& y0) { x0 = (t_in_image % g.bx) * ex, y0 = (t_in_image / g.bx) * ey; }
+CW_FN int cw_n0(int cb, int nbv) { return cb * nbv; }
+// (F(4x4), 4-wave form with the SPADE epilogue: the block's 32 accumulator rows are gamma | beta of the SAME 16 channels - columns n0 .. + 15 and
+// n0 + 32 .. + 47 of the stacked panel - so the modulation still finds both in one block)
+CW_FN int cw4_n0_spade_small(int cb) { return (cb >> 1) * 64 + (cb & 1) * 16; }
+// ---- the halo: element i of a stage (nel of them: pixel i >> lgp of the hw pixels wide halo, 16-byte piece i % 2^lgp of the stage's channels; a
+// thread holds i = tid + k threads) -> the pixel inside the image (linear index, or -1: padding / no element) -> its byte offset inside an input
+// of C channels of ebytes bytes, or the marker (the hardware returns zeros: no branches, no exec masks); the stage's channels through the scalar
+// offset.  fp32: 2 quads per pixel (lgp 1), bf16: 4 octets (lgp 2)
+CW_FN int cw_halo_pixel(int i, int hw, int nel, int lgp, int x0, int y0, int H, int W) {
+    const int pix = i >> lgp, hy = pix / hw, hx = pix - hy * hw;
+    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+    return i < nel && gy >= 0 && gy < H && gx >= 0 && gx < W ? gy * W + gx : -1;
+}
+CW_FN unsigned cw_halo_pixel_voff(int lin, int i, int lgp, int C, int ebytes) {
+    return lin >= 0 ? (unsigned)(lin * C + (16 / ebytes) * (i & ((1 << lgp) - 1))) * (unsigned)ebytes : CW_OOB;
+}
+CW_FN unsigned cw_halo_voff(int i, int hw, int nel, int lgp, int x0, int y0, int H, int W, int C, int ebytes) {
+    return cw_halo_pixel_voff(cw_halo_pixel(i, hw, nel, lgp, x0, y0, H, W), i, lgp, C, ebytes);
+}
+// a stage's channels c .. lie in ONE input (C0 is a multiple of the stage): in the second one (two-input launches) at c - C0
+CW_FN bool cw_stage_second(int c, int C0, bool two) { return two && c >= C0; }
+CW_FN unsigned cw_stage_soff(int c, int C0, bool two, int ebytes) { return (unsigned)(cw_stage_second(c, C0, two) ? c - C0 : c) * (unsigned)ebytes; }
+// ---- F(4x4)'s output pixels.  Image eb of the output (and of res / xn: the output's layout) is ONE buffer: a reader thread's pixel (ox, oy), first
+// channel chan, is a 32-bit offset inside it (out of range: right of / below the image - the hardware drops the store and returns zeros for the
+// load), the second channel group (+ 32 channels; 8-wave form, not the SPADE store) an increment of the VECTOR offset: the scalar offset of the
+// stores and loads stays the constant 0 (test_no_wide_buffer_store_with_register_soffset; lwg_convt_wino.h: ctw_store_block)
+CW_FN unsigned cw4_out_voff(int ox, int oy, int H, int W, int YC, int chan) {
+    return ox < W && oy < H ? (unsigned)((oy * W + ox) * YC + chan) * 4u : CW_OOB;
+}
+CW_FN unsigned cw4_out_group(unsigned vo, int h, bool grouped) { return vo + (grouped ? 128u * (unsigned)h : 0u); }
+
+// ---- the host contracts.  fp32 (lwg_conv2d_winograd_f32 / _f32_ws, lwg_conv2d_winograd4_f32): the launch description of the 3 x 3 / stride 1 /
+// pad 1 convolution as lwg_conv2d_nhwc_f32 takes it (nine taps, omul = 1, OH = H, OW = W, one or two inputs with C0 % 8 == 0, C1 % 8 == 0 and
+// (C0 + C1) % 16 == 0, N % 64 == 0, YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL (ycoff % 4 == 0) or LWG_EPI_SPADE (N = 2 YC, columns gamma | beta
+// interleaved in blocks of 32, ycoff = 0); any activation of lwg_act, the ReLU mask with LWG_EPI_RESIDUAL; every image of an input < 3 GiB) EXCEPT
+// args->w = the kernel's fragment panel of pair_bytes per (input channel, output column): F(2x2) 64 - Upk[16][Cin/8][2][N][4], element (p, s, kh,
+// n, kk) = (G w G^T)[xi = p / 4][nu = p % 4] of input channel 8 s + 2 kk + kh (concatenated order) and output column n -, F(4x4) 144 (see
+// lwg_winograd4_panel_f32).  out_slack: bytes beyond an output image that its offsets may reach where the image is one buffer of the store path
+// (F(4x4): 256), CW_NO_OUT_BUFFER where the stores go through 64-bit pointers (F(2x2): no limit on the output image)
+#define CW_NO_OUT_BUFFER (-1ll)
+CW_FN bool cw_contract_ok(const LwgConvArgs& a, unsigned long long pair_bytes, long long out_slack) {
+    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 9 || a.stride != 1 || a.omul != 1 || a.C0 <= 0 || (a.C0 % CW_KS) != 0 || a.C1 < 0 ||
+        (a.C1 % CW_KS) != 0 || ((a.C0 + a.C1) % (2 * CW_KS)) != 0 || (a.C1 > 0 && !a.x1) || a.N <= 0 || (a.N % CW_NB) != 0 || a.OH != a.H ||
+        a.OW != a.W || a.YH != a.H || a.YW != a.W || a.xdt != LWG_DT_F32 || a.ydt != LWG_DT_F32 || (long long)a.M != (long long)a.B * a.H * a.W ||
+        a.ycoff < 0 || (a.ycoff % 4) != 0 || (a.YC % 4) != 0 || (a.act == LWG_ACTIVATION_RELU_MASK && a.epi != LWG_EPI_RESIDUAL))
+        return false;
+    if (a.epi == LWG_EPI_SPADE) {
+        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.YC * 2 != a.N || a.ycoff != 0) return false;
+    } else {
+        if (a.ycoff + a.N > a.YC) return false;
+        if (a.epi != LWG_EPI_NONE && (a.epi != LWG_EPI_RESIDUAL || !a.res)) return false;
+    }
+    const unsigned long long cmax = (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1);
+    if ((unsigned long long)a.H * a.W * cmax * 4ull >= (unsigned long long)CW_OOB || pair_bytes * (a.C0 + a.C1) * a.N >= 0xffffffffull) return false;
+    if (out_slack >= 0 && (unsigned long long)a.H * a.W * a.YC * 4ull + (unsigned long long)out_slack >= (unsigned long long)CW_OOB) return false;
+    return true;
+}
+// bf16 (lwg_conv2d_winograd_bf16; include/lwg_hip.h): bf16 in and out, the taps ascending in (dy, dx) (the order the panel was built in), Cin and N
+// multiples of 64 (a second input: C0 too), 8-channel slices, activation none / ReLU / tanh / sigmoid - no ReLU mask.  32-bit offsets: one IMAGE
+// of either input (per-image buffer descriptors, so any batch) and the 32-byte-per-pair panel; nothing wraps - larger is refused
+CW_FN bool cwb_contract_ok(const LwgConvArgs& a) {
+    if (!a.x0 || !a.w || !a.y || a.B <= 0 || a.H <= 0 || a.W <= 0 || a.C0 <= 0 || a.C1 < 0 || a.N <= 0 || a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16 ||
+        a.ntaps != 9 || a.stride != 1 || a.omul != 1 || a.ooy != 0 || a.oox != 0 || a.OH != a.H || a.OW != a.W || a.YH != a.H || a.YW != a.W ||
+        (long long)a.M != (long long)a.B * a.H * a.W)
+        return false;
+    for (int t = 0; t < 9; ++t)
+        if (a.dy[t] != t / 3 - 1 || a.dx[t] != t % 3 - 1) return false;
+    const int Cin = a.C0 + a.C1;
+    if (a.N % 64 != 0 || Cin % 64 != 0 || (a.YC & 7) != 0 || (a.ycoff & 7) != 0 || a.ycoff < 0 || (a.C1 != 0 && (a.C0 % 64 != 0 || !a.x1))) return false;
+    if (a.act != LWG_ACTIVATION_NONE && a.act != LWG_ACTIVATION_RELU && a.act != LWG_ACTIVATION_TANH && a.act != LWG_ACTIVATION_SIGMOID) return false;
+    if ((unsigned long long)a.H * a.W * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 2ull >= (unsigned long long)CW_OOB ||
+        32ull * (unsigned long long)Cin * (unsigned long long)a.N >= (unsigned long long)CW_OOB || cw_total_blocks(a.B, a.H, a.W, a.N, 16, 16, 64) >= 0x7fffffffll)
+        return false;
+    if (a.epi == LWG_EPI_SPADE) return a.xn && a.mean && a.rstd && a.bias && a.YC * 2 == a.N && a.ycoff == 0;
+    return a.ycoff + a.N <= a.YC && (a.epi == LWG_EPI_NONE || (a.epi == LWG_EPI_RESIDUAL && a.res));
+}
+
+// the fp32 panel entry points' arguments (lwg_winograd_panel_f32, lwg_winograd4_panel_f32): tap9[3 r + s] = the tap index of kernel position
+// (dy, dx) = (r - 1, s - 1) in the GEMM panel
+struct LwgWinoTaps { int t[9]; };
+CW_FN bool cw_panel_args_ok(const float* wpanel, const float* upk, int Cin, int N, const int* tap9, LwgWinoTaps& taps) {
+    if (!wpanel || !upk || !tap9 || Cin <= 0 || (Cin % 32) != 0 || N <= 0) return false;
+    for (int i = 0; i < 9; ++i) {
+        if (tap9[i] < 0 || tap9[i] > 8) return false;
+        taps.t[i] = tap9[i];
+    }
+    return true;
+}
+
+// ---- part 2: device code and the launch ----
+#ifdef __HIPCC__
+#include "lwg_common.h"
+
+template <int V> struct IntC { static constexpr int value = V; };
+// POLICY: the cache policy of the load (0 = default; F(4x4)'s halo loads pass W4_NT_LD)
+template <int POLICY = 0>
+__device__ __forceinline__ floatx4 cw_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, POLICY));
+}
+// image b of an input (B, H, W, C) of ebytes-byte elements as a buffer
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cw_image_rsrc(const void* x, int b, int H, int W, int C, unsigned ebytes) {
+    const unsigned img = (unsigned)(H * W);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(x)) + (size_t)b * img * C * ebytes, 0, (int)(img * (unsigned)C * ebytes), 0x00020000);
+}
+
+// The per-block state of the fp32 kernels (workgroup-uniform): image b, block corner (x0, y0), first output column n0, this image of each input
+// as a buffer; this thread's NQ halo elements (pixel, channel quad): byte offsets inside either input.
+// TWO (round 6): the launch has a second input (skip concatenation).  One-input launches - four fifths of the engine's time - carry no per-load choice
+// of the source tensor at all: as a uniform branch pair around every halo load it cost 1.9 % of the K loop and 700 cycles of every block's set-up
+// (profiles/r06_k_*); the two-input form selects the descriptor / offset (scalar selects + one v_cndmask per load) instead of branching.
+template <int NQ, bool TWO>
+struct CwBlock {
+    int b, x0, y0, n0;
+    __amdgpu_buffer_rsrc_t rx0, rx1;
+    unsigned voff0[NQ], voff1[NQ];
+
+    // tile t of the grid (ex x ey pixels per block), first output column n
+    __device__ __forceinline__ void locate(const LwgConvArgs& a, const CwGrid& g, int t, int ex, int ey, int n) {
+        b = __builtin_amdgcn_readfirstlane(cw_image(g, t));
+        cw_corner(g, t - b * g.bx * g.by, ex, ey, x0, y0);
+        n0 = n;
+        rx0 = cw_image_rsrc(a.x0, b, a.H, a.W, a.C0, 4u);
+        if constexpr (TWO) rx1 = cw_image_rsrc(a.x1, b, a.H, a.W, a.C1, 4u);
+    }
+    // the elements tid + nth k of the hw pixels wide halo (nel elements); padding pixels / threads without an element: an out-of-range offset (zeros)
+    __device__ __forceinline__ void halo(const LwgConvArgs& a, int tid, int nth, int hw, int nel) {
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+            voff0[k] = cw_halo_voff(tid + nth * k, hw, nel, 1, x0, y0, a.H, a.W, a.C0, 4);
+            if constexpr (TWO) voff1[k] = cw_halo_voff(tid + nth * k, hw, nel, 1, x0, y0, a.H, a.W, a.C1, 4);
+        }
+    }
+    // halo element k of the stage whose first channel (concatenated order) is c
+    template <int POLICY = 0>
+    __device__ __forceinline__ floatx4 rld1(const LwgConvArgs& a, int c, int k) const {
+        if constexpr (!TWO) {
+            return cw_buf_load<POLICY>(rx0, voff0[k], cw_stage_soff(c, a.C0, false, 4));
+        } else {
+            const bool second = cw_stage_second(c, a.C0, true);
+            const __amdgpu_buffer_rsrc_t r = second ? rx1 : rx0;
+            const unsigned v = second ? voff1[k] : voff0[k];
+            return cw_buf_load<POLICY>(r, v, cw_stage_soff(c, a.C0, true, 4));
+        }
+    }
+};
+// a halo element's four channels -> its slot of the channel-major planes raw[buf] (plane floats apart)
+__device__ __forceinline__ void cw_rst1(float* dst, int plane, floatx4 v) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[k * plane] = v[k];
+}
+
+// The dynamic-LDS opt-in of one kernel instantiation (once per device) and its launch
+template <void (*KERNEL)(const LwgConvArgs)>
+static inline int cw_launch(dim3 grid, unsigned threads, size_t lds, hipStream_t stream, const LwgConvArgs& a) {
+    static unsigned long long done = 0ull;
+    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a);
+    return (int)hipGetLastError();
+}
+// persistent workgroups: one per CU (LDS) at most, each walking block ids blockIdx.x + k gridDim.x (LWG_WINO_PERSIST = 0: one block per workgroup)
+static inline dim3 cw_persistent_grid(long long total, int cus) { return dim3((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total)); }
+#endif  // __HIPCC__

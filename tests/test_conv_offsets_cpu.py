@@ -5,9 +5,9 @@ the image) gets the marker 0xC0000000 - at or beyond any image's size, so the ha
 while every offset the kernel forms - the marker plus a per-pass or per-stage increment included - stays within 32 bits, and while the C++
 expressions that form the offsets do not overflow their own types.
 
-The audit below compiles the kernels' own offset arithmetic into a host program with signed-overflow traps - the transposed kernels' by INCLUDING
-csrc/lwg_convt_wino.h, whose integer functions are what both kernels compile; the 3 x 3 kernels' expressions cut VERBATIM out of their sources -
-and evaluates it for the corner shapes the host contracts accept: the widest output rows at the
+The audit below compiles the kernels' own offset arithmetic into a host program with signed-overflow traps by INCLUDING csrc/lwg_convt_wino.h (the
+two transposed kernels) and csrc/lwg_conv_wino.h (the three 3 x 3 kernels), whose integer functions are what the kernels compile, and evaluates
+it - offsets, block walks, host contracts - for the corner shapes the host contracts accept: the widest output rows at the
 fewest rows, the tallest images at one or two pixels of width, images just under the size limits, widths and heights that are not multiples of the
 tile.  Every kept access must land at its own pixel and channel; every dropped one at or beyond the buffer's size modulo 2^32.
 
@@ -18,7 +18,6 @@ import shutil
 import subprocess
 import sys
 import tempfile
-import textwrap
 
 import pytest
 
@@ -27,95 +26,24 @@ CSRC = os.path.join(ROOT, "ipercore_amd", "csrc")
 OOB = 0xC0000000
 
 
-def _src(name):
-    text = open(os.path.join(CSRC, name)).read()
-    return re.sub(r"//[^\n]*", "", text)                    # comments out: statements are cut at ';' on paren depth 0
-
-
-def _stmts(text):
-    """The statements of a piece of C++ (split at ';' outside parentheses), whitespace-normalised."""
-    out, depth, cur = [], 0, []
-    for ch in text:
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-        if ch == ";" and depth == 0:
-            out.append(" ".join("".join(cur).split()))
-            cur = []
-        else:
-            cur.append(ch)
-    return [s.lstrip("{} ").strip() for s in out]
-
-
-def _call_args(text, fname):
-    """Argument texts of the first call of fname in text."""
-    i = text.index(fname + "(") + len(fname) + 1
-    depth, cur, args = 0, [], []
-    while True:
-        ch = text[i]
-        i += 1
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            if depth == 0:
-                args.append(" ".join("".join(cur).split()))
-                return args
-            depth -= 1
-        if ch == "," and depth == 0:
-            args.append(" ".join("".join(cur).split()))
-            cur = []
-        else:
-            cur.append(ch)
-
-
 def _code(name):
     """csrc/<name> without its comments."""
-    return _src(name)
+    return re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
 
 
 CONVT_KERNELS = ("convt_winograd.hip", "convt_winograd24.hip")
 CONVT_HEADER = "lwg_convt_wino.h"
 
 
-def _w4_exprs():
-    s = _src("conv_winograd4.hip")
-    vo = re.search(r"vo\[hp\]\[i\] = (.*?);", s, re.S).group(1)
-    st = _call_args(s[s.index("__builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i])"):], "__builtin_amdgcn_raw_buffer_store_b128")
-    ld = _call_args(s[s.index("ext[h][i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(re"):], "__builtin_amdgcn_raw_buffer_load_b128")
-    return " ".join(vo.split()), st[2], st[3], ld[1], ld[2]
-
-
-def _halo_exprs():
-    """(kernel, input 0 / 1, offset expression) of the 3 x 3 Winograd kernels' halo loads (the transposed kernels': ctw_halo_voff of the header)."""
-    out = []
-    for name, var in (("conv_winograd.hip", "q"), ("conv_winograd4.hip", "k")):
-        s = _src(name)
-        for inp in ("0", "1"):
-            m = re.search(r"voff%s\[%s\] = (in \?.*?);" % (inp, var), s, re.S)
-            if m:
-                out.append((name, inp, " ".join(m.group(1).split())))
-    return out
-
-
-def _halo_soffsets():
-    """The stage's channel offset of every halo load: the scalar offset argument, as written in each kernel."""
-    got = {}
-    for name in ("conv_winograd.hip", "conv_winograd4.hip"):
-        s = _src(name)
-        r = s[s.index("auto rld1"):]
-        fn = re.search(r"(\w+_buf_load\w*)\(rx0, voff0\[\w\], ", r).group(1)
-        got[name] = _call_args(r, fn)[2]
-    return got
+CONV3_KERNELS = ("conv_winograd.hip", "conv_winograd4.hip", "conv_winograd_bf16.hip")
+CONV3_HEADER = "lwg_conv_wino.h"
 
 
 def test_offset_expressions_are_found():
-    """The audit below reads what it checks out of the kernels: the expressions it cuts out must be there, in the forms it knows how to drive.  The
-    transposed kernels are audited through the shared header, so the converse is checked here: neither kernel forms a store or halo offset of its
-    own, and both run the header's block walk, halo staging and store phase."""
+    """The kernels are audited through the shared headers, so the converse is checked here: no kernel forms a store or halo offset, an input
+    descriptor, a marker or a contract of its own, and each runs the header's block walk, halo offsets and (transposed kernels) store phase."""
     h = _code(CONVT_HEADER)
-    st = _call_args(h, "__builtin_amdgcn_raw_buffer_store_b128")
-    assert st[2].startswith("(int)ctw_store_voff(") and "pass" in st[2] and st[3] == "0", st       # pass offsets in the VECTOR offset (test_no_wide_buffer_store_with_register_soffset)
+    assert "(v, ry, (int)ctw_store_voff(q4, s, pass, ey0, a.YH), 0, NT)" in h      # pass offsets in the VECTOR offset (test_no_wide_buffer_store_with_register_soffset)
     assert "ctw_store_thread(q4, tide, ex0, ey0, a.ycoff, en0, a.YH, a.YW, a.YC)" in h
     assert "ctw_buf_load(rx0, voff0[q], ctw_halo_soff(st))" in h and "voff0[q] = ctw_halo_voff(tid + WG_THREADS * q, x0, y0, a.H, a.W, a.C0)" in h
     assert "ctw_has_block(o, id)" in h and "!ctw_contract_ok(*pa, pair_bytes, panel_limit)" in h
@@ -126,12 +54,40 @@ def test_offset_expressions_are_found():
         assert '#include "%s"' % CONVT_HEADER in k, name
         for call in ("CtwBlock<", "bk.setup(a, tid, id)", "bk.has_block(nblk)", "bk.rld1(", "bk.rst1(raw0, ", "ctw_store_block<", "return ctw_launch("):
             assert call in k, (name, call)
-    vo, st_off, st_soff, ld_off, ld_soff = _w4_exprs()
-    assert "W4_OOB" in vo and st_soff == "0" and ld_soff == "0"
-    assert len(_halo_exprs()) == 4                                       # two inputs in each of the two 3 x 3 kernels
-    so = _halo_soffsets()
-    assert so == {"conv_winograd.hip": "(unsigned)c * 4u", "conv_winograd4.hip": "(unsigned)c * 4u"}, so
     assert "CTW_FN unsigned ctw_halo_soff(int st) { return (unsigned)(st * KS) * 4u; }" in h
+    # the 3 x 3 kernels: csrc/lwg_conv_wino.h
+    h = _code(CONV3_HEADER)
+    for call in ("voff0[k] = cw_halo_voff(tid + nth * k, hw, nel, 1, x0, y0, a.H, a.W, a.C0, 4)", "voff1[k] = cw_halo_voff(tid + nth * k, hw, nel, 1, x0, y0, a.H, a.W, a.C1, 4)",
+                 "cw_buf_load<POLICY>(rx0, voff0[k], cw_stage_soff(c, a.C0, false, 4))", "cw_buf_load<POLICY>(r, v, cw_stage_soff(c, a.C0, true, 4))",
+                 "const bool second = cw_stage_second(c, a.C0, true)", "rx0 = cw_image_rsrc(a.x0, b, a.H, a.W, a.C0, 4u)", "rx1 = cw_image_rsrc(a.x1, b, a.H, a.W, a.C1, 4u)"):
+        assert call in h, call
+    calls = {
+        "conv_winograd.hip": ("cw_grid(a.B, H, W, N, 2 * TPB, 2 * TPB, NBV)", "cw_order(CW_COLMAJOR, gridDim.x, blockIdx.x, N / NBV, g)", "CwBlock<2, TWO> bk", "cw_block(o, id, cb, t)",
+                              "bk.locate(a, g, t, 2 * TPB, 2 * TPB, cw_n0(cb, NBV))", "bk.halo(a, tid, WG_THREADS, HALO, PLANE * 2)", "bk.rld1(a, (st + sbeg) * KS, q)",
+                              "cw_rst1(raw0 + ", "cw_has_block(o, nblk)", "cw_contract_ok(a, 64ull, CW_NO_OUT_BUFFER)", "cw_launch<", "cw_panel_args_ok(",
+                              "#define TPB 8", "#define HALO 18", "#define KS 8"),
+        "conv_winograd4.hip": ("cw_grid(a.B, H, W, N, 4 * W4_PBX, 4 * W4_PBY, NBV)", "cw_order(cw4_order_kind(LWG_W4_XCD, LWG_W4_CHUNK, SM, gridDim.x, N / NBV, Cin, N, g.tiles, g.total), gridDim.x, blockIdx.x, N / NBV, g)",
+                               "CwBlock<NQ, TWO> bk", "cw_block(o, id, cb, t)", "bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV))",
+                               "bk.halo(a, tids, NTH, W4_HW, W4_NEL)", "bk.template rld1<W4_NT_LD>(a, c, k)", "const int c = st * W4_KS;", "cw_rst1(raw0 + ", "cw_has_block(o, nblk)",
+                               "vo[hp][i] = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan)",
+                               "re, (int)cw4_out_group(vo[NVP == 2 ? h : 0][i], h, !SM), 0, W4_NT_RES)",                       # (scalar offsets: the constant 0)
+                               "ry, (int)cw4_out_group(vo[NVP == 2 ? h : 0][i], h, EPI != LWG_EPI_SPADE && !SM), 0, W4_NT_ST)",
+                               "cw_contract_ok(*pa, 144ull, 256ll)", "cw_launch<", "cw_panel_args_ok(", "#define W4_PBX 8", "#define W4_PBY 4", "#define W4_HW 34", "#define W4_HH 18",
+                               "#define W4_NEL (W4_HW * W4_HH * 2)", "#define W4_NQ 3", "NQ = SM ? 5 : W4_NQ", "NTH = SM ? 256 : W4_THREADS", "#define W4_KS 8"),
+        "conv_winograd_bf16.hip": ("cw_grid(a.B, H, W, N, 16, 16, 64)", "cw_image(g, t)", "cw_corner(g, t - b * g.bx * g.by, 16, 16, x0, y0)", "cw_n0(cb, 64)",
+                                   "cw_image_rsrc(a.x0, b, H, W, a.C0, 2u)", "cw_image_rsrc(a.x1, b, H, W, a.C1, 2u)",
+                                   "hlin[q] = cw_halo_pixel(tid + WB_THREADS * q, WB_HALO, 4 * WB_HALO_PIX, 2, x0, y0, H, W)",
+                                   "cw_halo_pixel_voff(hlin[q], tid + WB_THREADS * q, 2, use1 ? a.C1 : a.C0, 2)", "use1 = cw_stage_second(cc, a.C0, TWO)",
+                                   "soff = cw_stage_soff(cc, a.C0, TWO, 2)", "cwb_contract_ok(*pa)", "cw_launch<", "#define WB_HALO 18", "#define WB_HALO_LOADS 3", "#define WB_KS 32"),
+    }
+    for name in CONV3_KERNELS:
+        k = _code(name)
+        assert '#include "%s"' % CONV3_HEADER in k, name
+        for word in ("0xC0000000", "_OOB", "gy * W + gx", "a.M !=", "a.ntaps !=", "a.stride !=", "hipLaunchKernelGGL((lwg_conv", "lwg_allow_dynamic_lds", "done["):
+            assert word not in k, (name, word)
+        assert not re.search(r"make_buffer_rsrc\([^;]*a\.x[01]", k), name
+        for call in calls[name]:
+            assert call in k, (name, call)
 
 
 # ---- host contracts (restated from the entry points; test_host_limits_at_the_boundary checks them against the library) ----
@@ -142,6 +98,14 @@ def _convt_ok(H, W, C0, YC):
 
 def _w4_ok(H, W, C, YC):
     return H * W * C * 4 < OOB and H * W * YC * 4 + 256 < OOB
+
+
+def _w2_ok(H, W, C):
+    return H * W * C * 4 < OOB
+
+
+def _wb_ok(H, W, C):
+    return H * W * C * 2 < OOB
 
 
 def _wmax(ok, H, *rest):
@@ -190,6 +154,13 @@ def _w4_shapes():
             out.append((_hmax(_w4_ok, W, 64, YC), W, 64, N, YC, YC - N))
         W = 3001
         out.append((_hmax(_w4_ok, W, 64, YC), W, 64, N, YC, 0))
+    return out
+
+
+def _wb_shapes():
+    """(H, W, C) of the bf16 F(2x2, 3x3) kernel's contract, at its corners: the widest rows at the fewest rows, the tallest images at the fewest columns."""
+    out = [(H, _wmax(_wb_ok, H, 64), 64) for H in (1, 2, 3)] + [(_hmax(_wb_ok, W, 64), W, 64) for W in (1, 2, 3)]
+    out += [(H, W - (W - 1) % 16, C) for H, W, C in out[:3]] + [(1201, _wmax(_wb_ok, 1201, 64), 64)]
     return out
 
 
@@ -273,13 +244,121 @@ static int convt_contract(int B, int H, int W, int C0, int N, int YC, int ydt, u
 }
 """
 
+# the 3 x 3 kernels through csrc/lwg_conv_wino.h: F(4x4)'s output pixels, every kernel's halo by element index (every thread x every piece x every
+# stage of both inputs), the block walks of the fp32 kernels in every order, the three host contracts
+_CONV3 = r"""
+#include "lwg_conv_wino.h"
+// the F(4x4, 3x3) kernel's output pixels (stores; residual / SPADE epilogue loads): one pixel (ox, oyb + i), channel group chan (+ 32 h)
+template <int EPI, bool SM>
+static void w4_pixel(const Args& a, int ox, int oyb, int chan) {
+    const int W = a.W, H = a.H;
+    const u64 size = (u64)H * W * a.YC * 4ull;
+    for (int i = 0; i < 4; ++i) {
+        const unsigned vo = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan);
+        for (int h = 0; h < 2; ++h) {
+            const bool keep = ox < W && oyb + i < H;
+            const int ch = chan + (EPI == LWG_EPI_SPADE || SM ? 0 : 32 * h);
+            const u64 want = (((u64)(oyb + i) * W + ox) * a.YC + ch) * 4ull;
+            check(keep, cw4_out_group(vo, h, EPI != LWG_EPI_SPADE && !SM), 0u, want, size, ox, oyb + i, ch);      // (scalar offsets: the constant 0 of the kernel)
+            if (EPI != LWG_EPI_SPADE) {
+                const int chl = chan + (SM ? 0 : 32 * h);
+                const u64 wl = (((u64)(oyb + i) * W + ox) * a.YC + chl) * 4ull;
+                check(keep, cw4_out_group(vo, h, !SM), 0u, wl, size, ox, oyb + i, chl);
+            }
+        }
+    }
+}
+
+// a kernel's halo staging: nth threads x nq elements of a hw x hh halo in 2^lgp 16-byte pieces per pixel, stages of ks channels of ebytes bytes
+struct HaloForm { const char* name; int nth, nq, hw, hh, lgp, ebytes, ks, ex, ey; };
+static const HaloForm F22 = {"conv_winograd", 512, 2, 18, 18, 1, 4, 8, 16, 16}, F44 = {"conv_winograd4", 512, 3, 34, 18, 1, 4, 8, 32, 16},
+                      F44S = {"conv_winograd4 4-wave", 256, 5, 34, 18, 1, 4, 8, 32, 16}, FB16 = {"conv_winograd_bf16", 512, 3, 18, 18, 2, 2, 32, 16, 16};
+
+static void conv_halo(const HaloForm& f, const Args& a, int x0, int y0) {
+    const int nel = (f.hw * f.hh) << f.lgp, per = 16 / f.ebytes;
+    for (int inp = 0; inp < 2; ++inp) {
+        const int C = inp ? a.C1 : a.C0, cbeg = inp ? a.C0 : 0;
+        const u64 size = (u64)a.H * a.W * C * f.ebytes;
+        for (int i = 0; i < f.nth * f.nq; ++i) {
+            const unsigned v = cw_halo_voff(i, f.hw, nel, f.lgp, x0, y0, a.H, a.W, C, f.ebytes);
+            const int lin = cw_halo_pixel(i, f.hw, nel, f.lgp, x0, y0, a.H, a.W);
+            const int pix = i >> f.lgp, piece = i & ((1 << f.lgp) - 1), gy = y0 - 1 + pix / f.hw, gx = x0 - 1 + pix % f.hw;
+            const bool in = i < nel && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            if (v != cw_halo_pixel_voff(lin, i, f.lgp, C, f.ebytes) || (lin >= 0) != in || (in && (u64)lin != (u64)gy * a.W + gx))
+                if (bad++ < 8) printf("BAD %s element %d at (%d, %d): pixel %d, offset %u\n", where, i, x0, y0, lin, v);
+            for (int c = cbeg; c < cbeg + C; c += f.ks) {                         // the stages of this input (channels in concatenated order)
+                const u64 want = in ? (((u64)gy * a.W + gx) * C + per * piece + (c - cbeg)) * f.ebytes : 0ull;
+                check(in, v, cw_stage_soff(c, a.C0, true, f.ebytes), want, size, gx, gy, c - cbeg + per * piece);
+                if (cw_stage_second(c, a.C0, true) != (inp == 1) || cw_stage_second(c, a.C0, false) ||
+                    (!inp && cw_stage_soff(c, a.C0, false, f.ebytes) != cw_stage_soff(c, a.C0, true, f.ebytes)))       // (the one-input form: the same offset)
+                    if (bad++ < 8) printf("BAD %s stage at channel %d: input / one-input offset\n", where, c);
+            }
+        }
+    }
+}
+
+// ... at the block corners first, last and middle in x and y, and at the block where an input's bytes cross 2^31
+static void run_halo(const HaloForm& f, const Args& a) {
+    static char name[160];
+    snprintf(name, sizeof name, "%s halo H=%d W=%d C=%d+%d", f.name, a.H, a.W, a.C0, a.C1);
+    where = name;
+    const int bx = (a.W + f.ex - 1) / f.ex, by = (a.H + f.ey - 1) / f.ey;
+    for (int y : {0, (by - 1) * f.ey, (by / 2) * f.ey}) for (int x : {0, (bx - 1) * f.ex, (bx / 2) * f.ex}) conv_halo(f, a, x, y);
+    const u64 p = (1ull << 31) / ((u64)(a.C0 > a.C1 ? a.C0 : a.C1) * f.ebytes);                 // the first pixel beyond 2^31 bytes
+    if (p / a.W < (u64)a.H) conv_halo(f, a, (int)(p % a.W) / f.ex * f.ex, (int)(p / a.W) / f.ey * f.ey);
+}
+
+// every workgroup's walk over a launch of nwg workgroups: each (column block, tile) exactly once, inside the grid, no block behind the last one; the
+// order is the one the restated rule expects; spade: the 4-wave SPADE form's column map - the columns n0 .. + 15 and n0 + 32 .. + 47 of all
+// blocks tile N once (per tile)
+static void conv_walk(bool f4, int B, int H, int W, int N, int Cin, int nbv, unsigned nwg, int xcd_sw, int chunk_sw, int want_kind, bool spade) {
+    const int ex = f4 ? 32 : 16, ey = 16, ncb = N / nbv;
+    const CwGrid g = cw_grid(B, H, W, N, ex, ey, nbv);
+    if ((long long)nwg > cw_total_blocks(B, H, W, N, ex, ey, nbv)) nwg = (unsigned)g.total;          // (the launch: min(blocks, CUs) workgroups)
+    const int kind = f4 ? cw4_order_kind(xcd_sw, chunk_sw, nbv == 32, nwg, ncb, Cin, N, g.tiles, g.total) : CW_COLMAJOR;
+    u64 fails = kind != want_kind;
+    std::vector<int> seen((size_t)g.total, 0), cols((size_t)N, 0);
+    for (unsigned wg = 0; wg < nwg; ++wg) {
+        const CwOrder o = cw_order(kind, nwg, wg, ncb, g);
+        int id = (int)wg;
+        do {                                                                           // (the first block is taken unconditionally, as the kernels do)
+            int cb, t, x0 = -1, y0 = -1;
+            cw_block(o, id, cb, t);
+            const int b = t >= 0 && t < g.tiles ? cw_image(g, t) : -1, n0 = spade ? cw4_n0_spade_small(cb) : cw_n0(cb, nbv);
+            if (b >= 0) cw_corner(g, t - b * g.bx * g.by, ex, ey, x0, y0);
+            if (cb < 0 || cb >= ncb || b < 0 || b >= B || x0 < 0 || x0 >= W || y0 < 0 || y0 >= H || x0 % ex || y0 % ey || n0 < 0 || n0 + (spade ? 48 : nbv) > N) ++fails;
+            else {
+                ++seen[(size_t)cb * g.tiles + t];
+                if (t == 0) for (int k = 0; k < (spade ? 16 : nbv); ++k) { ++cols[n0 + k]; if (spade) ++cols[n0 + 32 + k]; }
+            }
+            ++walked;
+            id += (int)nwg;
+        } while (cw_has_block(o, id));
+        for (int k = 1; k < 4; ++k) if (cw_has_block(o, id + k * (int)nwg)) ++fails;
+    }
+    for (int v : seen) if (v != 1) ++fails;
+    for (int v : cols) if (v != 1) ++fails;
+    if (fails) { bad += fails; printf("BAD walk f4=%d B=%d H=%d W=%d N=%d Cin=%d nbv=%d nwg=%u xcd=%d chunk=%d kind=%d (want %d): %llu\n", (int)f4, B, H, W, N, Cin, nbv, nwg, xcd_sw, chunk_sw, kind, want_kind, fails); }
+}
+
+// which: 0 lwg_conv2d_winograd_f32 (_ws), 1 lwg_conv2d_winograd4_f32, 2 lwg_conv2d_winograd_bf16
+static int conv_contract(int which, int B, int H, int W, int C0, int C1, int N, int YC, int ycoff, int epi, int act, int M) {
+    static float dummy;
+    LwgConvArgs a = {};
+    a.x0 = a.w = a.bias = a.res = a.xn = a.mean = a.rstd = &dummy; a.y = &dummy;
+    if (C1) a.x1 = &dummy;
+    a.B = B; a.H = a.OH = a.YH = H; a.W = a.OW = a.YW = W; a.C0 = C0; a.C1 = C1; a.N = N; a.M = M;
+    a.YC = YC; a.ycoff = ycoff; a.ntaps = 9; a.stride = 1; a.omul = 1; a.epi = epi; a.act = act; a.xdt = a.ydt = which == 2 ? LWG_DT_BF16 : LWG_DT_F32;
+    for (int t = 0; t < 9; ++t) { a.dy[t] = t / 3 - 1; a.dx[t] = t % 3 - 1; }
+    return (int)(which == 2 ? cwb_contract_ok(a) : cw_contract_ok(a, which ? 144ull : 64ull, which ? 256ll : CW_NO_OUT_BUFFER));
+}
+"""
+
 _HARNESS = r"""
 #include <cstdio>
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
-#define W4_OOB 0xC0000000u
-#define W4_KS 8
 struct Args { int H, W, C0, C1, N, YH, YW, YC, ycoff; };
 typedef unsigned long long u64;
 static u64 kept = 0, dropped = 0, bad = 0, walked = 0;
@@ -296,31 +375,7 @@ static void check(bool keep, unsigned voff, unsigned soff, u64 want, u64 size, i
 
 @CONVT@
 
-// the F(4x4, 3x3) kernel's output pixels (stores; residual / SPADE epilogue loads): one pixel (ox, oyb + i), channel group chan (+ 32 h)
-template <int EPI, bool SM>
-static void w4_pixel(const Args& a, int ox, int oyb, int chan) {
-    constexpr int NVP = 1;
-    const int W = a.W, H = a.H;
-    const u64 size = (u64)H * W * a.YC * 4ull;
-    for (int i = 0; i < 4; ++i) {
-        unsigned vo[NVP][4];
-        for (int hp = 0; hp < NVP; ++hp) vo[hp][i] = @VO@;
-        for (int h = 0; h < 2; ++h) {
-            const bool keep = ox < W && oyb + i < H;
-            const int ch = chan + (EPI == LWG_EPI_SPADE || SM ? 0 : 32 * h);
-            const u64 want = (((u64)(oyb + i) * W + ox) * a.YC + ch) * 4ull;
-            check(keep, (unsigned)(@ST_OFF@), (unsigned)(@ST_SOFF@), want, size, ox, oyb + i, ch);
-            if (EPI != LWG_EPI_SPADE) {
-                const int chl = chan + (SM ? 0 : 32 * h);
-                const u64 wl = (((u64)(oyb + i) * W + ox) * a.YC + chl) * 4ull;
-                check(keep, (unsigned)(@LD_OFF@), (unsigned)(@LD_SOFF@), wl, size, ox, oyb + i, chl);
-            }
-        }
-    }
-}
-
-// halo loads: the element (gx, gy, channel quad half) of an input with C channels, the stage's channels c .. c + 7 through the scalar offset
-@HALO@
+@CONV3@
 
 static void run_convt(void (*fn)(const Args&, int, int, int), const char* name, Args a) {
     const int bx = (a.W + 15) / 16, by = (a.H + 15) / 16;
@@ -390,28 +445,76 @@ def _contract_cases():
 _PANELS = {"lwg_conv_transpose4_winograd_f32": (144, 0xffffffff), "lwg_conv_transpose4_winograd24_f32": (240, 0x7fffffff)}      # bytes per (Cin, N) pair, size limit
 
 
+# the generator's 3 x 3 layer shapes at 512 x 512 (H = W, Cin, N): residual blocks and SPADE gamma | beta pairs at 128^2, the decoder's (skip) convolutions
+_GEN512 = ((128, 256, 256), (128, 256, 512), (256, 128, 128), (256, 256, 128), (256, 128, 256), (512, 64, 64), (512, 128, 64))
+
+
+def _w4_kind(nwg, ncb, Cin, N, tiles, sm, xcd_sw, chunk_sw):
+    """The F(4x4, 3x3) kernel's block order, restated: 2 XCD-aware, 1 chunked, 0 column-block-major."""
+    nwg = min(nwg, tiles * ncb)
+    if xcd_sw and not sm and nwg % 8 == 0 and (ncb in (4, 8) or (ncb == 2 and (Cin >= 192 or xcd_sw == 2))) and nwg < tiles * ncb and tiles >= nwg // ncb:
+        return 2
+    return 1 if chunk_sw == 2 or (chunk_sw == 1 and 144 * Cin * N <= 5 << 20) else 0
+
+
+def _walk3_cases():
+    """(f4, B, H, W, N, Cin, nbv, nwg, xcd switch, chunk switch, order expected, SPADE column map) for conv_walk: the generator's layers at the benchmark's
+    frame batches on 256 workgroups and ragged launches (_walk_cases()' style; N = 128 with Cin on both sides of 192 and of the 5 MiB panel rule), F(2x2)
+    at 64 and 32 channels per block, F(4x4) in its 8-wave and 4-wave forms under the product's switches and with each order forced."""
+    shapes = [(B, S, S, N, Cin, 256) for S, Cin, N in _GEN512 for B in (300, 32, 2, 1)]
+    shapes += [(1, 40, 56, 64 * ncb, 64, nwg) for ncb in (1, 2, 4, 8) for nwg in (8, 24, 64, 250, 256, 304)]
+    shapes += [(3, 17, 100, 64 * ncb, 256, nwg) for ncb in (2, 3, 8) for nwg in (16, 40, 63)]
+    shapes += [(1, 16, 32 * t, 512, 64, 64) for t in (9, 8, 7)] + [(5, 1, 1, 128, 64, 8)]          # tiles = 9, 8, 7 against grid / ncb = 8
+    shapes += [(B, 100, 130, 128, Cin, nwg) for Cin in (128, 176, 192, 208, 272, 288) for B, nwg in ((9, 256), (9, 250), (1, 16))]
+    out = []
+    for B, H, W, N, Cin, nwg in shapes:
+        for nbv in (64, 32):
+            out.append((0, B, H, W, N, Cin, nbv, nwg, 0, 0, 0, 0))
+            tiles = B * ((H + 15) // 16) * ((W + 31) // 32)
+            for xs, cs in ((1, 1), (2, 1), (0, 2), (0, 0)):
+                out.append((1, B, H, W, N, Cin, nbv, nwg, xs, cs, _w4_kind(nwg, N // nbv, Cin, N, tiles, nbv == 32, xs, cs), 0))
+            out.append((1, B, H, W, N, Cin, 32, nwg, 1, 1, _w4_kind(nwg, N // 32, Cin, N, tiles, True, 1, 1), 1))
+    assert {c[10] for c in out if c[0] and c[6] == 64 and (c[8], c[9]) == (1, 1)} == {0, 1, 2}       # the product's rule picks each order somewhere
+    return out
+
+
+def _fp32_ok(pair, slack, B, H, W, C0, C1, N, YC, ycoff, epi, act, M):
+    """cw_contract_ok restated for the fields the cases vary (pair: panel bytes per (Cin, N); slack: None = the output is no buffer)."""
+    if M <= 0 or C0 <= 0 or C0 % 8 or C1 < 0 or C1 % 8 or (C0 + C1) % 16 or N <= 0 or N % 64 or M != B * H * W or ycoff < 0 or ycoff % 4 or YC % 4:
+        return False
+    if (act == 5 and epi != 1) or (epi == 2 and (YC * 2 != N or ycoff)) or (epi != 2 and (ycoff + N > YC or epi not in (0, 1))):
+        return False
+    return _w2_ok(H, W, max(C0, C1)) and pair * (C0 + C1) * N < 0xffffffff and (slack is None or H * W * YC * 4 + slack < OOB)
+
+
+def _bf16_ok(B, H, W, C0, C1, N, YC, ycoff, epi, act, M):
+    """cwb_contract_ok restated for the same fields."""
+    if min(B, H, W, C0, N) <= 0 or C1 < 0 or M != B * H * W or N % 64 or (C0 + C1) % 64 or YC % 8 or ycoff % 8 or ycoff < 0 or (C1 and C0 % 64):
+        return False
+    if act not in (0, 1, 2, 3) or not _wb_ok(H, W, max(C0, C1)) or 32 * (C0 + C1) * N >= OOB or B * ((H + 15) // 16) * ((W + 15) // 16) * (N // 64) >= 0x7fffffff:
+        return False
+    return (YC * 2 == N and ycoff == 0) if epi == 2 else (ycoff + N <= YC and epi in (0, 1))
+
+
+def _contract3_cases():
+    """(B, H, W, C0, C1, N, YC, ycoff, epi, act, M) for the three 3 x 3 entry points' predicates: _limit_cases()'s shapes over and under each limit,
+    the corner shapes of the audit, and one case on either side of every other size term.  M is what a caller computes in an int."""
+    rows = []
+    for _, fn, over, under in _limit_cases():
+        if fn in ("lwg_conv2d_winograd4_f32", "lwg_conv2d_winograd_f32", "lwg_conv2d_winograd_f32_ws"):
+            rows += [(kw["B"], kw["H"], kw["W"], kw["C0"], kw.get("C1", 0), kw["N"], kw["YC"], 0, 0, 0) for kw in (over, under)]
+    rows += [(1, H, W, C, C, N, YC, ycoff, 0, 0) for H, W, C, N, YC, ycoff in _w4_shapes()]
+    rows += [(1, H, W + d, C, C, 64, 64, 0, 0, 0) for H, W, C in _wb_shapes()[:6] for d in (0, 1)]                   # bf16: the input image on either side of 3 GiB
+    rows += [(1, 8, 8, 4096, 0, N, N, 0, 0, 0) for N in (7232, 7296, 16320, 16384, 24512, 24576)]                 # the panel limits: 144, 64 and 32 bytes per pair
+    rows += [((1 << 27) - d, 1, 1, 64, 0, 1024, 1024, 0, 0, 0) for d in (0, 1)]                                     # bf16: 2^31 blocks | 16 fewer
+    rows += [(65537, 1, 65536, 64, 0, 64, 64, 0, 0, 0)]                                                             # B H W = 2^32 + 65536: an int M wraps to 65536
+    rows += [(2, 20, 24, 64, 64, 128, 64, 0, 2, 1), (2, 20, 24, 64, 64, 128, 128, 0, 2, 1), (2, 20, 24, 64, 0, 64, 128, 64, 1, 5),
+             (2, 20, 24, 64, 0, 64, 128, 64, 0, 5), (2, 20, 24, 64, 0, 64, 128, 68, 1, 2), (2, 20, 24, 72, 56, 64, 68, 4, 0, 3), (2, 20, 24, 64, 0, 64, 64, 0, 3, 0)]
+    wrap = lambda m: (m + (1 << 31)) % (1 << 32) - (1 << 31)      # noqa: E731
+    return [r + (wrap(r[0] * r[1] * r[2]),) for r in rows]
+
+
 def _harness():
-    vo, st_off, st_soff, ld_off, ld_soff = _w4_exprs()
-    halo, hcalls = [], []
-    soffs = _halo_soffsets()
-    for j, (name, inp, expr) in enumerate(_halo_exprs()):
-        cvar = "a.C" + inp if "a.C" + inp in expr else "Cin"
-        so = soffs[name]
-        halo.append(textwrap.dedent("""
-        static void halo_%d(const Args& a, int gx, int gy) {
-            const int W = a.W, H = a.H, Cin = %s;
-            const u64 size = (u64)H * W * Cin * 4ull;
-            for (int half = 0; half < 2; ++half) {
-                const int hq = half;
-                const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-                const unsigned v = %s;
-                for (int c = 0; c < Cin; c += 8) {
-                    const u64 want = in ? (((u64)gy * W + gx) * Cin + 4 * half + c) * 4ull : 0ull;
-                    check(in, v, %s, want, size, gx, gy, c + 4 * half);
-                }
-            }
-        }""") % (j, cvar, expr.replace("a.C0", "Cin").replace("a.C1", "Cin"), so))
-        hcalls.append((name, j))
     main = []
     who = "%s (%s)" % (CONVT_HEADER, ", ".join(CONVT_KERNELS))
     for sh in _convt_shapes():
@@ -426,12 +529,14 @@ def _harness():
     for sh in _w4_shapes():
         H, W, C, N, YC, ycoff = sh
         a = "Args{%d, %d, %d, %d, %d, %d, %d, %d, %d}" % (H, W, C, C, N, H, W, YC, ycoff)
-        main.append("    run_w4(%s);" % a)
-        for name, j in hcalls:
-            main.append('    where = "%s halo H=%d W=%d"; for (int gy : {-1, 0, %d, %d}) for (int gx : {-1, 0, %d, %d}) halo_%d(%s, gx, gy);'
-                        % (name, H, W, H - 1, H, W - 1, W, j, a))
-    return (_HARNESS.replace("@CONVT@", _CONVT).replace("@VO@", vo).replace("@ST_OFF@", st_off).replace("@ST_SOFF@", st_soff)
-            .replace("@LD_OFF@", ld_off).replace("@LD_SOFF@", ld_soff).replace("@HALO@", "\n".join(halo)).replace("@MAIN@", "\n".join(main)))
+        main.append("    run_w4(%s); run_halo(F22, %s); run_halo(F44, %s); run_halo(F44S, %s);" % (a, a, a, a))
+    for H, W, C in _wb_shapes():
+        main.append("    run_halo(FB16, Args{%d, %d, %d, %d, 64, %d, %d, 64, 0});" % (H, W, C, C, H, W))
+    for c in _walk3_cases():
+        main.append("    conv_walk(%d, %d, %d, %d, %d, %d, %d, %du, %d, %d, %d, %d);" % c)
+    for j, c in enumerate(_contract3_cases()):
+        main.append('    printf("contract3 %d %%d%%d%%d\\n", %s);' % (j, ", ".join("conv_contract(%d, %s)" % (w, ", ".join(str(v) for v in c)) for w in (0, 1, 2))))
+    return _HARNESS.replace("@CONVT@", _CONVT).replace("@CONV3@", _CONV3).replace("@MAIN@", "\n".join(main))
 
 
 def _compiler():
@@ -442,10 +547,12 @@ def _compiler():
 
 
 def test_buffer_offsets_stay_in_32_bits_at_the_contract_edges():
-    """Every buffer access of the fp32 Winograd kernels whose offset can be the out-of-range marker plus an increment, at the corner shapes their host
+    """Every buffer access of the Winograd kernels whose offset can be the out-of-range marker plus an increment, at the corner shapes their host
     contracts accept: the stores of F(4x4, 3x3), convT F(2x2, 2x2) and convT F(2x4, 2x2) (NHWC and channel-quad planes), the residual / SPADE
-    epilogue loads of F(4x4, 3x3), the halo loads of all four.  Kept accesses land on their own pixel and channel, dropped ones at or beyond the
-    buffer's size modulo 2^32, and no expression that forms an offset overflows its C++ type (signed overflow traps)."""
+    epilogue loads of F(4x4, 3x3), the halo loads of all five (the bf16 F(2x2, 3x3) kernel's included) by element index.  Kept accesses land on
+    their own pixel and channel, dropped ones at or beyond the buffer's size modulo 2^32, and no expression that forms an offset overflows its C++
+    type (signed overflow traps).  The block walks visit every block once in the order the restated rules expect, and the host contracts agree
+    with their restatements on both sides of every size limit."""
     src = _harness()
     with tempfile.TemporaryDirectory() as d:
         cpp, exe = os.path.join(d, "audit.cpp"), os.path.join(d, "audit")
@@ -454,7 +561,7 @@ def test_buffer_offsets_stay_in_32_bits_at_the_contract_edges():
         r = subprocess.run([_compiler(), *flags, "-I", CSRC, cpp, "-o", exe], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-3000:]
         r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    out = "\n".join(ln for ln in r.stdout.splitlines() if not ln.startswith(("conv", "lwg_convt", "contract")))
+    out = "\n".join(ln for ln in r.stdout.splitlines() if not ln.startswith(("lwg_convt", "contract")))
     assert r.returncode >= 0, "signed overflow in an offset expression (trapped) at: " + r.stdout.strip().splitlines()[-1:].__repr__()
     assert r.returncode == 0, out[-3000:]
     kept, dropped = (int(v) for v in re.search(r"kept (\d+) dropped (\d+)", r.stdout).groups())
@@ -468,6 +575,15 @@ def test_buffer_offsets_stay_in_32_bits_at_the_contract_edges():
     for j, (fn, B, H, W, C0, N, YC, ydt) in enumerate(cases):
         assert got[j] == int(_convt_ok(H, W, C0, YC)), (fn, B, H, W, C0, N, YC, ydt, got[j])
     assert 0 < sum(got.values()) < len(cases)
+    # ... and the 3 x 3 entry points' (cw_contract_ok with each fp32 kernel's panel and output slack, cwb_contract_ok)
+    got = dict((int(i), v) for i, v in re.findall(r"^contract3 (\d+) (\d\d\d)$", r.stdout, re.M))
+    cases = _contract3_cases()
+    assert len(got) == len(cases)
+    for j, c in enumerate(cases):
+        want = "%d%d%d" % (_fp32_ok(64, None, *c), _fp32_ok(144, 256, *c), _bf16_ok(*c))
+        assert got[j] == want, (c, got[j], want)
+    for w in range(3):
+        assert 0 < sum(int(v[w]) for v in got.values()) < len(cases)
 
 
 # ---- host limits ----
