@@ -235,6 +235,21 @@ int lwg_conv2d_wgrad_nhwc_f32(const LwgConvArgs* args, const float* dy, float* d
 int lwg_conv2d_wgrad_unpacked_f32(const LwgConvArgs* args, const float* dy, float* ws, float* dw, int D0, int D1, int KH, int KW,
                                   int transposed, const int* kidx, int cin, int nout, float* db, lwg_stream_t stream);
 int lwg_colsum_nhwc_f32(const float* x, size_t rows, int C, float* out, float* ws, lwg_stream_t stream);
+/* The weight gradient of a 3x3 / stride 1 / pad 1 convolution in F(2x2, 3x3) Winograd form (csrc/conv_wgrad_winograd.hip): dU = sum over the 2x2
+ * output tiles of (B^T d B) (A dy A^T) as 16 GEMMs on the fp32 matrix pipe - 16 products per tile and channel pair instead of 36 -, both operands
+ * transformed inside the kernel, then dw = G^T dU G in the reduction launch.  fp32-grade (0.67 - 1.9x the direct kernel's relative L2 error against fp64 on the tested operands, table in DESIGN.md 3.10b), not
+ * the bits of lwg_conv2d_wgrad_unpacked_f32; deterministic (slabs added in slab order, no float atomics).  Opt-in: nothing selects it by default.
+ * `args` is the FORWARD launch description as for lwg_conv2d_wgrad_unpacked_f32 (args->y / w / bias / epi / act are ignored): fp32 x0 (B,H,W,C0) /
+ *   x1 (B,H,W,C1), C0 % 64 == 0, C1 % 64 == 0 (0: no x1), N % 64 == 0, ntaps == 9 with tap t = (dy, dx) = (t / 3 - 1, t % 3 - 1), stride 1, omul 1,
+ *   ooy = oox = 0, OH == YH == H, OW == YW == W, M == B H W; dy (B,H,W,YC) holds column n at ycoff + n (ycoff + N <= YC); x0, x1 and dy each
+ *   < 3 GiB (32-bit buffer offsets).  dw: (nout, cin, 3, 3) contiguous - nn.Conv2d's layout -, cin <= C0 + C1 and nout <= N drop the zero-extended
+ *   channels.  ws: lwg_conv2d_wgrad_winograd_ws_floats(args) floats: a function of the launch shape and the CU count of the current device, which
+ *   it queries (hipGetDevice + hipDeviceGetAttribute, cached; 256 CUs are assumed where no device answers); 0 for NULL or a launch outside the
+ *   contract.  The bias gradient is not part of it (lwg_colsum_nhwc_f32).
+ * Returns 0, or 1 (hipErrorInvalidValue) - checked on the host before any launch - for a NULL pointer, cin < 1, nout < 1, cin > C0 + C1, nout > N or
+ * a launch outside the contract. */
+size_t lwg_conv2d_wgrad_winograd_ws_floats(const LwgConvArgs* args);
+int lwg_conv2d_wgrad_winograd_f32(const LwgConvArgs* args, const float* dy, float* ws, float* dw, int cin, int nout, lwg_stream_t stream);
 
 /* Elementwise / normalisation pieces of the personalization step and their backward (csrc/train_ops.hip); NHWC fp32.
  *   act codes: LWG_ACTIVATION_* plus 4 = LeakyReLU(0.2) (discriminators/patch_dis.py:33-47).

@@ -220,9 +220,18 @@ def wgrad_to_conv(dwk, ntaps, cin_packed, cin, n, kh, kw):
     return unpack_wgrad(dwk, ntaps, cin_packed)[:, :cin, :n].reshape(kh, kw, cin, n).permute(3, 2, 0, 1).contiguous()
 
 
+def wgrad_conv_is_winograd(x0, spec, dy, x1, kh, kw):
+    """Does ``wgrad_conv`` run this launch on the F(2x2, 3x3) Winograd weight-gradient kernel (ops.WGRAD_PRECISION = "winograd" and the launch is
+    eligible)?  Such a launch carries no fused bias gradient."""
+    return ops.WGRAD_PRECISION == "winograd" and kh == 3 and kw == 3 and ops._wgrad_wino_use(x0, spec, dy, x1)
+
+
 def wgrad_conv(x0, spec, dy, x1, kh, kw, cin, n, db=None):
     """nn.Conv2d weight gradient (N, Cin, kh, kw) of the launch ``spec``: on the device ONE reduction launch writes it in place
     (ops.conv2d_wgrad_unpacked) - and the bias gradient into ``db`` (n,) when given; the host-logic tests take the two-step form."""
+    if wgrad_conv_is_winograd(x0, spec, dy, x1, kh, kw):
+        assert db is None, "the Winograd weight gradient carries no bias gradient (ops.colsum)"
+        return ops.conv2d_wgrad_winograd(x0, spec, dy, torch.empty(n, cin, 3, 3, device=dy.device, dtype=torch.float32), cin, n, x1=x1)
     if dy.is_cuda:
         return ops.conv2d_wgrad_unpacked(x0, spec, dy, torch.empty(n, cin, kh, kw, device=dy.device, dtype=torch.float32), False,
                                          range(kh * kw), cin, n, x1=x1, db=db)

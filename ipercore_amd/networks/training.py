@@ -137,6 +137,8 @@ class ConvFn(torch.autograd.Function):
         # the bias gradient of a convolution rides along with its weight gradient (the column sums of dy in the launch that stages dy
         # anyway: FUSED_BIAS_GRAD); a transposed convolution's four parity launches each see a quarter of dy -> the column-sum kernel
         fused_db = FUSED_BIAS_GRAD and want_db and want_dw and cfg.kind == "conv"
+        if fused_db and packing.wgrad_conv_is_winograd(x0, specs[0], dy, x1, weight.shape[2], weight.shape[3]):
+            fused_db = False                                         # the Winograd weight gradient (ops.wgrad_precision) stages no dy rows: column sums
         db = None
         if want_db:
             db = torch.empty(N, device=dev, dtype=torch.float32) if fused_db else ops.colsum(dy)[:N]

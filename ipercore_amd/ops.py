@@ -1096,6 +1096,63 @@ def conv2d_wgrad_unpacked(x0, spec, dy, dw, transposed, kidx, cin, nout, x1=None
     return dw
 
 
+# "direct": every weight gradient on lwg_conv_wgrad_kernel.  "winograd": the 3x3 / stride 1 / pad 1 launches with both channel counts % 64 == 0
+# (_wgrad_wino_use) run lwg_conv2d_wgrad_winograd_f32 - dU = sum V^T Z, dw = G^T dU G: 16 products per 2x2 output tile and channel pair instead of
+# 36 (csrc/conv_wgrad_winograd.hip); fp32-grade, not the direct kernel's bits, bias gradient by ops.colsum.  Every other launch exactly as "direct".
+WGRAD_PRECISION = "direct"
+
+
+class wgrad_precision(object):
+    """Context manager: ``with ops.wgrad_precision("winograd"): ...`` (trainers.TrainOpts.wgrad_precision)."""
+
+    def __init__(self, mode):
+        assert mode in ("direct", "winograd")
+        self.mode = mode
+
+    def __enter__(self):
+        global WGRAD_PRECISION
+        self.prev = WGRAD_PRECISION
+        WGRAD_PRECISION = self.mode
+
+    def __exit__(self, *exc):
+        global WGRAD_PRECISION
+        WGRAD_PRECISION = self.prev
+
+
+def _wgrad_wino_use(x0, spec, dy, x1=None):
+    """Launches lwg_conv2d_wgrad_winograd_f32 takes (its C contract): fp32 device tensors, 3x3 / stride 1 / pad 1 with the taps ascending in (dy, dx),
+    C0 % 64 == 0, C1 % 64 == 0, N % 64 == 0, dy dense (B, H, W, N), every tensor < 3 GiB."""
+    if not (x0.is_cuda and dy.is_cuda) or x0.dtype != torch.float32 or dy.dtype != torch.float32 or x0.dim() != 4 or dy.dim() != 4:
+        return False
+    if x1 is not None and (not x1.is_cuda or x1.dtype != torch.float32 or x1.shape[:3] != x0.shape[:3] or x1.shape[3] % 64 != 0):
+        return False
+    C1 = 0 if x1 is None else x1.shape[3]
+    if spec.ntaps != 9 or spec.stride != 1 or spec.omul != 1 or spec.ooy != 0 or spec.oox != 0 or x0.shape[3] % 64 != 0 or spec.N % 64 != 0 or \
+            x0.shape[3] + C1 != spec.Cin or list(zip(spec.dy, spec.dx)) != _WINO_TAPS:
+        return False
+    if tuple(dy.shape) != (x0.shape[0], x0.shape[1], x0.shape[2], spec.N):
+        return False
+    pix = x0.shape[0] * x0.shape[1] * x0.shape[2]
+    return pix * max(x0.shape[3], C1, spec.N) * 4 < 0xC0000000
+
+
+def conv2d_wgrad_winograd(x0, spec, dy, dw, cin, nout, x1=None):
+    """The weight gradient of an eligible 3x3 launch (``_wgrad_wino_use``) in F(2x2, 3x3) Winograd form, written into dw (nout, cin, 3, 3)
+    (lwg_conv2d_wgrad_winograd_f32: one fused slab launch + one reduction launch; no bias gradient - ``colsum``)."""
+    a = conv_args(x0, spec, dy, x1=x1)
+    assert dw.is_contiguous() and tuple(dw.shape) == (nout, cin, 3, 3)
+    nws = _lib.lib().lwg_conv2d_wgrad_winograd_ws_floats(a)
+    if nws == 0:
+        raise ValueError("launch outside lwg_conv2d_wgrad_winograd_f32's contract (ops._wgrad_wino_use)")
+    if CONV_HOOK is not None:
+        CONV_HOOK(True, a.M, spec, EPI_NONE, None)
+    ws = torch.empty(nws, device=x0.device, dtype=torch.float32)
+    _lib.check(_lib.lib().lwg_conv2d_wgrad_winograd_f32(a, _ptr(dy), _ptr(ws), _ptr(dw), cin, nout, _stream()), "lwg_conv2d_wgrad_winograd_f32")
+    if CONV_HOOK is not None:
+        CONV_HOOK(False, a.M, spec, EPI_NONE, {"kernels": 2, "kind": "wgrad_winograd"})
+    return dw
+
+
 class PanelCache:
     """The panels of a training step, re-packed by ONE launch per step (lwg_pack_panels_f32) instead of one launch per panel.
 

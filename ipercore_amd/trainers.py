@@ -642,6 +642,10 @@ class TrainOpts(object):
     # ops.WINO_MIN_GRID), everything else - and every weight gradient - on the direct fp32 MFMA kernels; "fp32": all direct;
     # "split": forward and data-gradient convs with Cin % 32 == 0 on the bf16x6 kernel (fp32-level accuracy)
     conv_precision = "winograd"
+    # "direct": every weight gradient on the direct fp32 MFMA kernel.  "winograd" (opt-in): the 3 x 3 / stride 1 weight gradients with both
+    # channel counts % 64 == 0 in F(2x2,3x3) Winograd form (ops.wgrad_precision, csrc/conv_wgrad_winograd.hip): fp32-grade,
+    # not the direct kernel's bits; their bias gradients come from the column-sum kernel
+    wgrad_precision = "direct"
     # "VGG19": the transfer loss is the VGG19 perceptual loss (deploy.toml:83, the reference's default) instead of L1;
     # vgg_loss_path: torchvision vgg19 state_dict (used when the file exists, seeded weights otherwise)
     use_vgg = "VGG19"
@@ -903,7 +907,7 @@ class LWGTrainer(object):
         prev = ops.PANEL_CACHE, ops.BRANCH_STREAM
         ops.PANEL_CACHE, ops.BRANCH_STREAM = getattr(self, "_panel_cache", None), getattr(self, "_branch_stream", None)
         try:
-            with ops.conv_precision(self.opts.conv_precision):
+            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_precision(getattr(self.opts, "wgrad_precision", "direct")):
                 if self._graphable():
                     return self._graph_step()
                 if getattr(self.opts, "dp_schedule", "hooks") == "segmented" and self._multi():
@@ -1059,6 +1063,9 @@ class LWGTrainer(object):
         if self._graphs["dp"] != multi:                      # captured for the other form (a process group appeared / went away)
             self._graphs = None
             return self._graph_step()
+        if self._graphs["wgrad"] != ops.WGRAD_PRECISION:     # the weight-gradient kernels are frozen into the graph too
+            self._graphs = None
+            return self._graph_step()
         gr = self._graphs
         if multi:
             # [A: G fwd / bwd] -> {G's all-reduce on RCCL's stream || [D: D fwd / bwd on the second stream]} -> {Adam(G) || D's all-reduce}
@@ -1161,7 +1168,7 @@ class LWGTrainer(object):
                 self.optimizer_D.step()
         for o, sn in zip(opts_, snaps):                     # capturing step() advanced the host mirrors only; nothing ran on the device
             o.t = sn[4]
-        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi}
+        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION}
         self._captured_lr = (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr)
         self._static_losses = (loss_G.detach(), None if loss_D is None else loss_D.detach())
         self._static_inp = self.inp
