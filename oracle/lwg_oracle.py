@@ -573,6 +573,14 @@ def morph(mask, ks, mode="erode"):
     return (out >= 1).float()
 
 
+def soft_dilate(mask, ks):
+    """tools/utils/morphology/morph_ops.py:38-60: at least half of the ks x ks window (zero padded) is set."""
+    n_ks, pad_s = ks ** 2, ks // 2
+    kernel = torch.ones(1, 1, ks, ks, dtype=torch.float32)
+    out = F.conv2d(F.pad(mask, [pad_s] * 4, value=0.0), kernel)
+    return (out >= n_ks / 2).float()
+
+
 def canny_kernels():
     """canny_ops.py:9-36 gaussian / sobel (float64 -> float32 like the reference's weight assignment) and the 8
     directional kernels of :39-68.  cv2 is absent here, so the directional kernels are restated as what
@@ -655,12 +663,13 @@ def top_k_nearest(uncertain_pts, boundary_pts, top_k=3, chunk=4096):
     return v / torch.sum(v, dim=1, keepdim=True), ids, vals
 
 
-def make_morph_image(src_img, confidant_sil, outpad_sil):
-    """flowcomposition.py:295-386 with erode_ks = dilate_ks = 0 (the reference's call, :482-483).
+def make_morph_image(src_img, confidant_sil, outpad_sil, thin=None):
+    """flowcomposition.py:295-386 with erode_ks = dilate_ks = 0 (the reference's call, :482-483).  thin: an edge map to use in place
+    of canny(confidant_sil) (tests that need an exact number of boundary pixels).
     Returns (morph_img (n,3,h,w), thin_edges, tie_mask (n,h,w) bool: pixels whose 3rd and 4th nearest boundary
     distances coincide - there the reference's own result depends on the topk backend)."""
     n, _, h, w = src_img.shape
-    thin = canny(confidant_sil, 0.1, 0.9)
+    thin = canny(confidant_sil, 0.1, 0.9) if thin is None else thin
     uncertain_sil = outpad_sil * (1 - confidant_sil)
     outs, ties = [], torch.zeros(n, h, w, dtype=torch.bool)
     for i in range(n):

@@ -327,6 +327,26 @@ def test_source_stage_matches_reference(topo):
     assert np.array_equal(orc.morph(frac, 13, "dilate").numpy().astype(np.uint8), g["morph/dilate13_frac"])
 
 
+def golden_morph():
+    """tests/golden/golden_morph_v1.npz -> (masks (7,1,40,56) fp32 in k/8, ks list, {mode: (7, n_ks, 40, 56) uint8})."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_morph_v1.npz"))
+    masks = torch.tensor(g["masks8"].astype(np.float32) / 8.0).unsqueeze(1)
+    return masks, [int(k) for k in g["ks"]], {m: g[m] for m in ("erode", "dilate", "soft_dilate")}
+
+
+def test_morph_and_soft_dilate_match_reference():
+    """orc.morph / orc.soft_dilate vs the reference's own morph_ops.py (tests/golden/make_golden_morph.py): non-square masks on the border
+    (binary and k/8), ks 1..51 with 51 larger than the image.  Exact: every sum is a multiple of 1/8."""
+    masks, ks_list, want = golden_morph()
+    assert masks.shape == (7, 1, 40, 56) and ks_list == [1, 3, 5, 13, 21, 51]
+    for j, ks in enumerate(ks_list):
+        assert np.array_equal(orc.morph(masks, ks, "erode")[:, 0].numpy().astype(np.uint8), want["erode"][:, j]), ks
+        assert np.array_equal(orc.morph(masks, ks, "dilate")[:, 0].numpy().astype(np.uint8), want["dilate"][:, j]), ks
+        assert np.array_equal(orc.soft_dilate(masks, ks)[:, 0].numpy().astype(np.uint8), want["soft_dilate"][:, j]), ks
+    # the fixture is not trivial: the three modes differ from each other and from the input somewhere at ks = 3
+    assert not np.array_equal(want["dilate"][:, 1], want["soft_dilate"][:, 1]) and not np.array_equal(want["erode"][:, 1], want["soft_dilate"][:, 1])
+
+
 # ---------------------------------------------------------------------------------------------- temporal attention
 def _temporal_inputs(golden):
     """Same seeds as tests/golden/make_golden_temporal.py::temporal_inputs."""
