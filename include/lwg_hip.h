@@ -385,6 +385,19 @@ int lwg_lwb_attention_kv_bwd_f32(const float* q, const float* kv, const float* b
  * Add: (1, 1); Avg: scale_o = 1/(ns+1); SoftGateAdd: gate, (1, 1); SoftGateAvg: gate, scale_w = 1/ns.  Layouts as above. */
 int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const float* gate, const float* T, float* out, int B, int ns,
                      int h, int w, int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream);
+/* Backward of lwg_lwb_fuse_f32 (the training step of the AddLWB / AvgLWB / SoftGateLWB generators).  dout (B,h,w,C) upstream gradient:
+ *   d_tsf  = scale_o * dout                                               written, (B,h,w,C)
+ *   d_gate = scale_o * scale_w * dout * sum_s warp_s(src_x)               written, (B,h,w,C); only when gate != NULL (gathers recomputed)
+ *   d_src[sidx(b,s)][tap] += w_tap * scale_o * scale_w * gate * dout      ACCUMULATED with fp32 atomics over the in-range bilinear taps:
+ *                                                                         d_src (shaped like src_x) must be zero on entry; sidx = b*ns+s
+ *                                                                         if src_batched else s (shared sources: the B frames add up)
+ * Same flow resize / grid_sample / tap conventions as the forward (one shared device helper); the flows are not differentiated.
+ * src_x may be NULL when gate is NULL.  C in {32,64,128,256}, ns <= 64.  Returns 1 before any launch on: NULL T / dout / d_tsf / d_src,
+ * gate without d_gate or without src_x, an unsupported C, ns > 64, a non-positive size.  The sums into d_src depend on arrival order in
+ * the last bits. */
+int lwg_lwb_fuse_bwd_f32(const float* src_x, const float* gate, const float* T, const float* dout, float* d_tsf, float* d_src,
+                         float* d_gate, int B, int ns, int h, int w, int C, int S, int src_batched, float scale_w, float scale_o,
+                         lwg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Renderer (replaces the `neural_renderer` CUDA package as used by renders/nmr.py).

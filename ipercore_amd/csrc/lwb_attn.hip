@@ -417,6 +417,60 @@ extern "C" int lwg_lwb_attention_kv_bwd_f32(const float* q, const float* kv, con
 //   SoftGateLWB          generators/lwb_softgate_resunet.py:77-123   out = tsf_x + gate * (sum | mean over the warped sources)
 // as one gather kernel:   out = (tsf_x + gate * scale_w * sum_s warp_s(src_x)) * scale_o      (gate == nullptr: 1)
 // Same flow resize / grid_sample conventions, lane mapping and 16-byte gathers as lwg_lwb_attn_kernel.
+// The flow resize / grid_sample / tap-clamping expressions of the fusion block, shared by its forward and its backward kernel (one
+// copy: the backward scatters to exactly the taps, with exactly the weights, the forward gathered from).
+struct LwgFuseResize {      // per pixel: flow resize S x S -> h x w, bilinear, align_corners=True (ATen area_pixel_compute_source_index)
+    int y0, x0, y1, x1;
+    float ly0, ly1, lx0, lx1;
+    bool same;
+};
+struct LwgFuseTaps {        // per pixel and source: top-left tap (clamped to [-2, size + 1]) and the bilinear weights of grid_sample
+    int tx0, ty0;
+    float wx0, wx1, wy0, wy1;
+};
+
+__device__ __forceinline__ LwgFuseResize lwg_fuse_resize(int y, int x, int h, int w, int S) {
+    LwgFuseResize r;
+    const float sc_y = h > 1 ? (float)(S - 1) / (float)(h - 1) : 0.f;
+    const float sc_x = w > 1 ? (float)(S - 1) / (float)(w - 1) : 0.f;
+    const float sy = sc_y * (float)y, sx = sc_x * (float)x;
+    r.y0 = (int)sy; r.x0 = (int)sx;
+    r.y1 = r.y0 + (r.y0 < S - 1 ? 1 : 0); r.x1 = r.x0 + (r.x0 < S - 1 ? 1 : 0);
+    r.ly1 = sy - (float)r.y0; r.lx1 = sx - (float)r.x0;
+    r.ly0 = 1.f - r.ly1; r.lx0 = 1.f - r.lx1;
+    r.same = (h == S) && (w == S);
+    return r;
+}
+
+// Tp: the (S,S,2) flow of this frame and source
+__device__ __forceinline__ LwgFuseTaps lwg_fuse_taps(const float2* __restrict__ Tp, const LwgFuseResize& r, int y, int x, int h, int w, int S) {
+    float gx, gy;
+    if (r.same) {
+        const float2 t = Tp[(size_t)y * S + x];
+        gx = t.x; gy = t.y;
+    } else {
+        const float2 t00 = Tp[(size_t)r.y0 * S + r.x0], t01 = Tp[(size_t)r.y0 * S + r.x1];
+        const float2 t10 = Tp[(size_t)r.y1 * S + r.x0], t11 = Tp[(size_t)r.y1 * S + r.x1];
+        gx = r.ly0 * (r.lx0 * t00.x + r.lx1 * t01.x) + r.ly1 * (r.lx0 * t10.x + r.lx1 * t11.x);
+        gy = r.ly0 * (r.lx0 * t00.y + r.lx1 * t01.y) + r.ly1 * (r.lx0 * t10.y + r.lx1 * t11.y);
+    }
+    // grid_sample, align_corners=False: pixel = ((g + 1) * size - 1) / 2
+    const float ix = ((gx + 1.f) * (float)w - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)h - 1.f) * 0.5f;
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    LwgFuseTaps p;
+    p.wx1 = ix - fx0; p.wy1 = iy - fy0; p.wx0 = (fx0 + 1.f) - ix; p.wy0 = (fy0 + 1.f) - iy;
+    // clamp before the int conversion so wild flows cannot overflow; out-of-range taps are skipped anyway
+    p.tx0 = (int)fminf(fmaxf(fx0, -2.f), (float)w + 1.f); p.ty0 = (int)fminf(fmaxf(fy0, -2.f), (float)h + 1.f);
+    return p;
+}
+
+// tap t in 0..3 (row-major 2 x 2): its pixel, its weight, and whether it lies inside the h x w source map (zero padding otherwise)
+__device__ __forceinline__ bool lwg_fuse_tap(const LwgFuseTaps& p, int t, int h, int w, int& ty, int& tx, float& wt) {
+    ty = p.ty0 + (t >> 1); tx = p.tx0 + (t & 1);
+    wt = ((t >> 1) ? p.wy1 : p.wy0) * ((t & 1) ? p.wx1 : p.wx0);
+    return ty >= 0 && ty < h && tx >= 0 && tx < w;
+}
+
 template <int LPP>
 __global__ __launch_bounds__(256) void lwg_lwb_fuse_kernel(const float* __restrict__ tsf, const float* __restrict__ src,
                                                           const float* __restrict__ gate, const float* __restrict__ T,
@@ -432,41 +486,19 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_kernel(const float* __restri
     const int hw = h * w;
     const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
     const int y = rem / w, x = rem - y * w;
-
-    const float sc_y = h > 1 ? (float)(S - 1) / (float)(h - 1) : 0.f;
-    const float sc_x = w > 1 ? (float)(S - 1) / (float)(w - 1) : 0.f;
-    const float sy = sc_y * (float)y, sx = sc_x * (float)x;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < S - 1 ? 1 : 0), x1 = x0 + (x0 < S - 1 ? 1 : 0);
-    const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
-    const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
-    const bool same = (h == S) && (w == S);
+    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
 
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < ns; ++s) {
-        const float2* Tp = reinterpret_cast<const float2*>(T) + ((size_t)b * ns + s) * S * S;
-        float gx, gy;
-        if (same) {
-            const float2 t = Tp[(size_t)y * S + x];
-            gx = t.x; gy = t.y;
-        } else {
-            const float2 t00 = Tp[(size_t)y0 * S + x0], t01 = Tp[(size_t)y0 * S + x1];
-            const float2 t10 = Tp[(size_t)y1 * S + x0], t11 = Tp[(size_t)y1 * S + x1];
-            gx = ly0 * (lx0 * t00.x + lx1 * t01.x) + ly1 * (lx0 * t10.x + lx1 * t11.x);
-            gy = ly0 * (lx0 * t00.y + lx1 * t01.y) + ly1 * (lx0 * t10.y + lx1 * t11.y);
-        }
-        const float ix = ((gx + 1.f) * (float)w - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)h - 1.f) * 0.5f;
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.f) - ix, wy0 = (fy0 + 1.f) - iy;
-        const int tx0 = (int)fminf(fmaxf(fx0, -2.f), (float)w + 1.f), ty0 = (int)fminf(fmaxf(fy0, -2.f), (float)h + 1.f);
+        const LwgFuseTaps tp = lwg_fuse_taps(reinterpret_cast<const float2*>(T) + ((size_t)b * ns + s) * S * S, rz, y, x, h, w, S);
         const size_t sidx = src_batched ? (size_t)b * ns + s : (size_t)s;
         const float* Sb = src + sidx * hw * C + 4 * cl;
         floatx4 wv = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int ty = ty0 + (t >> 1), tx = tx0 + (t & 1);
-            const float wt = ((t >> 1) ? wy1 : wy0) * ((t & 1) ? wx1 : wx0);
-            if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
+            int ty, tx;
+            float wt;
+            if (lwg_fuse_tap(tp, t, h, w, ty, tx, wt)) {
                 const floatx4 v4 = *reinterpret_cast<const floatx4*>(Sb + ((size_t)ty * w + tx) * C);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) wv[k] += v4[k] * wt;
@@ -504,5 +536,109 @@ extern "C" int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const fl
         default: return (int)hipErrorInvalidValue;
     }
 #undef LWG_FUSE_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backward of the fusion block (personalization of the AddLWB / AvgLWB / SoftGateLWB generators).  With upstream gradient dout:
+//   d_tsf  = scale_o * dout                                                   (written)
+//   d_gate = scale_o * scale_w * dout * sum_s warp_s(src)                     (written; gate given only; gathers recomputed)
+//   d_src[sidx(b, s)][tap] += w_tap * (scale_o * scale_w * gate * dout)       (ACCUMULATED: fp32 atomics; zero d_src first)
+// The flows are not differentiated.  One pixel per LPP = C/4 lanes.  Everything that is loaded, gathered or stored plainly uses the
+// forward's mapping (lane cl owns channels 4 cl .. 4 cl + 3: 16-byte accesses).  The scattered value v = scale_o * scale_w * gate * dout
+// is the same for every source and tap of a pixel - only w_tap differs - so it is transposed ONCE per pixel through LDS to a
+// channel-interleaved mapping (lane cl owns channels cl, cl + LPP, cl + 2 LPP, cl + 3 LPP): each of the four atomic wave-instructions
+// of a tap then adds a contiguous 4 LPP = C-byte run per pixel (256 B at C = 256, two 128-B rows at C = 128) instead of 64 dwords
+// 16 bytes apart.  No per-source state is kept: scatter and gather of a source share one pass over its taps.
+template <int LPP>
+__global__ __launch_bounds__(256) void lwg_lwb_fuse_bwd_kernel(const float* __restrict__ src, const float* __restrict__ gate,
+                                                              const float* __restrict__ T, const float* __restrict__ dout,
+                                                              float* __restrict__ d_tsf, float* __restrict__ d_src,
+                                                              float* __restrict__ d_gate, int B, int ns, int h, int w, int S,
+                                                              int src_batched, float scale_w, float scale_o) {
+    constexpr int C = 4 * LPP;
+    constexpr int PPW = 64 / LPP;
+    __shared__ float vt[256 * 4];                 // per wave: its PPW pixels x C channels of v
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int cl = lane % LPP, pl = lane / LPP;
+    const long total = (long)B * h * w;
+    long gp = ((long)blockIdx.x * 4 + wid) * PPW + pl;
+    const bool live = gp < total;
+    if (!live) gp = total - 1;                    // every lane reaches the barrier; a dead lane stores and adds nothing
+    const int hw = h * w;
+    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
+    const int y = rem / w, x = rem - y * w;
+    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
+
+    const floatx4 do4 = *reinterpret_cast<const floatx4*>(dout + gp * C + 4 * cl);
+    floatx4 g4 = {1.f, 1.f, 1.f, 1.f};
+    if (gate) g4 = *reinterpret_cast<const floatx4*>(gate + gp * C + 4 * cl);
+    const float sow = scale_o * scale_w;
+    floatx4 dt4, v4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { dt4[k] = do4[k] * scale_o; v4[k] = sow * g4[k] * do4[k]; }
+    if (live) *reinterpret_cast<floatx4*>(d_tsf + gp * C + 4 * cl) = dt4;
+
+    float* vw = vt + wid * 256 + pl * C;          // this pixel's C floats
+    *reinterpret_cast<floatx4*>(vw + 4 * cl) = v4;
+    __syncthreads();
+    float vi[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) vi[k] = vw[cl + k * LPP];
+
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < ns; ++s) {
+        const LwgFuseTaps tp = lwg_fuse_taps(reinterpret_cast<const float2*>(T) + ((size_t)b * ns + s) * S * S, rz, y, x, h, w, S);
+        const size_t sidx = src_batched ? (size_t)b * ns + s : (size_t)s;
+        float* dSb = d_src + sidx * hw * C + cl;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            int ty, tx;
+            float wt;
+            if (lwg_fuse_tap(tp, t, h, w, ty, tx, wt)) {
+                const size_t off = ((size_t)ty * w + tx) * C;
+                if (gate) {
+                    const floatx4 s4 = *reinterpret_cast<const floatx4*>(src + sidx * hw * C + off + 4 * cl);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[k] += s4[k] * wt;
+                }
+                if (live) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) atomicAdd(dSb + off + k * LPP, wt * vi[k]);
+                }
+            }
+        }
+    }
+    if (gate && live) {
+        floatx4 dg4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dg4[k] = sow * do4[k] * acc[k];
+        *reinterpret_cast<floatx4*>(d_gate + gp * C + 4 * cl) = dg4;
+    }
+}
+
+// dout / d_tsf / gate / d_gate (B,h,w,C); src_x / d_src (ns,h,w,C) or (B*ns,h,w,C); T (B,ns,S,S,2).  d_tsf (and d_gate when a gate is
+// given) are written; d_src is ACCUMULATED into (zero it first).  src_x may be NULL when gate is NULL.  ns <= 64, C in {32,64,128,256}.
+extern "C" int lwg_lwb_fuse_bwd_f32(const float* src_x, const float* gate, const float* T, const float* dout, float* d_tsf, float* d_src,
+                                    float* d_gate, int B, int ns, int h, int w, int C, int S, int src_batched, float scale_w,
+                                    float scale_o, lwg_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (!T || !dout || !d_tsf || !d_src || (gate && (!d_gate || !src_x)) || B <= 0 || ns <= 0 || ns > 64 || h <= 0 || w <= 0 || S <= 0)
+        return (int)hipErrorInvalidValue;
+    const long total = (long)B * h * w;
+#define LWG_FUSE_BWD_LAUNCH(LPP)                                                                                      \
+    {                                                                                                                 \
+        const long per_block = 4 * (64 / LPP);                                                                        \
+        hipLaunchKernelGGL(lwg_lwb_fuse_bwd_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, stream, \
+                           src_x, gate, T, dout, d_tsf, d_src, d_gate, B, ns, h, w, S, src_batched, scale_w, scale_o);            \
+    }
+    switch (C) {
+        case 32: LWG_FUSE_BWD_LAUNCH(8) break;
+        case 64: LWG_FUSE_BWD_LAUNCH(16) break;
+        case 128: LWG_FUSE_BWD_LAUNCH(32) break;
+        case 256: LWG_FUSE_BWD_LAUNCH(64) break;
+        default: return (int)hipErrorInvalidValue;
+    }
+#undef LWG_FUSE_BWD_LAUNCH
     return (int)hipGetLastError();
 }

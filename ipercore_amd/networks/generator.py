@@ -247,7 +247,7 @@ class AttentionLWBGenerator(nn.Module):
     def _check(self, *tensors):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and self.training:
             raise NotImplementedError("these methods are the no_grad inference engine: call under torch.no_grad() / .eval(), or train "
-                                      "through ipercore_amd.networks.training.TrainableGenerator (trainers.LWGTrainer)")
+                                      "through ipercore_amd.networks.training.TrainableGenerator (trainers.LWGTrainer; all five LWB generators)")
         for t in tensors:
             if t is not None and not t.is_cuda:
                 raise RuntimeError("ipercore_amd generator runs on the MI355X only: got a CPU tensor (no fallback)")

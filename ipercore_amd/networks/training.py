@@ -1,4 +1,5 @@
-"""Training (autograd) path of the AttLWB-SPADE generator for the personalization step.
+"""Training (autograd) path of the five Liquid Warping Block generators (AttLWB-SPADE, AddLWB, AvgLWB, SoftGateAddLWB, SoftGateAvgLWB)
+for the personalization step.
 
 Reference: ``LWGTrainer.forward / optimize_G`` (tools/trainers/lwg_trainer.py:699-789) call
 ``AttentionLWBGenerator.forward(bg, src, tsf, Tst, only_tsf=False)`` (attlwb_spade_resunet.py:633-699) and
@@ -16,11 +17,15 @@ What runs where, this round:
 * what remains PyTorch-ROCm autograd: the tanh / sigmoid derivatives of the regressors' outputs, the mask compositing, the scalar
   losses (L1, LSGAN, BCE, TV) and the fan-in additions of tensors with two consumers - HBM-bound elementwise work (~90 small aten
   launches per step inside the captured graph).
+* the AddLWB / AvgLWB / SoftGateLWB generators (``gen.lwb_kind`` != "att") run the warp-and-fuse block instead of the attention block:
+  ``FuseFn`` = ``lwg_lwb_fuse_f32`` forward (the inference engine's launch) and ``lwg_lwb_fuse_bwd_f32`` backward (gathers recomputed, fp32
+  atomics for the bilinear scatter into the source features' gradient); SoftGate's gate is two ``ConvFn`` convolutions and ``torch.sigmoid``
+  (its derivative stays with PyTorch autograd, like the regressors').
 (The per-frame INFERENCE engine uses a different attention form - the query projection folded into the cached K, csrc/lwb_attn_x.hip;
 here fq is trainable, so q = fq(x) stays an explicit convolution.)
 There is no CPU fallback: ``ConvFn`` raises on CPU tensors.
 
-The module reuses the parameter tree of ``generator.AttentionLWBGenerator`` (same ``state_dict`` keys), so a
+The module reuses the parameter tree of ``generator.AttentionLWBGenerator`` and its subclasses (same ``state_dict`` keys), so a
 personalized checkpoint saved from here loads into the inference engine unchanged.
 """
 import contextlib
@@ -369,6 +374,27 @@ class AttnKVFn(torch.autograd.Function):
         return dq, dkv, dbk, dbv, None
 
 
+class FuseFn(torch.autograd.Function):
+    """Warp-and-fuse LWB of the AddLWB / AvgLWB / SoftGateLWB generators with its HIP backward:
+    out = (tsf_x + gate * scale_w * sum_s warp_s(src_x)) * scale_o  (gate None: 1).
+    tsf_x / gate (B,h,w,C); src_x (B*ns,h,w,C) (src_batched) or (ns,h,w,C); T (B,ns,S,S,2) constant, at image size."""
+
+    @staticmethod
+    def forward(ctx, tsf_x, src_x, gate, T, scale_w=1.0, scale_o=1.0, src_batched=True):
+        tsf_x, src_x, T = tsf_x.contiguous(), src_x.contiguous(), T.contiguous()
+        gate = None if gate is None else gate.contiguous()
+        out = ops.lwb_fuse(tsf_x, src_x, T, torch.empty_like(tsf_x), gate=gate, scale_w=scale_w, scale_o=scale_o, src_batched=src_batched)
+        ctx.scale_w, ctx.scale_o, ctx.src_batched = scale_w, scale_o, src_batched
+        ctx.save_for_backward(src_x, gate, T)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        src_x, gate, T = ctx.saved_tensors
+        d_tsf, d_src, d_gate = ops.lwb_fuse_bwd(src_x, gate, T, dout, src_batched=ctx.src_batched, scale_w=ctx.scale_w, scale_o=ctx.scale_o)
+        return d_tsf, d_src, d_gate, None, None, None, None
+
+
 class MaxPool2Fn(torch.autograd.Function):
     """nn.MaxPool2d(2, 2) on NHWC (csrc/train_ops.hip)."""
 
@@ -394,7 +420,9 @@ def lwb_transform(x, T):
 
 
 class TrainableGenerator(object):
-    """Functional training forward over the parameters of an ``AttentionLWBGenerator`` (reference :633-699)."""
+    """Functional training forward over the parameters of an ``AttentionLWBGenerator`` (reference :633-699) or of one of its
+    AddLWB / AvgLWB / SoftGateAddLWB / SoftGateAvgLWB subclasses (lwb_resunet.py / lwb_softgate_resunet.py: the same three streams with
+    another Liquid Warping Block; ``gen.lwb_kind`` picks the block per site)."""
 
     def __init__(self, gen):
         self.gen = gen
@@ -441,6 +469,24 @@ class TrainableGenerator(object):
         gamma = self.cv(pfx + ".spade.mlp_gamma", actv)
         beta = self.cv(pfx + ".spade.mlp_beta", actv)
         return NormAct.apply(tsf_x, gamma, beta, _NONE)
+
+    # -- AddLWB / AvgLWB (lwb_resunet.py:77-152), SoftGateLWB (lwb_softgate_resunet.py:77-123): the constants of generator._attlwb
+    def fuselwb(self, pfx, tsf_x, src_x, Tst):
+        kind, ns = self.gen.lwb_kind, Tst.shape[1]
+        if kind == "add":
+            return FuseFn.apply(tsf_x, src_x, None, Tst, 1.0, 1.0)
+        if kind == "avg":
+            return FuseFn.apply(tsf_x, src_x, None, Tst, 1.0, 1.0 / (ns + 1))
+        # tsf_x feeds the gate AND the fusion (two consumers: no mask flags on its producer); gate_conv.0's ReLU output feeds only gate_conv.2
+        g = self.cv(pfx + ".gate_conv.0", tsf_x, act=_RELU, premasked=True)
+        gate = torch.sigmoid(self.cv(pfx + ".gate_conv.2", g, mask_dx=True))
+        return FuseFn.apply(tsf_x, src_x, gate, Tst, 1.0 if kind == "sg_add" else 1.0 / ns, 1.0)
+
+    def lwb(self, pfx, tsf_x, src_x, Tst):
+        """The Liquid Warping Block of one site."""
+        if self.gen.lwb_kind == "att":
+            return self.attlwb(pfx, tsf_x, src_x, Tst)
+        return self.fuselwb(pfx, tsf_x, src_x, Tst)
 
     def res_block(self, pfx, x):
         return x + self.cv(pfx + ".main.2", self.cv(pfx + ".main.0", x, act=_RELU, premasked=True), mask_dx=True)
@@ -500,11 +546,11 @@ class TrainableGenerator(object):
         x, enc = tsf8, []
         for i in range(self.n_down):
             x = self.cv(f"tsf_net_enc.layers.{i}.0", x, stride=2, act=_RELU, cin_pad=8 if i == 0 else None, need_dx=i != 0)
-            x = self.attlwb(f"enc_attlwbs.{i}", x, enc_src[i], Tst)
+            x = self.lwb(f"enc_attlwbs.{i}", x, enc_src[i], Tst)
             enc.append(x)
         for i in range(self.n_res):
             x = self.res_block(f"res_blocks.{i}", x)
-            x = self.attlwb(f"res_attlwbs.{i}", x, res_src[i], Tst)
+            x = self.lwb(f"res_attlwbs.{i}", x, res_src[i], Tst)
         for i in range(self.n_down):
             x = self.cv(f"tsf_net_dec.upconvs.{i}.0", x, kind="convT", act=_RELU, mask_dx=i > 0)      # input: the skipper's ReLU output
             if i != self.n_down - 1:

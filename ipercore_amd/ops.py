@@ -739,6 +739,22 @@ def lwb_fuse(tsf_x, src_x, T, out, gate=None, scale_w=1.0, scale_o=1.0, src_batc
     return out
 
 
+def lwb_fuse_bwd(src_x, gate, T, dout, src_batched=False, scale_w=1.0, scale_o=1.0):
+    """Gradients of ``lwb_fuse`` w.r.t. tsf_x, src_x and gate (the flows are constants) -> (d_tsf, d_src, d_gate | None).
+    d_src is summed with fp32 atomics (bilinear scatter): its last bits depend on arrival order."""
+    B, h, w, C = dout.shape
+    ns, S = T.shape[1], T.shape[2]
+    assert T.shape[0] == B and src_x.shape[0] == (B * ns if src_batched else ns) and tuple(src_x.shape[1:]) == (h, w, C)
+    assert gate is None or gate.shape == dout.shape
+    dout = dout.contiguous()
+    d_tsf = torch.empty_like(dout)
+    d_src = torch.zeros_like(src_x)
+    d_gate = None if gate is None else torch.empty_like(dout)
+    _lib.check(_lib.lib().lwg_lwb_fuse_bwd_f32(_ptr(src_x), _ptr(gate), _ptr(T), _ptr(dout), _ptr(d_tsf), _ptr(d_src), _ptr(d_gate), B, ns, h, w, C,
+                                               S, 1 if src_batched else 0, float(scale_w), float(scale_o), _stream()), "lwg_lwb_fuse_bwd_f32")
+    return d_tsf, d_src, d_gate
+
+
 def lwb_attention_bwd(q, Ks, Vs, bk, bv, T, dout, src_batched=False):
     """Gradients of ``lwb_attention`` w.r.t. q, Ks, Vs (the flows are constants).  dbv = colsum(dout), dbk = 0."""
     B, h, w, C = q.shape

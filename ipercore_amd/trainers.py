@@ -758,7 +758,9 @@ class FlowCompositionForTrainer(FlowComposition):
 
 
 class LWGTrainer(object):
-    """lwg_trainer.py:609-832 for bs = 1 sample per process, share_bg = True, temporal = False, use_gan = True."""
+    """lwg_trainer.py:609-832 for bs = 1 sample per process, share_bg = True, temporal = False, use_gan = True.
+    G: any of the five Liquid Warping Block generators (AttLWB-SPADE, AddLWB, AvgLWB, SoftGateAddLWB, SoftGateAvgLWB) - the reference's
+    trainer is generator-agnostic; ``TrainableGenerator`` picks the block from ``G.lwb_kind``."""
 
     def __init__(self, G, D=None, opts=None, group=None, flow_comp=None):
         self.G, self.D, self.group, self.flow_comp = G, D, group, flow_comp
