@@ -385,6 +385,13 @@ int lwg_lwb_attention_kv_bwd_f32(const float* q, const float* kv, const float* b
  * Add: (1, 1); Avg: scale_o = 1/(ns+1); SoftGateAdd: gate, (1, 1); SoftGateAvg: gate, scale_w = 1/ns.  Layouts as above. */
 int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const float* gate, const float* T, float* out, int B, int ns,
                      int h, int w, int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream);
+/* The same block of the bf16 engines ("bf16" / "bf16_winograd": bf16 activation storage): tsf_x, src_x, gate and out are bf16 NHWC with the
+ * shapes above, T stays fp32 (B,ns,S,S,2); src_batched, scale_w, scale_o and a NULL gate mean what they mean above.  One definition of the flow
+ * resize / grid_sample coordinates / tap clamping / zero padding with lwg_lwb_fuse_f32 and its backward (shared device helpers); the
+ * arithmetic is fp32 in lwg_lwb_fuse_f32's order on the exactly widened inputs, rounded ONCE (to nearest even) to bf16 at the store.
+ * C in {32,64,128,256}.  Returns 1 before any launch on: NULL tsf_x / src_x / T / out, a non-positive B / ns / h / w / S, an unsupported C. */
+int lwg_lwb_fuse_bf16(const void* tsf_x, const void* src_x, const void* gate, const float* T, void* out, int B, int ns, int h, int w,
+                      int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream);
 /* Backward of lwg_lwb_fuse_f32 (the training step of the AddLWB / AvgLWB / SoftGateLWB generators).  dout (B,h,w,C) upstream gradient:
  *   d_tsf  = scale_o * dout                                               written, (B,h,w,C)
  *   d_gate = scale_o * scale_w * dout * sum_s warp_s(src_x)               written, (B,h,w,C); only when gate != NULL (gathers recomputed)

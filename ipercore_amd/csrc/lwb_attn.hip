@@ -539,6 +539,112 @@ extern "C" int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const fl
     return (int)hipGetLastError();
 }
 
+// The same block on bf16 tsf_x / src_x / gate / out (the "bf16" / "bf16_winograd" engines: bf16 activation storage end to end); the flows stay
+// fp32.  One pixel per LPP = C/8 lanes, lane cl owns channels 8 cl .. 8 cl + 7: every load, gather and store is a 16-byte access and a tap of
+// a pixel is one contiguous 2C-byte run.  Flow resize, grid_sample coordinates, tap clamping and zero padding are the helpers above, and the
+// arithmetic is lwg_lwb_fuse_kernel's, in fp32 and in its order: bf16 widened by shift (exact), four taps into wv, acc += wv source after
+// source, (t + g * (acc * scale_w)) * scale_o, then ONE round-to-nearest-even to bf16 at the store (v_cvt_pk_bf16_f32).  No LDS, no
+// cross-lane traffic: a lane past the last pixel simply leaves.
+typedef unsigned int lwg_fuse_uintx4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned lwg_pack_bf16x2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 v;
+    v[0] = (__bf16)lo;
+    v[1] = (__bf16)hi;
+    return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ void lwg_fuse_widen8(const lwg_fuse_uintx4 v, float (&f)[8]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f[2 * k] = __builtin_bit_cast(float, v[k] << 16);
+        f[2 * k + 1] = __builtin_bit_cast(float, v[k] & 0xffff0000u);
+    }
+}
+
+template <int LPP>
+__global__ __launch_bounds__(256) void lwg_lwb_fuse_bf16_kernel(const __bf16* __restrict__ tsf, const __bf16* __restrict__ src,
+                                                               const __bf16* __restrict__ gate, const float* __restrict__ T,
+                                                               __bf16* __restrict__ out, int B, int ns, int h, int w, int S, int src_batched,
+                                                               float scale_w, float scale_o) {
+    constexpr int C = 8 * LPP;
+    constexpr int PPW = 64 / LPP;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int cl = lane % LPP;
+    const long total = (long)B * h * w;
+    const long gp = ((long)blockIdx.x * 4 + wid) * PPW + lane / LPP;
+    if (gp >= total) return;
+    const int hw = h * w;
+    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
+    const int y = rem / w, x = rem - y * w;
+    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
+
+    // the pixel's own rows are requested before the flow -> taps -> gather chain, not after it: they ride under it (seven pixels in eight of a
+    // rendered frame are background - every tap outside - and would otherwise wait for the flow and then again for tsf_x)
+    const lwg_fuse_uintx4 tq = *reinterpret_cast<const lwg_fuse_uintx4*>(tsf + gp * C + 8 * cl);
+    lwg_fuse_uintx4 gq = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};        // bf16 1.0 pairs
+    if (gate) gq = *reinterpret_cast<const lwg_fuse_uintx4*>(gate + gp * C + 8 * cl);
+
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+    for (int s = 0; s < ns; ++s) {
+        const LwgFuseTaps tp = lwg_fuse_taps(reinterpret_cast<const float2*>(T) + ((size_t)b * ns + s) * S * S, rz, y, x, h, w, S);
+        const size_t sidx = src_batched ? (size_t)b * ns + s : (size_t)s;
+        const __bf16* Sb = src + sidx * hw * C + 8 * cl;
+        float wv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wv[k] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            int ty, tx;
+            float wt;
+            if (lwg_fuse_tap(tp, t, h, w, ty, tx, wt)) {
+                float v8[8];
+                lwg_fuse_widen8(*reinterpret_cast<const lwg_fuse_uintx4*>(Sb + ((size_t)ty * w + tx) * C), v8);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) wv[k] += v8[k] * wt;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] += wv[k];       // the reference sums the warped sources one after the other
+    }
+    float t8[8], g8[8];
+    lwg_fuse_widen8(tq, t8);
+    lwg_fuse_widen8(gq, g8);
+    float r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = (t8[k] + g8[k] * (acc[k] * scale_w)) * scale_o;
+    lwg_fuse_uintx4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = lwg_pack_bf16x2(r[2 * k], r[2 * k + 1]);
+    *reinterpret_cast<lwg_fuse_uintx4*>(out + gp * C + 8 * cl) = o;
+}
+
+// tsf_x / gate / out (B,h,w,C) bf16; src_x (ns,h,w,C) or (B*ns,h,w,C) bf16; T (B,ns,S,S,2) fp32; gate may be NULL; C in {32,64,128,256}.
+extern "C" int lwg_lwb_fuse_bf16(const void* tsf_x, const void* src_x, const void* gate, const float* T, void* out, int B, int ns, int h,
+                                 int w, int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (!tsf_x || !src_x || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0) return (int)hipErrorInvalidValue;
+    const long total = (long)B * h * w;
+#define LWG_FUSE16_LAUNCH(LPP)                                                                                        \
+    {                                                                                                                 \
+        const long per_block = 4 * (64 / LPP);                                                                        \
+        hipLaunchKernelGGL(lwg_lwb_fuse_bf16_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, stream, \
+                           static_cast<const __bf16*>(tsf_x), static_cast<const __bf16*>(src_x), static_cast<const __bf16*>(gate), T,     \
+                           static_cast<__bf16*>(out), B, ns, h, w, S, src_batched, scale_w, scale_o);                                     \
+    }
+    switch (C) {
+        case 32: LWG_FUSE16_LAUNCH(4) break;
+        case 64: LWG_FUSE16_LAUNCH(8) break;
+        case 128: LWG_FUSE16_LAUNCH(16) break;
+        case 256: LWG_FUSE16_LAUNCH(32) break;
+        default: return (int)hipErrorInvalidValue;
+    }
+#undef LWG_FUSE16_LAUNCH
+    return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Backward of the fusion block (personalization of the AddLWB / AvgLWB / SoftGateLWB generators).  With upstream gradient dout:
 //   d_tsf  = scale_o * dout                                                   (written)

@@ -233,6 +233,7 @@ class AttentionLWBGenerator(nn.Module):
         # "fp32": every layer on the direct kernel (the rounds 1-4 default; frames differ from "winograd" by ~3e-6);
         # "bf16": BASELINE configs[3] - every activation tensor of the engine is stored as bf16, the convs run on the bf16 MFMA kernel
         #   (fp32 accumulation), InstanceNorm statistics / attention / head read bf16; the first conv of a stream takes the fp32 input;
+        #   all five LWB generators take it - the Add / Avg / SoftGate blocks fuse on lwg_lwb_fuse_bf16 (csrc/lwb_attn.hip), SoftGate's gate is bf16;
         # "bf16_winograd": "bf16" in everything (storage, first layer, 1x1 / strided / transposed launches, fused head) except that the eligible
         #   3x3 / stride 1 layers run the fused bf16 F(2x2,3x3) Winograd kernel (csrc/conv_winograd_bf16.hip): opt-in, not "bf16"'s bits;
         # "split": fp32 tensors, every product formed from six bf16 MFMAs (exact three-way operand split).
@@ -297,6 +298,8 @@ class AttentionLWBGenerator(nn.Module):
     def _attlwb(self, st, tsf_x, kv, Tst, batched, scratch):
         B, h, w, C = tsf_x.shape
         if self.lwb_kind != "att":
+            # Add / Avg / SoftGate blocks in tsf_x's storage type: ops.lwb_fuse dispatches on it (lwg_lwb_fuse_f32 | lwg_lwb_fuse_bf16), the
+            # gate convolutions of a bf16 tsf_x run on the bf16 conv kernels and leave a bf16 gate
             ns = Tst.shape[1]
             Tst = scratch.flow(Tst, h, w)
             if self.lwb_kind == "add":
@@ -340,8 +343,6 @@ class AttentionLWBGenerator(nn.Module):
         n_down = len(pk.tsf_enc)
         x = tsf8
         adt = self._act_dtype()
-        if adt != torch.float32 and self.lwb_kind != "att":
-            raise NotImplementedError("bf16 activation storage is built for the attention LWB (AttLWB-SPADE) generators")
         if feats.kv[0][0].dtype != adt:
             raise RuntimeError(f"source features are {feats.kv[0][0].dtype} but the generator runs in {self.conv_precision} mode: "
                                "rebuild them (Imitator.set_source / forward_src) after changing conv_precision")

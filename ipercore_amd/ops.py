@@ -730,10 +730,18 @@ def instnorm_finalize(ws, B, C, nrec, mean, rstd, eps=1e-5):
 
 
 def lwb_fuse(tsf_x, src_x, T, out, gate=None, scale_w=1.0, scale_o=1.0, src_batched=False):
-    """out = (tsf_x + gate * scale_w * sum_s warp_s(src_x)) * scale_o - AddLWB / AvgLWB / SoftGateLWB fusion."""
+    """out = (tsf_x + gate * scale_w * sum_s warp_s(src_x)) * scale_o - AddLWB / AvgLWB / SoftGateLWB fusion.
+    tsf_x (B,h,w,C) fp32 | bf16; src_x, gate, out in tsf_x's dtype; T (B,ns,S,S,2) fp32 flows."""
     B, h, w, C = tsf_x.shape
     ns, S = T.shape[1], T.shape[2]
     assert T.shape[0] == B and src_x.shape[0] == (B * ns if src_batched else ns) and tuple(src_x.shape[1:]) == (h, w, C)
+    assert src_x.dtype == tsf_x.dtype and out.dtype == tsf_x.dtype and (gate is None or gate.dtype == tsf_x.dtype)
+    assert T.dtype == torch.float32
+    if tsf_x.dtype == torch.bfloat16:
+        bf = torch.bfloat16
+        _lib.check(_lib.lib().lwg_lwb_fuse_bf16(_ptr(tsf_x, bf), _ptr(src_x, bf), _ptr(gate, bf), _ptr(T), _ptr(out, bf), B, ns, h, w, C, S,
+                                                1 if src_batched else 0, float(scale_w), float(scale_o), _stream()), "lwg_lwb_fuse_bf16")
+        return out
     _lib.check(_lib.lib().lwg_lwb_fuse_f32(_ptr(tsf_x), _ptr(src_x), _ptr(gate), _ptr(T), _ptr(out), B, ns, h, w, C, S,
                                            1 if src_batched else 0, float(scale_w), float(scale_o), _stream()), "lwg_lwb_fuse_f32")
     return out
