@@ -147,6 +147,28 @@ int lwg_winograd_panels_f32(const LwgWinoDesc* descs_dev, int ndesc, int total_b
  * NOR on the form the entry point chooses for the launch (an 8-wave block of 64 output channels in persistent workgroups - block order by column block
  * per XCD, see the kernel - or, for launches that would leave half the chip without a workgroup, a 4-wave block of 32: bitwise the same values). */
 int lwg_conv2d_winograd4_f32(const LwgConvArgs* args, lwg_stream_t stream);
+/* The same launch driven by two tile lists (csrc/conv_winograd4.hip, csrc/spade_skip.hip): the SPADE convolutions of a Liquid Warping
+ * site read the attention output, which is ONE vector at every pixel without an in-image tap of any source.  A tile = one 32 x 16 block position of one
+ * frame (numbered b * bx * by + ty * bx + tx, bx = ceil(W / 32), by = ceil(H / 16)).  heavy / light: the tile ids of either class in ascending order,
+ * counts[0] / counts[1] their numbers - all in DEVICE memory, written by lwg_spade_skip_lists_f32 on the same stream, read by the kernel only (no host
+ * synchronisation).  Heavy tiles run the K loop and epilogue of lwg_conv2d_winograd4_f32 unchanged; light tiles are filled from cal, the result of the
+ * SAME convolution on the all-background frame (one image): LWG_EPI_NONE - cal (1, H, W, YC) in the output's layout, copied; LWG_EPI_SPADE - cal
+ * (1, H, W, N) = the stacked gamma | beta columns of that frame as an LWG_EPI_NONE / LWG_ACTIVATION_NONE launch of the same panel and bias leaves
+ * them, modulated with the frame's own xn / mean / rstd and activated.  Bitwise the result of lwg_conv2d_winograd4_f32 wherever every light tile's
+ * input window equals the all-background frame's.  LWG_EPI_NONE and LWG_EPI_SPADE only, one input (C1 = 0), H * W * N * 4 + 256 < 3 GiB; launches that
+ * lwg_conv2d_winograd4_f32 runs in its 4-wave form (lwg_conv2d_winograd4_list_applies = 0) run exactly that, the lists unread. */
+typedef struct LwgConvLists {
+    const int* heavy;
+    const int* light;
+    const int* counts;
+    const float* cal;
+} LwgConvLists;
+int lwg_conv2d_winograd4_list_f32(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
+int lwg_conv2d_winograd4_list_applies(const LwgConvArgs* args);
+/* The lists of a frame batch from its resized flows T (B, ns, h, w, 2) (lwg_flow_resize_f32; -2 = background): tile (b, ty, tx) is heavy when any pixel
+ * of its block's window - the block grown by d pixels, clipped to the image - has an in-image tap of any source by lwg_lwb_attention_x's own predicate
+ * (csrc/lwg_lwb_taps.h).  marks: B * tiles ints of scratch; heavy, light: B * tiles ints each; counts: 2 ints.  Two launches, a deterministic scan. */
+int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, lwg_stream_t stream);
 /* That panel from the fp32 GEMM panel of the same convolution (arguments as lwg_winograd_panel_f32): U = G w G^T in fp64, rounded once. */
 int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream);
 /* The same convolution for the 3x3 (9 taps) and 2x2 (4 taps, transposed-conv parity) stride-1 launches, as the

@@ -45,6 +45,11 @@ class LwgWinoDesc(ctypes.Structure):
     _fields_ = [("wpanel", ctypes.c_void_p), ("upk", ctypes.c_void_p), ("Cin", c_i), ("N", c_i), ("first_block", c_i), ("tap9", c_i * 9)]
 
 
+class LwgConvLists(ctypes.Structure):
+    """Mirror of ``struct LwgConvLists`` (include/lwg_hip.h): the tile lists and calibration frame of lwg_conv2d_winograd4_list_f32."""
+    _fields_ = [("heavy", c_f), ("light", c_f), ("counts", c_f), ("cal", c_f)]
+
+
 class LwgPackDesc(ctypes.Structure):
     """Mirror of ``struct LwgPackDesc`` (include/lwg_hip.h): one panel of lwg_pack_panels_f32."""
     _fields_ = [("w", c_f), ("out", c_f)] + [(n, c_i) for n in ("D1", "KHW", "transposed", "ntaps", "cin", "cin_pad", "nout", "n_pad", "Kp",
@@ -66,6 +71,9 @@ _SIGS = {
     "lwg_winograd_panel_f32": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_f]),
     "lwg_winograd_panels_f32": (c_i, [c_f, c_i, c_i, c_f]),
     "lwg_conv2d_winograd4_f32": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
+    "lwg_conv2d_winograd4_list_f32": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
+    "lwg_conv2d_winograd4_list_applies": (c_i, [ctypes.POINTER(LwgConvArgs)]),
+    "lwg_spade_skip_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
     "lwg_winograd4_panel_f32": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_f]),
     "lwg_conv2d_nhwc_bf16_hr": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
     "lwg_conv2d_winograd_bf16": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),

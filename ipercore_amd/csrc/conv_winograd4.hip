@@ -103,8 +103,26 @@ __device__ __forceinline__ void w4_bt6(const float (&r)[6], float (&v)[6]) {
 // transform and stages five halo pieces.  Every output element is accumulated over the stages and k-pairs in the same order and finished by the same
 // expressions in both forms (the transform, the folds and the reader are explicit fma / add sequences): bitwise the same result - a frame does not depend on
 // its batch (check_winograd4: frame n of a 40-frame launch = the frame alone, across the forms).
-template <int EPI, bool TWO, bool SM = false>
-__global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_kernel(const LwgConvArgs a) {
+// The SPADE modulation and the activation of sixteen outputs: what the epilogue and the light-tile loop of the list-driven form both apply
+__device__ __forceinline__ float w4_spade_mod(float x, float mu, float rs, float gam, float bet) { return (x - mu) * rs * (1.f + gam) + bet; }
+// (the activation resolved once per sixteen values - lwg_common.h; around the whole output pass the four copies of the pass cost registers:
+// 40-90 spilled, their reloads between the stores each waiting for every store before them)
+__device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[4]) {
+    lwg_act_dispatch(act, [&](auto ACTC) {
+        constexpr int EA = decltype(ACTC)::value;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) o[i][c] = lwg_act_c<EA>(o[i][c], act);
+    });
+}
+
+// LIST (lwg_conv2d_winograd4_list_f32; 8-wave form, LWG_EPI_NONE / LWG_EPI_SPADE, one input): the workgroup's blocks come from two tile lists in device
+// memory (lwg_conv_wino.h: cw_list_entry) - the heavy entries through the K loop and epilogue below, untouched, then the light ones from the calibration
+// frame in a streaming loop without LDS.  Heavy first: a static walk that mixed them would leave most workgroups waiting for the few
+// that drew the heavy blocks of a clustered body.
+template <int EPI, bool TWO, bool SM, bool LIST>
+__device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists& sk) {
     constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;          // (its 32 accumulator rows: gamma | beta of the SAME 16 channels, cw4_n0_spade_small)
     constexpr int NVP = SM && !SMS ? 2 : 1;                  // patches per reader thread and pass
     constexpr int NTH = SM ? 256 : W4_THREADS;               // threads per workgroup
@@ -125,6 +143,14 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
     const CwGrid g = cw_grid(a.B, H, W, N, 4 * W4_PBX, 4 * W4_PBY, NBV);
     const CwOrder o = cw_order(cw4_order_kind(LWG_W4_XCD, LWG_W4_CHUNK, SM, gridDim.x, N / NBV, Cin, N, g.tiles, g.total), gridDim.x, blockIdx.x, N / NBV, g);
     int blk = blockIdx.x;
+    // LIST: the heavy entries' number (the ids below it run the K loop); a workgroup may own none
+    // (counts and tile ids are clamped to the launch's grid: lists that do not belong to this launch must not become addresses)
+    const int nht = LIST ? min(max(__builtin_amdgcn_readfirstlane(sk.counts[0]), 0), g.tiles) : 0;
+    const int nhe = nht * (N / NBV);
+    // a launch whose tiles are ALL heavy (a frame batch without background) walks its blocks in the plain entry point's order - decided here, on the
+    // device: the list order costs such a launch 0.3-3 % (profiles/spade_skip_ab_tool_list_order.txt)
+    const bool lst = LIST ? nht < g.tiles : false;
+    const bool run = lst ? blk < nhe : true;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(144u * (unsigned)Cin * (unsigned)N), 0x00020000);
     const int q = wid & 3, ct = SM ? 0 : wid >> 2;           // this wave's product set and 32-channel tile
@@ -134,7 +160,17 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
     unsigned uvoff, uvoffc;                                  // this lane's column of the fragment panel: the 16-byte parts, the ninth product
     auto setup = [&](int id) {
         int cb, t;
-        cw_block(o, id, cb, t);
+        if constexpr (LIST) {
+            if (lst) {
+                int slot;
+                cw_list_entry(id, N / NBV, slot, cb);
+                t = min(max(__builtin_amdgcn_readfirstlane(sk.heavy[slot]), 0), g.tiles - 1);
+            } else {
+                cw_block(o, id, cb, t);
+            }
+        } else {
+            cw_block(o, id, cb, t);
+        }
         bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV));
         int tids = tid;                                      // (through an empty asm: the halo geometry is recomputed per block - hoisted out of the block
         asm volatile("" : "+v"(tids));                       //  loop it would sit in registers through the K loop)
@@ -143,7 +179,7 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
         uvoff = (unsigned)(((lane >> 5) * 9 * N + 4 * col) * 4);
         uvoffc = (unsigned)(((lane >> 5) * 9 * N + 8 * N + col) * 4);
     };
-    setup(blk);
+    if (run) setup(blk);
     int wst[NQ];                                             // the halo elements' LDS slot
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
@@ -417,12 +453,12 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #pragma unroll
         for (int k = 0; k < NQ; ++k) rreg[k] = rld1(nst > 2 ? 2 : 1, k);
     };
-    issue_loads();
+    if (run) issue_loads();
 #ifdef LWG_W4_TS
     int lab_bi = 0;
 #endif
     W4TSA(11);
-    for (;;) {
+    if (run) for (;;) {
     W4TS(0);
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
@@ -561,7 +597,8 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
             // (unconditional: the last block re-requests its own first stages, nobody waits for them; see conv_winograd.hip)
             W4TS(8);
             nblk = blk + (int)gridDim.x;
-            more = cw_has_block(o, nblk);
+            if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
+            else more = cw_has_block(o, nblk);
             setup(more ? nblk : blk);
             W4TS(9);
             issue_loads();
@@ -607,7 +644,7 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) o[i][c] = (ext[0][i][c] - mu[c]) * rs[c] * (1.f + gam[i][c]) + o[i][c];
+                    for (int c = 0; c < 4; ++c) o[i][c] = w4_spade_mod(ext[0][i][c], mu[c], rs[c], gam[i][c], o[i][c]);
             } else if (EPI == LWG_EPI_RESIDUAL) {
                 if (a.act == LWG_ACT_RELU_MASK) {            // data gradient behind a ReLU: res = the forward input, the mask source
 #pragma unroll
@@ -619,15 +656,7 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
                     for (int i = 0; i < 4; ++i) o[i] += ext[h][i];
                 }
             }
-            // (the activation resolved once per sixteen values - lwg_common.h; around the whole output pass the four copies of the pass cost registers:
-            // 40-90 spilled, their reloads between the stores each waiting for every store before them)
-            lwg_act_dispatch(a.act, [&](auto ACTC) {
-                constexpr int EA = decltype(ACTC)::value;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) o[i][c] = lwg_act_c<EA>(o[i][c], a.act);
-            });
+            w4_act16(a.act, o);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)cw4_out_group(vo[NVP == 2 ? h : 0][i], h, EPI != LWG_EPI_SPADE && !SM), 0, W4_NT_ST);
@@ -646,6 +675,81 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 #ifdef LWG_W4_TS
     if (tid == 0) reinterpret_cast<unsigned long long*>(const_cast<float*>(a.res))[(size_t)blockIdx.x * 16 + 13] = (unsigned long long)lab_bi;
 #endif
+    if constexpr (LIST) {
+        // the light entries of this workgroup: its ids behind the heavy ones.  A block is 512 pixels x NQD 16-byte channel quads (LWG_EPI_NONE: the 64
+        // columns; LWG_EPI_SPADE: the 32 channels whose gamma | beta the block's 64 columns are); a thread keeps one quad and walks the pixels in passes of
+        // four loads / stores; consecutive lanes = the quads of a pixel (a pixel's 256 / 128 bytes contiguous).  Pixels right of / below the image: the
+        // out-of-range offset (dropped stores, zero loads), as in the epilogue.
+        typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
+        constexpr int NQD = EPI == LWG_EPI_SPADE ? 8 : 16;
+        const int ncb = N / NBV;
+        const int nend = nhe + min(max(__builtin_amdgcn_readfirstlane(sk.counts[1]), 0), g.tiles - nht) * ncb;
+        const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
+        // the calibration frame (one image): the output's layout | SPADE: the N stacked gamma | beta columns
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sk.cal), 0, (int)((unsigned)(H * W) * (unsigned)(EPI == LWG_EPI_SPADE ? N : a.YC) * 4u), 0x00020000);
+#pragma unroll 1
+        for (int id = cw_list_first_light((int)blockIdx.x, (int)gridDim.x, nhe); id < nend; id += (int)gridDim.x) {
+            int slot, cb;
+            cw_list_entry(id - nhe, ncb, slot, cb);
+            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), g.tiles - 1);
+            const int eb = __builtin_amdgcn_readfirstlane(cw_image(g, t)), en0 = cw_n0(cb, NBV);
+            int ex0, ey0;
+            cw_corner(g, t - eb * g.bx * g.by, 4 * W4_PBX, 4 * W4_PBY, ex0, ey0);
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
+            int px, py, q4;
+            cw4_light_elem(tid, 0, W4_THREADS, NQD, px, py, q4);
+            if constexpr (EPI == LWG_EPI_SPADE) {
+                const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.xn) + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
+                const int cbase = en0 >> 1;                  // the block's first output channel (its columns: gamma | beta of 32 channels)
+                const floatx4 mu = *reinterpret_cast<const floatx4*>(a.mean + (size_t)eb * a.YC + cbase + 4 * q4);
+                const floatx4 rs = *reinterpret_cast<const floatx4*>(a.rstd + (size_t)eb * a.YC + cbase + 4 * q4);
+#pragma unroll 1
+                for (int it = 0; it < 512 * NQD / W4_THREADS; it += 4) {
+                    unsigned vo[4];
+                    floatx4 o[4], gam[4], xv[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
+                        vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, cbase + 4 * q4);
+                        const unsigned vc = cw4_out_voff(ex0 + px, ey0 + py, H, W, N, en0 + 4 * q4);
+                        gam[i] = cw_buf_load(rc, cw4_out_group(vc, 0, true), 0u);
+                        o[i] = cw_buf_load(rc, cw4_out_group(vc, 1, true), 0u);       // beta: 32 columns on
+                        xv[i] = cw_buf_load<W4_NT_RES>(re, vo[i], 0u);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) o[i][c] = w4_spade_mod(xv[i][c], mu[c], rs[c], gam[i][c], o[i][c]);
+                    w4_act16(a.act, o);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
+                }
+            } else {
+#pragma unroll 1
+                for (int it = 0; it < 512 * NQD / W4_THREADS; it += 4) {
+                    unsigned vo[4];
+                    floatx4 o[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
+                        vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, a.ycoff + en0 + 4 * q4);
+                        o[i] = cw_buf_load(rc, vo[i], 0u);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
+                }
+            }
+        }
+    }
+}
+
+template <int EPI, bool TWO, bool SM = false>
+__global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_kernel(const LwgConvArgs a) {
+    w4_body<EPI, TWO, SM, false>(a, LwgConvLists{});
+}
+template <int EPI>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_list_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    w4_body<EPI, false, false, true>(a, sk);
 }
 
 // The fragment panel from the fp32 GEMM panel of the same convolution (lwg_conv2d_nhwc_f32's w: [9 Cin / 4][N][4], k = ((c / 32) 9 + tap) 32 + c % 32):
@@ -717,4 +821,25 @@ extern "C" int lwg_conv2d_winograd4_f32(const LwgConvArgs* pa, lwg_stream_t stre
     if (a.epi == LWG_EPI_SPADE) return sm ? lwg_wino4_go<LWG_EPI_SPADE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_SPADE, false>(a, grid, lds, stream);
     if (a.epi == LWG_EPI_RESIDUAL) return sm ? lwg_wino4_go<LWG_EPI_RESIDUAL, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_RESIDUAL, false>(a, grid, lds, stream);
     return sm ? lwg_wino4_go<LWG_EPI_NONE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_NONE, false>(a, grid, lds, stream);
+}
+
+// The list-driven launch (include/lwg_hip.h): the same contract, LWG_EPI_NONE / LWG_EPI_SPADE and one input only; the grid is sized from the launch's
+// total as above (the lists' counts are read by the kernel, never by the host).  Launches of the 4-wave form run the plain entry point.
+static bool lwg_wino4_list_ok(const LwgConvArgs* pa) {
+    return pa && cw_contract_ok(*pa, 144ull, 256ll) && pa->C1 == 0 && (pa->epi == LWG_EPI_NONE || pa->epi == LWG_EPI_SPADE) &&
+           cw_contract_calib_ok(*pa) && cw_total_blocks(pa->B, pa->H, pa->W, pa->N, 4 * W4_PBX, 4 * W4_PBY, W4_NB) < (1ll << 30);
+}
+extern "C" int lwg_conv2d_winograd4_list_applies(const LwgConvArgs* pa) {
+    if (!lwg_wino4_list_ok(pa)) return 0;
+    return !(LWG_W4_SMALL && 2 * cw_total_blocks(pa->B, pa->H, pa->W, pa->N, 4 * W4_PBX, 4 * W4_PBY, W4_NB) <= lwg_device_cus());
+}
+extern "C" int lwg_conv2d_winograd4_list_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
+    if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
+    if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const LwgConvArgs& a = *pa;
+    const size_t lds = (size_t)(W4_BIAS_OFF + 64) * 4;
+    const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
+    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
+                                  : cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
 }

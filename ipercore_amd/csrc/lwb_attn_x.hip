@@ -19,6 +19,7 @@
 // lwg_in_stats_final (norm.hip) - and the separate statistics pass over x (9 launches, 9 full reads per frame) disappears.
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
+#include "lwg_lwb_taps.h"
 
 typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
 
@@ -177,16 +178,8 @@ __global__ __launch_bounds__(256 * PW, PW == 1 ? OCC : 1) void lwg_lwb_attnx_ker
             }
         }
     };
-    // grid_sample, align_corners=False: pixel = ((g + 1) * size - 1) / 2; the four bilinear weights and the top-left tap (clamped before the int
-    // conversion so wild flows cannot overflow; out-of-range taps read zeros)
-    auto taps_of = [&](const float2 t, float (&wt)[4], int& tx0, int& ty0) {
-        const float ix = ((t.x + 1.f) * (float)w - 1.f) * 0.5f, iy = ((t.y + 1.f) * (float)h - 1.f) * 0.5f;
-        const float fx0 = floorf(ix), fy0 = floorf(iy);
-        const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.f) - ix, wy0 = (fy0 + 1.f) - iy;
-        tx0 = (int)fminf(fmaxf(fx0, -2.f), (float)w + 1.f);
-        ty0 = (int)fminf(fmaxf(fy0, -2.f), (float)h + 1.f);
-        wt[0] = wy0 * wx0; wt[1] = wy0 * wx1; wt[2] = wy1 * wx0; wt[3] = wy1 * wx1;
-    };
+    // the bilinear weights and the top-left tap of a flow value (lwg_lwb_taps.h: shared with the SPADE skip classifier)
+    auto taps_of = [&](const float2 t, float (&wt)[4], int& tx0, int& ty0) { lwb_taps_of(t, w, h, wt, tx0, ty0); };
     // one source's logit / value folded into the running softmax of a pixel (online form, the sources in order)
     auto fold = [&](const float (&ka)[CPL], const float (&va)[CPL], float kap, const float (&xv)[CPL], float& mrun, float& lrun, float (&o)[CPL]) {
         float dot = 0.f;
@@ -238,7 +231,7 @@ __global__ __launch_bounds__(256 * PW, PW == 1 ? OCC : 1) void lwg_lwb_attnx_ker
                 float wt[4];
                 int tx0, ty0;
                 taps_of(t, wt, tx0, ty0);
-                mine |= live && tx0 >= -1 && tx0 < w && ty0 >= -1 && ty0 < h;
+                mine |= live && lwb_tap_in_image(tx0, ty0, w, h);
             }
         }
         if (__syncthreads_or(mine ? 1 : 0) == 0) {
@@ -340,7 +333,7 @@ __global__ __launch_bounds__(256 * PW, PW == 1 ? OCC : 1) void lwg_lwb_attnx_ker
             float wt[4];
             int tx0, ty0;
             taps_of(t, wt, tx0, ty0);
-            const bool any_tap = live && tx0 >= -1 && tx0 < w && ty0 >= -1 && ty0 < h;
+            const bool any_tap = live && lwb_tap_in_image(tx0, ty0, w, h);
             float ka[CPL], va[CPL], kap = 0.f;
 #pragma unroll
             for (int k = 0; k < CPL; ++k) ka[k] = va[k] = 0.f;

@@ -116,6 +116,24 @@ CW_FN unsigned cw4_out_voff(int ox, int oy, int H, int W, int YC, int chan) {
 }
 CW_FN unsigned cw4_out_group(unsigned vo, int h, bool grouped) { return vo + (grouped ? 128u * (unsigned)h : 0u); }
 
+// ---- list-driven launches of F(4x4) (lwg_conv2d_winograd4_list_f32, spade_skip.hip).  A tile (one 32 x 16 block position of one image,
+// cw_grid's numbering) is HEAVY when the window of its block - the block grown by d pixels, clipped to the image - holds a pixel with an in-image tap of
+// any source, else LIGHT.  The launch's entries: heavy entry e = (tile heavy[e / ncb], column block e % ncb) for e < nhe = heavy tiles x ncb, then light
+// entry e - nhe the same way through the light list; persistent workgroup wg of nwg walks the ids wg + k nwg of [0, nhe + nle) - its heavy ones through the
+// K loop first, then its light ones in the streaming loop (which starts at cw_list_first_light).
+struct CwWindow { int x0, y0, x1, y1; };     // [x0, x1) x [y0, y1)
+CW_FN CwWindow cw_block_window(int x0, int y0, int ex, int ey, int d, int H, int W) {
+    return CwWindow{x0 - d > 0 ? x0 - d : 0, y0 - d > 0 ? y0 - d : 0, x0 + ex + d < W ? x0 + ex + d : W, y0 + ey + d < H ? y0 + ey + d : H};
+}
+CW_FN void cw_list_entry(int e, int ncb, int& slot, int& cb) { slot = e / ncb, cb = e - slot * ncb; }
+CW_FN int cw_list_first_light(int wg, int nwg, int nhe) { return wg >= nhe ? wg : wg + (nhe - wg + nwg - 1) / nwg * nwg; }
+// a light block's elements: pass it of thread tid (nth threads) -> pixel (px, py) of the 32 x 16 block and 16-byte channel quad q4 of its nq quads (a
+// power of two: 16 - the block's 64 columns -, SPADE 8 - its 32 channels); nth % nq == 0: a thread keeps its quad through the passes
+CW_FN void cw4_light_elem(int tid, int it, int nth, int nq, int& px, int& py, int& q4) {
+    const int e = it * nth + tid, p = e / nq;
+    q4 = e - p * nq, px = p & 31, py = p >> 5;
+}
+
 // ---- the host contracts.  fp32 (lwg_conv2d_winograd_f32 / _f32_ws, lwg_conv2d_winograd4_f32): the launch description of the 3 x 3 / stride 1 /
 // pad 1 convolution as lwg_conv2d_nhwc_f32 takes it (nine taps, omul = 1, OH = H, OW = W, one or two inputs with C0 % 8 == 0, C1 % 8 == 0 and
 // (C0 + C1) % 16 == 0, N % 64 == 0, YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL (ycoff % 4 == 0) or LWG_EPI_SPADE (N = 2 YC, columns gamma | beta
@@ -141,6 +159,10 @@ CW_FN bool cw_contract_ok(const LwgConvArgs& a, unsigned long long pair_bytes, l
     if ((unsigned long long)a.H * a.W * cmax * 4ull >= (unsigned long long)CW_OOB || pair_bytes * (a.C0 + a.C1) * a.N >= 0xffffffffull) return false;
     if (out_slack >= 0 && (unsigned long long)a.H * a.W * a.YC * 4ull + (unsigned long long)out_slack >= (unsigned long long)CW_OOB) return false;
     return true;
+}
+// the list-driven F(4x4) launch besides: its calibration frame (one image of YC - SPADE: N - channels) is one buffer of the same kind
+CW_FN bool cw_contract_calib_ok(const LwgConvArgs& a) {
+    return (unsigned long long)a.H * a.W * (unsigned long long)(a.epi == LWG_EPI_SPADE ? a.N : a.YC) * 4ull + 256ull < (unsigned long long)CW_OOB;
 }
 // bf16 (lwg_conv2d_winograd_bf16; include/lwg_hip.h): bf16 in and out, the taps ascending in (dy, dx) (the order the panel was built in), Cin and N
 // multiples of 64 (a second input: C0 too), 8-channel slices, activation none / ReLU / tanh / sigmoid - no ReLU mask.  32-bit offsets: one IMAGE
@@ -242,6 +264,14 @@ static inline int cw_launch(dim3 grid, unsigned threads, size_t lds, hipStream_t
     static unsigned long long done = 0ull;
     if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done); e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a);
+    return (int)hipGetLastError();
+}
+// ... of a list-driven kernel (LwgConvArgs and the lists)
+template <void (*KERNEL)(const LwgConvArgs, const LwgConvLists)>
+static inline int cw_launch_lists(dim3 grid, unsigned threads, size_t lds, hipStream_t stream, const LwgConvArgs& a, const LwgConvLists& l) {
+    static unsigned long long done = 0ull;
+    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done); e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a, l);
     return (int)hipGetLastError();
 }
 // persistent workgroups: one per CU (LDS) at most, each walking block ids blockIdx.x + k gridDim.x (LWG_WINO_PERSIST = 0: one block per workgroup)

@@ -1,0 +1,76 @@
+// The tile lists of lwg_conv2d_winograd4_list_f32 (conv_winograd4.hip) from a frame batch's resized flows.
+// The renderer marks the pixels outside the body with flow -2: no tap of any source falls into the image there, and lwg_lwb_attention_x leaves the SAME
+// vector (bv) at every such pixel of every frame.  A 3x3 convolution block whose whole input window is such pixels computes what the same block of an
+// all-background frame computes - the list-driven convolution copies that instead.  Here: (1) per (frame, 32 x 16 block) one mark - does any pixel of the
+// block's window (the block grown by d pixels, clipped to the image) have an in-image tap of any source, by the attention kernel's own predicate
+// (lwg_lwb_taps.h); (2) one workgroup turns the marks into the heavy and the light tile ids in ascending order (a fixed-order scan, every list slot
+// written by one thread) and their counts - all in device memory, read by the convolution kernel only.
+#include <hip/hip_runtime.h>
+#include "lwg_common.h"
+#include "lwg_conv_wino.h"
+#include "lwg_lwb_taps.h"
+
+#define SK_EX 32             // the F(4x4, 3x3) kernel's block: 32 x 16 output pixels
+#define SK_EY 16
+
+// one workgroup per tile (cw_grid's numbering: b * bx * by + ty * bx + tx)
+__global__ __launch_bounds__(256) void lwg_spade_skip_mark_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks) {
+    const CwGrid g = cw_grid(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
+    const int t = blockIdx.x, b = cw_image(g, t);
+    int x0, y0;
+    cw_corner(g, t - b * g.bx * g.by, SK_EX, SK_EY, x0, y0);
+    const CwWindow win = cw_block_window(x0, y0, SK_EX, SK_EY, d, h, w);
+    const int ww = win.x1 - win.x0, n = ww * (win.y1 - win.y0);
+    bool mine = false;
+    for (int s = 0; s < ns; ++s) {
+        const float2* Ts = T + ((size_t)b * ns + s) * h * w;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int yy = i / ww, y = win.y0 + yy, x = win.x0 + (i - yy * ww);
+            float wt[4];
+            int tx0, ty0;
+            lwb_taps_of(Ts[(size_t)y * w + x], w, h, wt, tx0, ty0);
+            mine |= lwb_tap_in_image(tx0, ty0, w, h);
+        }
+    }
+    const int any = __syncthreads_or(mine ? 1 : 0);
+    if (threadIdx.x == 0) marks[t] = any ? 1 : 0;
+}
+
+// ONE workgroup: thread i owns the marks [i per, (i + 1) per); counts per thread, an inclusive scan over the 1024 threads in LDS, then every thread writes
+// its tiles behind the heavy / light tiles of the threads before it - both lists ascending
+__global__ __launch_bounds__(1024) void lwg_spade_skip_scan_kernel(const int* __restrict__ marks, int n, int* __restrict__ heavy, int* __restrict__ light,
+                                                                   int* __restrict__ counts) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x, per = (n + 1023) / 1024;
+    const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
+    int c = 0;
+    for (int i = i0; i < i1; ++i) c += marks[i] != 0;
+    part[tid] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int hv = part[tid] - c;                                   // heavy tiles before i0
+    for (int i = i0; i < i1; ++i) {
+        if (marks[i] != 0) heavy[hv++] = i;
+        else light[i - hv] = i;
+    }
+    if (tid == 1023) {
+        counts[0] = part[1023];
+        counts[1] = n - part[1023];
+    }
+}
+
+extern "C" int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
+                                        lwg_stream_t stream_) {
+    if (!T || !marks || !heavy || !light || !counts || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64) return (int)hipErrorInvalidValue;
+    const long long tiles = cw_total_blocks(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
+    if (tiles >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(lwg_spade_skip_mark_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks);
+    hipLaunchKernelGGL(lwg_spade_skip_scan_kernel, dim3(1), dim3(1024), 0, stream, marks, (int)tiles, heavy, light, counts);
+    return (int)hipGetLastError();
+}

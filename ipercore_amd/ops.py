@@ -356,6 +356,42 @@ def _wwino4(spec):
     return spec._wwino4
 
 
+SPADE_SKIP = True       # switch: the SPADE convolutions of the attention sites ("winograd" mode, fp32, F(4x4, 3x3) launches of the 8-wave form) run
+                        # list-driven - blocks whose input window is all background are filled from a calibration frame
+SPADE_SKIP_D = (1, 5)   # pixels a block's window reaches beyond the block: the `shared` convolution, the gamma | beta convolution behind it
+
+
+_LISTS_APPLY = {}
+
+
+def spade_skip_lists(flow, d):
+    """The heavy / light tile lists of one frame batch for ``conv2d(..., lists=)`` from its resized flows (B, ns, h, w, 2): two launches, everything
+    stays in device memory (lwg_spade_skip_lists_f32).  Returns (heavy, light, counts) int32 tensors."""
+    B, ns, h, w, two = flow.shape
+    assert two == 2 and flow.dtype == torch.float32
+    tiles = B * ((h + 15) // 16) * ((w + 31) // 32)
+    buf = torch.empty(3 * tiles + 2, device=flow.device, dtype=torch.int32)
+    marks, heavy, light, counts = buf[:tiles], buf[tiles:2 * tiles], buf[2 * tiles:3 * tiles], buf[3 * tiles:]
+    i32 = torch.int32
+    _lib.check(_lib.lib().lwg_spade_skip_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
+                                                   _ptr(counts, i32), _stream()), "lwg_spade_skip_lists_f32")
+    return heavy, light, counts
+
+
+def conv2d_lists_apply(x0, spec, y, epi=EPI_NONE, act=ACT_NONE, xn=None, mean=None, rstd=None):
+    """Would ``conv2d`` run this launch list-driven if it were given lists?  A rule on the configuration (precision mode, switches, layer) and the
+    launch's size (lwg_conv2d_winograd4_list_applies: the 8-wave form) - never on the tensors' content."""
+    if not SPADE_SKIP or CONV_PRECISION != "winograd" or not x0.is_cuda or x0.dtype != torch.float32 or not _wino4_use(spec, False) or \
+            not _wino_eligible(spec, x0, y, None, epi, act, None, False):
+        return False
+    key = (x0.shape, y.shape, spec.Cin, spec.N, epi, act)          # the C rule reads the launch's sizes only: asked once per shape
+    if key not in _LISTS_APPLY:
+        a = conv_args(x0, spec, y, None, epi, act, None, xn, mean, rstd)
+        a.w = _ptr(_wwino4(spec))
+        _LISTS_APPLY[key] = bool(_lib.lib().lwg_conv2d_winograd4_list_applies(a))
+    return _LISTS_APPLY[key]
+
+
 def conv_args(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, mean=None, rstd=None,
               out_hw=None, ycoff=0, q4=False):
     """Fill the C-ABI argument block of one conv launch (see ``conv2d``).  q4: y is (B, YC/4, YH, YW, 4) - channel-quad planes
@@ -401,8 +437,9 @@ def _hook_end(a, spec, epi, kind, slices=True, extra=0):
 
 
 def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, mean=None, rstd=None,
-           out_hw=None, ycoff=0, splitk=False, q4=False):
+           out_hw=None, ycoff=0, splitk=False, q4=False, lists=None):
     """y <- conv(cat[x0, x1]) per ``spec``; x*: (B,H,W,C) NHWC; y: (B,YH,YW,YC) NHWC (written in place).
+    lists: (heavy, light, counts, cal) - ``spade_skip_lists`` and the calibration frame - for a launch ``conv2d_lists_apply`` accepted.
     splitk: let the library split small-M / large-K launches over K (the training step's one-sample launches).  Off on the
     synthesis path: a frame's result must not depend on how many frames share its launch (batch invariance is a parity check).
     q4: y is (B, YC/4, YH, YW, 4), channel-quad planes (the fp32 MFMA path only: what ``head_compose(..., q4=True)`` reads)."""
@@ -411,6 +448,8 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         raise ValueError("channel-quad-plane outputs: fp32 activations on the fp32 MFMA path, no split-K")
     if CONV_HOOK is not None:
         CONV_HOOK(True, a.M, spec, epi, None)
+    if lists is not None and not (x0.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION == "winograd" and _wino4_use(spec, splitk)):
+        raise ValueError("lists: the F(4x4, 3x3) launches of the \"winograd\" mode only (conv2d_lists_apply)")
     kind, sliced, extra = "direct", True, 0
     if x0.dtype == torch.bfloat16:
         kind = "bf16"
@@ -446,7 +485,12 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         if _wino4_use(spec, splitk):
             a.w = _ptr(_wwino4(spec))
             kind = "winograd4"
-            _lib.check(_lib.lib().lwg_conv2d_winograd4_f32(a, _stream()), "lwg_conv2d_winograd4_f32")
+            if lists is not None:
+                i32 = torch.int32
+                ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32), _ptr(lists[3]))
+                _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
+            else:
+                _lib.check(_lib.lib().lwg_conv2d_winograd4_f32(a, _stream()), "lwg_conv2d_winograd4_f32")
         elif nws:
             a.w = _ptr(_wwino(spec))
             ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
