@@ -169,6 +169,15 @@ int lwg_conv2d_winograd4_list_applies(const LwgConvArgs* args);
  * of its block's window - the block grown by d pixels, clipped to the image - has an in-image tap of any source by lwg_lwb_attention_x's own predicate
  * (csrc/lwg_lwb_taps.h).  marks: B * tiles ints of scratch; heavy, light: B * tiles ints each; counts: 2 ints.  Two launches, a deterministic scan. */
 int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, lwg_stream_t stream);
+/* The same at the granularity of 16 x 8 SUB-TILES (csrc/lwg_conv_wino.h CW4F_*): a 32 x 16 block is four sub-tiles, sub-tile id =
+ * 4 * tile + 2 * (sub-tile row) + sub-tile column; a sub-tile is heavy / light by the same rule applied to ITS window, sub-tiles wholly outside the image
+ * are in neither list.  lwg_spade_skip_fine_lists_f32 writes the block lists as above AND the sub-tile lists (fmarks, fheavy, flight: 4 * B * tiles ints
+ * each, fcounts: 2 ints) in the same two launches; a block's mark is the OR of its sub-tiles' marks.  lwg_conv2d_winograd4_fine_f32 takes the SUB-TILE
+ * lists in lists->heavy / light / counts: a workgroup runs the unchanged K loop on groups of four heavy sub-tiles of any frames and positions, light
+ * sub-tiles are filled from cal.  Contract, launch-size rule (lwg_conv2d_winograd4_list_applies) and result: those of lwg_conv2d_winograd4_list_f32. */
+int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
+int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, int* fmarks,
+                                  int* fheavy, int* flight, int* fcounts, lwg_stream_t stream);
 /* That panel from the fp32 GEMM panel of the same convolution (arguments as lwg_winograd_panel_f32): U = G w G^T in fp64, rounded once. */
 int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream);
 /* The same convolution for the 3x3 (9 taps) and 2x2 (4 taps, transposed-conv parity) stride-1 launches, as the

@@ -48,6 +48,15 @@
 #define W4_NPL 28                                // planes: rows 0..3 x 4 output columns, rows 4 / 5: 2 halves x 3 partial sums
 #define W4_MS (W4_NPL * 16 * W4_MSR)             // one pass = 16 patches
 #define W4_BIAS_OFF (W4_LOOP > W4_MS ? W4_LOOP : W4_MS)          // the block's 64 bias values, behind both uses of the LDS
+// FINE (the sub-tile form, lwg_conv_wino.h CW4F_*): the SAME rows of W4_RS = 40 floats - the 18-pixel halo rows of two slots side by side, 20 floats
+// apart, the lower two slots ten rows down: a channel plane is 20 rows + 4 (4 PLANE = 16 mod 32 as above).  The patches (pty, ptx 0-3 | 4-7) of a
+// ds_read_b128 lane group start in rows 0, 4, 10, 14 = bank quads 0, 8, 4, 12 (+ ptx % 4): sixteen distinct ones.
+#define W4F_SLOT(s) (((s) / CW4F_NSX) * CW4F_HH * W4_RS + ((s) % CW4F_NSX) * (W4_RS / CW4F_NSX))
+#define W4F_PLANE (CW4F_NS / CW4F_NSX * CW4F_HH * W4_RS + 4)
+static_assert(W4_RS / CW4F_NSX >= CW4F_HW && (W4_RS / CW4F_NSX) % 4 == 0 && W4F_PLANE >= W4_PLANE, "two sub-tile halo rows per LDS row");
+#define W4F_LOOP (2 * W4_KS * W4F_PLANE + 2 * W4_VS + W4_THREADS + 3 * W4F_PLANE)
+#define W4F_BIAS_OFF (W4F_LOOP > W4_MS ? W4F_LOOP : W4_MS)
+static_assert(CW4F_SX == 16 && CW4F_SY == 8 && CW4F_NS * CW4F_ROUNDS * 64 == W4_NQ * W4_THREADS, "sub-tile halo: four slots x six wave rounds = the staged elements");
 #ifndef LWG_W4_XCD
 #define LWG_W4_XCD 1         // XCD-aware block order (see the kernel): 0 = off (lab)
 #endif
@@ -107,11 +116,12 @@ __device__ __forceinline__ void w4_bt6(const float (&r)[6], float (&v)[6]) {
 __device__ __forceinline__ float w4_spade_mod(float x, float mu, float rs, float gam, float bet) { return (x - mu) * rs * (1.f + gam) + bet; }
 // (the activation resolved once per sixteen values - lwg_common.h; around the whole output pass the four copies of the pass cost registers:
 // 40-90 spilled, their reloads between the stores each waiting for every store before them)
-__device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[4]) {
+template <int NR>
+__device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[NR]) {
     lwg_act_dispatch(act, [&](auto ACTC) {
         constexpr int EA = decltype(ACTC)::value;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < NR; ++i)
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[i][c] = lwg_act_c<EA>(o[i][c], act);
     });
@@ -121,8 +131,18 @@ __device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[4]) {
 // memory (lwg_conv_wino.h: cw_list_entry) - the heavy entries through the K loop and epilogue below, untouched, then the light ones from the calibration
 // frame in a streaming loop without LDS.  Heavy first: a static walk that mixed them would leave most workgroups waiting for the few
 // that drew the heavy blocks of a clustered body.
-template <int EPI, bool TWO, bool SM, bool LIST>
+// FINE (lwg_conv2d_winograd4_fine_f32; a LIST form): the lists hold 16 x 8 sub-tiles; a workgroup's "block" is a GROUP of four heavy sub-tiles - any
+// frames, any positions - in the four slots of its 4 x 8 patches (cw4f_slot_of_patch).  Only the halo staging (four 18 x 10 sub-planes per channel
+// plane, a wave stages the halo of one slot = one image descriptor), the transform's base addresses and the epilogue's output bases (the reader's slot is
+// wave-uniform per pass) differ; the K loop is the same code.
+template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false>
 __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists& sk) {
+    static_assert(!FINE || (LIST && !SM && !TWO && LWG_W4_RDMAP), "the sub-tile form: a list-driven 8-wave launch");
+    constexpr int RS = W4_RS;                                // the halo planes' geometry in LDS
+    constexpr int PLANE = FINE ? W4F_PLANE : W4_PLANE;
+    constexpr int RAW = W4_KS * PLANE;
+    constexpr int DUMP_OFF = 2 * RAW + 2 * W4_VS;
+    constexpr int BIAS_OFF = FINE ? W4F_BIAS_OFF : W4_BIAS_OFF;
     constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;          // (its 32 accumulator rows: gamma | beta of the SAME 16 channels, cw4_n0_spade_small)
     constexpr int NVP = SM && !SMS ? 2 : 1;                  // patches per reader thread and pass
     constexpr int NTH = SM ? 256 : W4_THREADS;               // threads per workgroup
@@ -145,11 +165,14 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     int blk = blockIdx.x;
     // LIST: the heavy entries' number (the ids below it run the K loop); a workgroup may own none
     // (counts and tile ids are clamped to the launch's grid: lists that do not belong to this launch must not become addresses)
-    const int nht = LIST ? min(max(__builtin_amdgcn_readfirstlane(sk.counts[0]), 0), g.tiles) : 0;
-    const int nhe = nht * (N / NBV);
+    // (FINE: the entries are sub-tiles, nhe counts their groups)
+    const int nall = FINE ? cw4f_in_image_total(a.B, H, W) : g.tiles;
+    const int nht = LIST ? min(max(__builtin_amdgcn_readfirstlane(sk.counts[0]), 0), nall) : 0;
+    const int nhe = (FINE ? cw4f_groups(nht) : nht) * (N / NBV);
     // a launch whose tiles are ALL heavy (a frame batch without background) walks its blocks in the plain entry point's order - decided here, on the
     // device: the list order costs such a launch 0.3-3 % (profiles/spade_skip_ab_tool_list_order.txt)
-    const bool lst = LIST ? nht < g.tiles : false;
+    // (FINE: the entry point's second kernel runs the plain body for such a launch - this body always walks its lists)
+    const bool lst = FINE ? true : LIST ? nht < nall : false;
     const bool run = lst ? blk < nhe : true;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(144u * (unsigned)Cin * (unsigned)N), 0x00020000);
@@ -158,9 +181,34 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     floatx16 acc[9];                                         // products 0..5: (xi = q, nu); 6..8: (xi = 4 + q / 2, nu = 3 (q % 2) + 0..2)
     CwBlock<NQ, TWO> bk;                                     // the per-block state (lwg_conv_wino.h), this thread's NQ halo offsets in it
     unsigned uvoff, uvoffc;                                  // this lane's column of the fragment panel: the 16-byte parts, the ninth product
+    int fs0 = 0, fs1 = 0;                                    // FINE: the sub-tiles of this wave's reader patches, passes 0 | 1 (-1: an empty slot)
     auto setup = [&](int id) {
         int cb, t;
-        if constexpr (LIST) {
+        if constexpr (FINE) {
+            int tids = tid;
+            asm volatile("" : "+v"(tids));
+            int fsub[CW4F_NS], slot;                         // the group's sub-tiles
+            cw_list_entry(id, N / NBV, slot, cb);
+#pragma unroll
+            for (int k = 0; k < CW4F_NS; ++k) {
+                const int ix = cw4f_slot_index(slot, k, nht);
+                fsub[k] = ix < 0 ? -1 : min(max(__builtin_amdgcn_readfirstlane(sk.heavy[ix]), 0), CW4F_NS * g.tiles - 1);
+            }
+            bk.n0 = cw_n0(cb, NBV);
+            // a wave stages the halo of ONE slot (cw4f_halo_elem: slot wid / 2): one image descriptor
+            const int hs = wid >> 1, u = hs == 0 ? fsub[0] : hs == 1 ? fsub[1] : hs == 2 ? fsub[2] : fsub[3];
+            int b, x0, y0;
+            cw4f_corner(g, max(u, 0), b, x0, y0);
+            bk.rx0 = cw_image_rsrc(a.x0, __builtin_amdgcn_readfirstlane(b), H, W, a.C0, 4u);
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) {
+                int s, j;
+                cw4f_halo_elem(tids + NTH * k, s, j);
+                bk.voff0[k] = cw4f_halo_voff(u >= 0, j, x0, y0, H, W, a.C0);
+            }
+            // the epilogue's: pass ph reads patch rows 2 ph, 2 ph + 1, this wave the columns 4 (wid / 4) .. + 3 - slot 2 ph + wid / 4
+            fs0 = (wid >> 2) ? fsub[1] : fsub[0], fs1 = (wid >> 2) ? fsub[CW4F_NSX + 1] : fsub[CW4F_NSX];
+        } else if constexpr (LIST) {
             if (lst) {
                 int slot;
                 cw_list_entry(id, N / NBV, slot, cb);
@@ -171,10 +219,12 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         } else {
             cw_block(o, id, cb, t);
         }
+        if constexpr (!FINE) {
         bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV));
         int tids = tid;                                      // (through an empty asm: the halo geometry is recomputed per block - hoisted out of the block
         asm volatile("" : "+v"(tids));                       //  loop it would sit in registers through the K loop)
         bk.halo(a, tids, NTH, W4_HW, W4_NEL);
+        }
         const int col = SMS ? bk.n0 + (((lane & 31) >> 4) << 5) + (lane & 15) : bk.n0 + ct * 32 + (lane & 31);      // this lane's accumulator row = panel column
         uvoff = (unsigned)(((lane >> 5) * 9 * N + 4 * col) * 4);
         uvoffc = (unsigned)(((lane >> 5) * 9 * N + 8 * N + col) * 4);
@@ -184,8 +234,15 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
         const int i = tid + NTH * k;
+        if constexpr (FINE) {
+            int s, j, hy, hx, hq;
+            cw4f_halo_elem(i, s, j);
+            cw4f_halo_place(j, hy, hx, hq);
+            wst[k] = j < CW4F_NEL ? 4 * hq * PLANE + W4F_SLOT(s) + hy * RS + hx : DUMP_OFF + tid;
+        } else {
         const int pix = i >> 1, hq = i & 1, hy = pix / W4_HW, hx = pix - hy * W4_HW;
-        wst[k] = i < W4_NEL ? 4 * hq * W4_PLANE + hy * W4_RS + hx : W4_DUMP_OFF + tid;
+        wst[k] = i < W4_NEL ? 4 * hq * PLANE + hy * RS + hx : DUMP_OFF + tid;
+        }
     }
     floatx4 rreg[NQ];
     auto rld1 = [&](int st, int k) -> floatx4 {              // a stage's 8 channels lie in ONE input (C0 % 8 == 0)
@@ -196,7 +253,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #endif
         return bk.template rld1<W4_NT_LD>(a, c, k);
     };
-    auto rst1 = [&](int buf, int k, floatx4 v) { cw_rst1(raw0 + buf * W4_RAW + wst[k], W4_PLANE, v); };
+    auto rst1 = [&](int buf, int k, floatx4 v) { cw_rst1(raw0 + buf * RAW + wst[k], PLANE, v); };
     // weights: lane = (k-half lane / 32, channel lane % 32); element (q, stage, k-pair, k-half) = 9 N floats: [N][4] products 0-3, [N][4] products 4-7, [N] product 8 -
     // every load instruction reads contiguous memory (32 lanes x 16 bytes), nothing is padding
     floatx4 ufa[4], ufb[4];                                  // [register set = k-pair]: loaded TWO k-pairs ahead
@@ -227,7 +284,12 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     // the input transform's thread: patch tid % 32, channel (tid / 32) % 8, rows 3 half .. 3 half + 2
     const int patch = tid & 31, tc = (tid >> 5) & 7;
     const int pty = patch >> 3, ptx = patch & 7;
-    unsigned dbs = (unsigned)(tc * W4_PLANE + (4 * pty) * W4_RS + 4 * ptx) >> 2;      // its 6 x 6 input patch inside raw[0] (float index; 16-byte aligned)
+    int pby = pty, pbx = ptx, pslot = 0;                     // FINE: the patch inside its slot's sub-plane
+    if constexpr (FINE) {
+        cw4f_patch_in_slot(pty, ptx, pby, pbx);
+        pslot = W4F_SLOT(cw4f_slot_of_patch(pty, ptx));
+    }
+    unsigned dbs = (unsigned)(tc * PLANE + pslot + (4 * pby) * RS + 4 * pbx) >> 2;      // its 6 x 6 input patch inside raw[0] (float index; 16-byte aligned)
     asm volatile("" : "+v"(dbs));
     dbs <<= 2;
     // per half hf of the transform (this thread's one - index 0 - or, SM, both): the rows of X start at row hf; its 18 transformed values inside Vs[0]:
@@ -237,11 +299,11 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
     for (int hi = 0; hi < NHF; ++hi) {
         const int hf = SM ? hi : half;
-        dbx[hi] = (unsigned)(tc * W4_PLANE + (4 * pty + hf) * W4_RS + 4 * ptx) >> 2;
+        dbx[hi] = (unsigned)(tc * PLANE + pslot + (4 * pby + hf) * RS + 4 * pbx) >> 2;
         asm volatile("" : "+v"(dbx[hi]));
         dbx[hi] <<= 2;
-        vbx[hi] = (unsigned)(2 * W4_RAW + (hf ? 30 : 0) * W4_KS * 32 + tc * 32 + patch);
-        vbt[hi] = (unsigned)(2 * W4_RAW + (hf ? 18 : 6) * W4_KS * 32 + tc * 32 + patch);
+        vbx[hi] = (unsigned)(2 * RAW + (hf ? 30 : 0) * W4_KS * 32 + tc * 32 + patch);
+        vbt[hi] = (unsigned)(2 * RAW + (hf ? 18 : 6) * W4_KS * 32 + tc * 32 + patch);
         asm volatile("" : "+v"(vbx[hi]));
         asm volatile("" : "+v"(vbt[hi]));
         alpha[hi] = hf ? -1.f : -4.f;
@@ -249,8 +311,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         nbeta[hi] = -beta[hi];
     }
     unsigned fbs[2];                                         // this lane's fragments: products 0..5 | 6..8, inside Vs[0]
-    fbs[0] = (unsigned)(2 * W4_RAW + (6 * q) * W4_KS * 32 + lane);
-    fbs[1] = (unsigned)(2 * W4_RAW + (6 * (4 + (q >> 1)) + 3 * (q & 1)) * W4_KS * 32 + lane);
+    fbs[0] = (unsigned)(2 * RAW + (6 * q) * W4_KS * 32 + lane);
+    fbs[1] = (unsigned)(2 * RAW + (6 * (4 + (q >> 1)) + 3 * (q & 1)) * W4_KS * 32 + lane);
     asm volatile("" : "+v"(fbs[0]));
     asm volatile("" : "+v"(fbs[1]));
     float fb[9];                                             // the current k-pair's nine fragments (each refilled right behind its MFMA)
@@ -258,8 +320,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         return smem[fbs[j < 6 ? 0 : 1] + buf * W4_VS + ((j < 6 ? j : j - 6) * W4_KS + 2 * kk) * 32];
     };
     auto rd6 = [&](unsigned base, int buf, int r, float (&d)[6]) {     // row r (from the base's row) of this thread's patch in raw[buf]
-        const floatx4 v4 = *reinterpret_cast<const floatx4*>(smem + base + buf * W4_RAW + r * W4_RS);
-        const float2 v2 = *reinterpret_cast<const float2*>(smem + base + buf * W4_RAW + r * W4_RS + 4);
+        const floatx4 v4 = *reinterpret_cast<const floatx4*>(smem + base + buf * RAW + r * RS);
+        const float2 v2 = *reinterpret_cast<const float2*>(smem + base + buf * RAW + r * RS + 4);
         d[0] = v4[0]; d[1] = v4[1]; d[2] = v4[2]; d[3] = v4[3]; d[4] = v2.x; d[5] = v2.y;
     };
     auto vst6 = [&](unsigned base, int buf, int i, const float (&v)[6]) {   // six values of a row of V -> Vs[buf], row i behind the base's
@@ -465,7 +527,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         rst1(0, k, r0[k]);
         rst1(1, k, r1[k]);
     }
-    if (tid < NBV) smem[W4_BIAS_OFF + tid] = bq;
+    if (tid < NBV) smem[BIAS_OFF + tid] = bq;
     __syncthreads();
     transform_full(0);
     __syncthreads();
@@ -480,7 +542,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     if (q == 1) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const floatx4 b4 = *reinterpret_cast<const floatx4*>(smem + W4_BIAS_OFF + ct * 32 + 8 * g + 4 * (lane >> 5));
+            const floatx4 b4 = *reinterpret_cast<const floatx4*>(smem + BIAS_OFF + ct * 32 + 8 * g + 4 * (lane >> 5));
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[1][4 * g + k] = b4[k];
         }
@@ -496,7 +558,9 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         iteration(s + 1, IntC<1>(), IntC<0>());
     }
     W4TS(2);
-    const int eb = bk.b, ex0 = bk.x0, ey0 = bk.y0, en0 = bk.n0;          // this block's coordinates (the state moves on to the next block below)
+    int eb = FINE ? 0 : bk.b, ex0 = FINE ? 0 : bk.x0, ey0 = FINE ? 0 : bk.y0;     // this block's coordinates (the state moves on to the next block below)
+    const int en0 = bk.n0;
+    const int es0 = fs0, es1 = fs1;
     // epilogue.  (1) M A in registers: row q -> F[b] (b = 0..3, into acc[0..3]); the half row -> three partial sums (into acc[6..8]):
     //   nu 0..2: a0 = m0 + m1 + m2, a1 = m1 - m2, a2 = m1 + m2;  nu 3..5: b0 = m3 + m4, b1 = m3 - m4, b2 = m5
     //   (F[0] = a0 + b0, F[1] = a1 + 2 b1, F[2] = a2 + 4 b0, F[3] = a1 + 8 b1 + b2: finished by the reader)
@@ -544,17 +608,21 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     const int n4 = SMS ? (lanee & 3) * 4 : LWG_W4_RDMAP && !SM ? (gidx & 7) * 4 : (lanee & 7) * 4;
     const int cbase = SMS ? (en0 >> 6) * 32 + ((en0 >> 4) & 1) * 16 : en0 >> 1;       // SPADE: the block's first output channel
     floatx4 mu, rs;
-    if (EPI == LWG_EPI_SPADE) {
-        mu = *reinterpret_cast<const floatx4*>(a.mean + (size_t)eb * a.YC + cbase + n4);
-        rs = *reinterpret_cast<const floatx4*>(a.rstd + (size_t)eb * a.YC + cbase + n4);
-    }
     // image eb of the output (and of res / xn: the output's layout) as ONE buffer: a reader thread's four pixels are 32-bit offsets inside it (out of
     // range: right of / below the image - the hardware drops the store and returns zeros for the load), the second channel group an immediate
     typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
     const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
     const float* const esrc = EPI == LWG_EPI_SPADE ? a.xn : EPI == LWG_EPI_RESIDUAL ? a.res : a.y;
-    const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(esrc) + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t ry, re;
+    auto eframe = [&]() {                                    // image eb: once per block (FINE: per pass - the slot's image)
+        if (EPI == LWG_EPI_SPADE) {
+            mu = *reinterpret_cast<const floatx4*>(a.mean + (size_t)eb * a.YC + cbase + n4);
+            rs = *reinterpret_cast<const floatx4*>(a.rstd + (size_t)eb * a.YC + cbase + n4);
+        }
+        ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
+        re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(esrc) + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
+    };
+    if constexpr (!FINE) eframe();
     const int chan = EPI == LWG_EPI_SPADE ? cbase + n4 : a.ycoff + en0 + n4;
     bool more = false;
     int nblk = blk;
@@ -563,6 +631,14 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         // (pass 0 needs no barrier in front of its writes: the last LDS reads of the K loop - the fragments of its last k-pair - were issued in front of
         // the last stage's barrier; pass 1 waits for the readers of pass 0)
         if (ph == 1) __syncthreads();
+        if constexpr (FINE) {
+            const int u = ph ? es1 : es0;
+            int ub;
+            cw4f_corner(g, max(u, 0), ub, ex0, ey0);
+            eb = __builtin_amdgcn_readfirstlane(ub);
+            if (u < 0) ex0 = W, ey0 = H;                     // an empty slot: every store out of range
+            eframe();
+        }
         if (((lanee >> 4) & 1) == ph) {
             float* dst = Ms + (lanee & 15) * MSR + ct * 32 + 4 * (lanee >> 5);
 #pragma unroll
@@ -580,7 +656,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
         for (int hp = 0; hp < NVP; ++hp) {
             const int p = ph * 16 + (SMS ? lanee >> 2 : SM ? 8 * hp + (lanee >> 3) : p16);
-            const int ox = ex0 + 4 * (p & 7) + rb, oyb = ey0 + 4 * (p >> 3);
+            const int ox = ex0 + 4 * (FINE ? (p & 7) % (CW4F_SX / 4) : (p & 7)) + rb, oyb = ey0 + 4 * (FINE ? (p >> 3) % (CW4F_SY / 4) : (p >> 3));
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 vo[hp][i] = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan);
@@ -597,7 +673,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             // (unconditional: the last block re-requests its own first stages, nobody waits for them; see conv_winograd.hip)
             W4TS(8);
             nblk = blk + (int)gridDim.x;
-            if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
+            if constexpr (FINE) more = nblk < nhe;
+            else if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
             else more = cw_has_block(o, nblk);
             setup(more ? nblk : blk);
             W4TS(9);
@@ -681,9 +758,11 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         // four loads / stores; consecutive lanes = the quads of a pixel (a pixel's 256 / 128 bytes contiguous).  Pixels right of / below the image: the
         // out-of-range offset (dropped stores, zero loads), as in the epilogue.
         typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
+        // FINE: a light entry is a sub-tile, 128 pixels (cw4f_light_pixel): NPASS passes in all, NI at a time
         constexpr int NQD = EPI == LWG_EPI_SPADE ? 8 : 16;
+        constexpr int NPASS = (FINE ? CW4F_SX * CW4F_SY : 512) * NQD / W4_THREADS, NI = NPASS < 4 ? NPASS : 4;
         const int ncb = N / NBV;
-        const int nend = nhe + min(max(__builtin_amdgcn_readfirstlane(sk.counts[1]), 0), g.tiles - nht) * ncb;
+        const int nend = nhe + min(max(__builtin_amdgcn_readfirstlane(sk.counts[1]), 0), nall - nht) * ncb;
         const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
         // the calibration frame (one image): the output's layout | SPADE: the N stacked gamma | beta columns
         const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sk.cal), 0, (int)((unsigned)(H * W) * (unsigned)(EPI == LWG_EPI_SPADE ? N : a.YC) * 4u), 0x00020000);
@@ -691,10 +770,16 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         for (int id = cw_list_first_light((int)blockIdx.x, (int)gridDim.x, nhe); id < nend; id += (int)gridDim.x) {
             int slot, cb;
             cw_list_entry(id - nhe, ncb, slot, cb);
-            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), g.tiles - 1);
-            const int eb = __builtin_amdgcn_readfirstlane(cw_image(g, t)), en0 = cw_n0(cb, NBV);
-            int ex0, ey0;
-            cw_corner(g, t - eb * g.bx * g.by, 4 * W4_PBX, 4 * W4_PBY, ex0, ey0);
+            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), (FINE ? CW4F_NS : 1) * g.tiles - 1);
+            const int en0 = cw_n0(cb, NBV);
+            int eb, ex0, ey0;
+            if constexpr (FINE) {
+                cw4f_corner(g, t, eb, ex0, ey0);
+                eb = __builtin_amdgcn_readfirstlane(eb);
+            } else {
+                eb = __builtin_amdgcn_readfirstlane(cw_image(g, t));
+                cw_corner(g, t - eb * g.bx * g.by, 4 * W4_PBX, 4 * W4_PBY, ex0, ey0);
+            }
             const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
             int px, py, q4;
             cw4_light_elem(tid, 0, W4_THREADS, NQD, px, py, q4);
@@ -704,12 +789,13 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
                 const floatx4 mu = *reinterpret_cast<const floatx4*>(a.mean + (size_t)eb * a.YC + cbase + 4 * q4);
                 const floatx4 rs = *reinterpret_cast<const floatx4*>(a.rstd + (size_t)eb * a.YC + cbase + 4 * q4);
 #pragma unroll 1
-                for (int it = 0; it < 512 * NQD / W4_THREADS; it += 4) {
-                    unsigned vo[4];
-                    floatx4 o[4], gam[4], xv[4];
+                for (int it = 0; it < NPASS; it += NI) {
+                    unsigned vo[NI];
+                    floatx4 o[NI], gam[NI], xv[NI];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
+                    for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
+                        if constexpr (FINE) cw4f_light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, cbase + 4 * q4);
                         const unsigned vc = cw4_out_voff(ex0 + px, ey0 + py, H, W, N, en0 + 4 * q4);
                         gam[i] = cw_buf_load(rc, cw4_out_group(vc, 0, true), 0u);
@@ -717,26 +803,27 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
                         xv[i] = cw_buf_load<W4_NT_RES>(re, vo[i], 0u);
                     }
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
+                    for (int i = 0; i < NI; ++i)
 #pragma unroll
                         for (int c = 0; c < 4; ++c) o[i][c] = w4_spade_mod(xv[i][c], mu[c], rs[c], gam[i][c], o[i][c]);
                     w4_act16(a.act, o);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
+                    for (int i = 0; i < NI; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
                 }
             } else {
 #pragma unroll 1
-                for (int it = 0; it < 512 * NQD / W4_THREADS; it += 4) {
-                    unsigned vo[4];
-                    floatx4 o[4];
+                for (int it = 0; it < NPASS; it += NI) {
+                    unsigned vo[NI];
+                    floatx4 o[NI];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
+                    for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
+                        if constexpr (FINE) cw4f_light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, a.ycoff + en0 + 4 * q4);
                         o[i] = cw_buf_load(rc, vo[i], 0u);
                     }
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
+                    for (int i = 0; i < NI; ++i) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, o[i]), ry, (int)vo[i], 0, W4_NT_ST);
                 }
             }
         }
@@ -750,6 +837,19 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 template <int EPI>
 __global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_list_kernel(const LwgConvArgs a, const LwgConvLists sk) {
     w4_body<EPI, false, false, true>(a, sk);
+}
+template <int EPI>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) >= cw4f_in_image_total(a.B, a.H, a.W)) return;      // nothing is light: the kernel below
+    w4_body<EPI, false, false, true, true>(a, sk);
+}
+// ... and its companion, launched behind it: a launch in which nothing is light (a frame batch without background) runs the plain kernel's body - its
+// block order, staging and epilogue - decided here, on the device; every other launch ends at once.  (Two kernels, not two bodies in one: the
+// scalar-register spill lanes of both bodies together cost the SPADE form a vector register it does not have.)
+template <int EPI>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < cw4f_in_image_total(a.B, a.H, a.W)) return;
+    w4_body<EPI, false, false, false>(a, LwgConvLists{});
 }
 
 // The fragment panel from the fp32 GEMM panel of the same convolution (lwg_conv2d_nhwc_f32's w: [9 Cin / 4][N][4], k = ((c / 32) 9 + tap) 32 + c % 32):
@@ -842,4 +942,20 @@ extern "C" int lwg_conv2d_winograd4_list_f32(const LwgConvArgs* pa, const LwgCon
     const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
     return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
                                   : cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
+}
+
+// The sub-tile form (include/lwg_hip.h): pl->heavy / light / counts = the SUB-TILE lists of lwg_spade_skip_fine_lists_f32; the same contract and the same
+// launch-size rule (lwg_conv2d_winograd4_list_applies) as the block lists
+extern "C" int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
+    if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
+    if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const LwgConvArgs& a = *pa;
+    const size_t lds = (size_t)(W4F_BIAS_OFF + 64) * 4, ldsp = (size_t)(W4_BIAS_OFF + 64) * 4;
+    const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
+    const int e = a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_fine_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
+                                         : cw_launch_lists<lwg_conv_winograd4_fine_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
+    if (e != 0) return e;
+    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, ldsp, stream, a, *pl)
+                                  : cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, ldsp, stream, a, *pl);
 }

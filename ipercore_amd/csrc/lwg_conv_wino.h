@@ -134,6 +134,66 @@ CW_FN void cw4_light_elem(int tid, int it, int nth, int nq, int& px, int& py, in
     q4 = e - p * nq, px = p & 31, py = p >> 5;
 }
 
+// ---- sub-tile lists of F(4x4) (lwg_conv2d_winograd4_fine_f32, spade_skip.hip).  A 32 x 16 block is CW4F_NS sub-tiles of CW4F_SX x
+// CW4F_SY output pixels (patch-aligned: 4 x 2 patches); sub-tile u = CW4F_NS * block + s, s = sub-tile row * 2 + sub-tile column - so the sub-tiles of
+// a launch whose sub-tiles are all heavy are exactly the plain blocks, in their order.  A sub-tile is heavy / light by the block rule applied to ITS
+// window (cw_block_window of the sub-tile); sub-tiles wholly outside the image are in neither list.  The launch's heavy entries: entry e = (group
+// e / ncb, column block e % ncb), the group's CW4F_NS slots = heavy[CW4F_NS * group ..] (slots past the count: empty); patch (pty, ptx) of the
+// workgroup's 4 x 8 patches belongs to slot cw4f_slot_of_patch - a group that is one whole block has the plain block's patch numbering.
+#define CW4F_SX 16
+#define CW4F_SY 8
+#define CW4F_NSX (32 / CW4F_SX)
+#define CW4F_NS (CW4F_NSX * (16 / CW4F_SY))
+#define CW4F_HW (CW4F_SX + 2)                // a sub-tile's halo: 18 x 10 pixels
+#define CW4F_HH (CW4F_SY + 2)
+#define CW4F_NEL (CW4F_HW * CW4F_HH * 2)     // ... (pixel, channel quad) elements of a stage
+#define CW4F_ROUNDS ((CW4F_NEL + 63) / 64)   // ... in wave rounds of 64: six per slot = the three rounds of two waves - a wave stages ONE slot (one image descriptor)
+CW_FN int cw4f_slot_of_patch(int pty, int ptx) { return (pty / (CW4F_SY / 4)) * CW4F_NSX + ptx / (CW4F_SX / 4); }
+CW_FN void cw4f_patch_in_slot(int pty, int ptx, int& ly, int& lx) { ly = pty % (CW4F_SY / 4), lx = ptx % (CW4F_SX / 4); }
+// sub-tile u -> its image and corner
+CW_FN void cw4f_corner(const CwGrid& g, int u, int& b, int& x0, int& y0) {
+    const int t = u / CW4F_NS, s = u - t * CW4F_NS;
+    b = cw_image(g, t);
+    cw_corner(g, t - b * g.bx * g.by, 32, 16, x0, y0);
+    x0 += (s % CW4F_NSX) * CW4F_SX, y0 += (s / CW4F_NSX) * CW4F_SY;
+}
+CW_FN bool cw4f_in_image(int x0, int y0, int H, int W) { return x0 < W && y0 < H; }
+CW_FN int cw4f_in_image_total(int B, int H, int W) { return B * ((W + CW4F_SX - 1) / CW4F_SX) * ((H + CW4F_SY - 1) / CW4F_SY); }
+CW_FN int cw4f_groups(int nh) { return (nh + CW4F_NS - 1) / CW4F_NS; }
+CW_FN int cw4f_slot_index(int grp, int k, int nh) { return grp * CW4F_NS + k < nh ? grp * CW4F_NS + k : -1; }      // the heavy list's index, -1: empty
+// the classifier: which sub-tiles of the block at (x0, y0) hold the image pixel (x, y) in their window (bit s)
+CW_FN unsigned cw4f_reached(int x, int y, int x0, int y0, int d) {
+    unsigned m = 0;
+    for (int s = 0; s < CW4F_NS; ++s) {
+        const int sx = x0 + (s % CW4F_NSX) * CW4F_SX, sy = y0 + (s / CW4F_NSX) * CW4F_SY;
+        m |= (x >= sx - d && x < sx + CW4F_SX + d && y >= sy - d && y < sy + CW4F_SY + d ? 1u : 0u) << s;
+    }
+    return m;
+}
+// halo element i = tid + 512 k of a stage (wave (i / 64) % 8, its round k) -> its slot - the wave's: waves 2 s, 2 s + 1 share slot s, three rounds each -
+// and its element j inside the slot's halo (j >= CW4F_NEL: none)
+CW_FN void cw4f_halo_elem(int i, int& slot, int& j) {
+    const int wave = (i >> 6) & 7, k = i >> 9, per = CW4F_ROUNDS / 3, wr = 3 * wave + k;
+    slot = wave / per, j = (wr - slot * CW4F_ROUNDS) * 64 + (i & 63);
+}
+// ... -> its halo pixel (hy, hx) and channel quad hq; its byte offset inside the image of the sub-tile at (x0, y0), or the marker
+CW_FN void cw4f_halo_place(int j, int& hy, int& hx, int& hq) {
+    const int pix = j >> 1;
+    hq = j & 1, hy = pix / CW4F_HW, hx = pix - hy * CW4F_HW;
+}
+// (present = false: an empty slot - nothing but markers)
+CW_FN unsigned cw4f_halo_voff(bool present, int j, int x0, int y0, int H, int W, int C) {
+    int hy, hx, hq;
+    cw4f_halo_place(j, hy, hx, hq);
+    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+    return present && j < CW4F_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W ? (unsigned)((gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
+}
+// a light sub-tile's elements from cw4_light_elem's (px, py) of the first CW4F_SX * CW4F_SY pixels
+CW_FN void cw4f_light_pixel(int& px, int& py) {
+    const int p = py * 32 + px;
+    py = p / CW4F_SX, px = p - py * CW4F_SX;
+}
+
 // ---- the host contracts.  fp32 (lwg_conv2d_winograd_f32 / _f32_ws, lwg_conv2d_winograd4_f32): the launch description of the 3 x 3 / stride 1 /
 // pad 1 convolution as lwg_conv2d_nhwc_f32 takes it (nine taps, omul = 1, OH = H, OW = W, one or two inputs with C0 % 8 == 0, C1 % 8 == 0 and
 // (C0 + C1) % 16 == 0, N % 64 == 0, YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL (ycoff % 4 == 0) or LWG_EPI_SPADE (N = 2 YC, columns gamma | beta

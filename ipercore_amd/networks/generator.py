@@ -180,6 +180,11 @@ def run_bg_layers(layers, bg4):
             return ops.nhwc_to_nchw(y, channels=3)
 
 
+def _skip_lists(lists, cal):
+    """The ``lists`` argument of ``ops.conv2d``: the classifier's result with its sub-tile lists and the calibration frame (a plain triple: the 4-tuple)."""
+    return (lists, cal) if isinstance(lists, ops.SkipLists) else tuple(lists) + (cal,)
+
+
 def spade_calibration(st, x):
     """The calibration frames of one attention site at x's feature size, by the product kernels from ONE all-background frame (every flow -2):
     att_cal = lwb_attention_x, actv_cal = shared(att_cal), gb_cal (1, h, w, 2C) = the gamma | beta convolution of actv_cal with no epilogue and no
@@ -348,9 +353,9 @@ class AttentionLWBGenerator(nn.Module):
         # blocks whose input window is all background (flow -2: att = one vector) are filled from the site's calibration frames
         l1 = l5 = None
         if ops.conv2d_lists_apply(att, st["shared"], actv, act=ops.ACT_RELU):
-            l1 = scratch.lists(flow, ops.SPADE_SKIP_D[0]) + (spade_calibration(st, tsf_x)[0],)
+            l1 = _skip_lists(scratch.lists(flow, ops.SPADE_SKIP_D[0]), spade_calibration(st, tsf_x)[0])
         if ops.conv2d_lists_apply(actv, st["gb"], out, epi=ops.EPI_SPADE, xn=tsf_x, mean=mean, rstd=rstd):
-            l5 = scratch.lists(flow, ops.SPADE_SKIP_D[1]) + (spade_calibration(st, tsf_x)[1],)
+            l5 = _skip_lists(scratch.lists(flow, ops.SPADE_SKIP_D[1]), spade_calibration(st, tsf_x)[1])
         # (the keyword only where it is used: the CPU emulation of the tests installs a conv2d of its own, which knows no lists)
         ops.conv2d(att, st["shared"], actv, act=ops.ACT_RELU, **({} if l1 is None else {"lists": l1}))
         return ops.conv2d(actv, st["gb"], out, epi=ops.EPI_SPADE, xn=tsf_x, mean=mean, rstd=rstd, **({} if l5 is None else {"lists": l5}))

@@ -361,21 +361,39 @@ SPADE_SKIP = True       # switch: the SPADE convolutions of the attention sites 
 SPADE_SKIP_D = (1, 5)   # pixels a block's window reaches beyond the block: the `shared` convolution, the gamma | beta convolution behind it
 
 
+SPADE_SKIP_FINE = True  # ... at the granularity of 16 x 8 sub-tiles (four per block) where ``spade_skip_fine_apply`` says so; False: block lists everywhere
+
 _LISTS_APPLY = {}
+
+
+class SkipLists(tuple):
+    """``spade_skip_lists``'s result: the block-level (heavy, light, counts), and as ``.fine`` the sub-tile-level triple from the same launches."""
+    fine = None
+
+
+def spade_skip_fine_apply(x0):
+    """Does a list-driven launch on this input take the sub-tile lists?  A rule on the configuration only (switch, feature size)."""
+    return SPADE_SKIP_FINE
 
 
 def spade_skip_lists(flow, d):
     """The heavy / light tile lists of one frame batch for ``conv2d(..., lists=)`` from its resized flows (B, ns, h, w, 2): two launches, everything
-    stays in device memory (lwg_spade_skip_lists_f32).  Returns (heavy, light, counts) int32 tensors."""
+    stays in device memory (lwg_spade_skip_fine_lists_f32).  Returns (heavy, light, counts) int32 tensors of the 32 x 16 blocks - a ``SkipLists``,
+    whose ``.fine`` holds the same triple for the 16 x 8 sub-tiles."""
     B, ns, h, w, two = flow.shape
     assert two == 2 and flow.dtype == torch.float32
     tiles = B * ((h + 15) // 16) * ((w + 31) // 32)
-    buf = torch.empty(3 * tiles + 2, device=flow.device, dtype=torch.int32)
-    marks, heavy, light, counts = buf[:tiles], buf[tiles:2 * tiles], buf[2 * tiles:3 * tiles], buf[3 * tiles:]
+    buf = torch.empty(15 * tiles + 4, device=flow.device, dtype=torch.int32)
+    fmarks, fheavy, flight = buf[:4 * tiles], buf[4 * tiles:8 * tiles], buf[8 * tiles:12 * tiles]      # (the sub-tiles' marks first: 16-byte aligned)
+    bb = buf[12 * tiles:]
+    marks, heavy, light, counts, fcounts = bb[:tiles], bb[tiles:2 * tiles], bb[2 * tiles:3 * tiles], bb[3 * tiles:3 * tiles + 2], bb[3 * tiles + 2:]
     i32 = torch.int32
-    _lib.check(_lib.lib().lwg_spade_skip_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
-                                                   _ptr(counts, i32), _stream()), "lwg_spade_skip_lists_f32")
-    return heavy, light, counts
+    _lib.check(_lib.lib().lwg_spade_skip_fine_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
+                                                        _ptr(counts, i32), _ptr(fmarks, i32), _ptr(fheavy, i32), _ptr(flight, i32), _ptr(fcounts, i32),
+                                                        _stream()), "lwg_spade_skip_fine_lists_f32")
+    out = SkipLists((heavy, light, counts))
+    out.fine = (fheavy, flight, fcounts)
+    return out
 
 
 def conv2d_lists_apply(x0, spec, y, epi=EPI_NONE, act=ACT_NONE, xn=None, mean=None, rstd=None):
@@ -439,7 +457,8 @@ def _hook_end(a, spec, epi, kind, slices=True, extra=0):
 def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, mean=None, rstd=None,
            out_hw=None, ycoff=0, splitk=False, q4=False, lists=None):
     """y <- conv(cat[x0, x1]) per ``spec``; x*: (B,H,W,C) NHWC; y: (B,YH,YW,YC) NHWC (written in place).
-    lists: (heavy, light, counts, cal) - ``spade_skip_lists`` and the calibration frame - for a launch ``conv2d_lists_apply`` accepted.
+    lists: (heavy, light, counts, cal) - ``spade_skip_lists`` and the calibration frame - for a launch ``conv2d_lists_apply`` accepted; or
+    (SkipLists, cal): the sub-tile lists where ``spade_skip_fine_apply`` says so, else the block lists.
     splitk: let the library split small-M / large-K launches over K (the training step's one-sample launches).  Off on the
     synthesis path: a frame's result must not depend on how many frames share its launch (batch invariance is a parity check).
     q4: y is (B, YC/4, YH, YW, 4), channel-quad planes (the fp32 MFMA path only: what ``head_compose(..., q4=True)`` reads)."""
@@ -487,8 +506,16 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
             kind = "winograd4"
             if lists is not None:
                 i32 = torch.int32
+                fine = len(lists) == 2 and isinstance(lists[0], SkipLists)
+                if fine:
+                    sl, cal = lists
+                    fine = sl.fine is not None and spade_skip_fine_apply(x0)
+                    lists = tuple(sl.fine if fine else sl) + (cal,)
                 ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32), _ptr(lists[3]))
-                _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
+                if fine:
+                    _lib.check(_lib.lib().lwg_conv2d_winograd4_fine_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_fine_f32")
+                else:
+                    _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
             else:
                 _lib.check(_lib.lib().lwg_conv2d_winograd4_f32(a, _stream()), "lwg_conv2d_winograd4_f32")
         elif nws:

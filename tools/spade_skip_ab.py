@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """A/B of the list-driven SPADE convolutions (ops.SPADE_SKIP) on the benchmark's clip, one process.
 
-  1. the heavy share - blocks whose window holds a pixel with an in-image tap - per feature size and window reach d, from the classifier's counts;
-  2. per-launch times (HIP events around the conv entry points, ops.CONV_HOOK) of the eighteen SPADE launches of a frame batch with the switch off and
-     on, alternated --reps times; median per launch and the sum;
-  3. the same on an all-foreground batch (random in-image flows: every block heavy) - the worst case: the list-driven form against the plain entry point,
-     with the spread of the plain entry point's own repeats beside it.
+  1. the heavy share - 32 x 16 blocks and 16 x 8 sub-tiles whose window holds a pixel with an in-image tap - per feature size and window reach d, from
+     the classifier's counts;
+  2. per-launch times (HIP events around the conv entry points, ops.CONV_HOOK) of the eighteen SPADE launches of a frame batch with the switch off,
+     with the block lists (ops.SPADE_SKIP_FINE = False) and with the sub-tile lists, alternated --reps times; median per launch and the sum;
+  3. the same on an all-foreground batch (random in-image flows: everything heavy) - the worst case: the list-driven forms against the plain entry
+     point, with the spread of the plain entry point's own repeats beside it.
 
-Usage: python tools/spade_skip_ab.py [--size 512] [--frames 300] [--reps 5]"""
+Usage: python tools/spade_skip_ab.py [--size 512] [--frames 300] [--reps 5] [--control]"""
 import argparse
 import os
 import statistics
@@ -45,6 +46,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--control", action="store_true", help="a second plain run per round (off2): the gap between two runs of the SAME entry point")
     args = ap.parse_args()
     S, n = args.size, args.frames
     case = syn.build_case(image_size=S, n_frames=n, ns=2)
@@ -59,45 +61,53 @@ def main():
     g = torch.Generator().manual_seed(5)
     Tfg = (torch.rand(Tst.shape, generator=g) * 1.8 - 0.9).to(Tst.device)
 
-    print("heavy share of the 32 x 16 blocks (clip of %d frames at %d^2 | all-foreground batch):" % (n, S))
+    print("heavy share of the 32 x 16 blocks | the 16 x 8 sub-tiles (clip of %d frames at %d^2 | all-foreground batch):" % (n, S))
     for T, tag in ((Tst, "clip"), (Tfg, "all-fg")):
         for h in (S // 2, S // 4, S // 8):
             flow = ops.flow_resize(T, h, h)
             for d in ops.SPADE_SKIP_D:
-                _, _, counts = ops.spade_skip_lists(flow, d)
-                nh, nl = (int(v) for v in counts.cpu())
-                print("  %-6s %4d^2  d=%d  heavy %6d of %6d = %.3f" % (tag, h, d, nh, nh + nl, nh / (nh + nl)))
+                lists = ops.spade_skip_lists(flow, d)
+                nh, nl = (int(v) for v in lists[2].cpu())
+                fh, fl = (int(v) for v in lists.fine[2].cpu())
+                print("  %-6s %4d^2  d=%d  heavy %6d of %6d = %.3f | %7d of %7d = %.3f" % (tag, h, d, nh, nh + nl, nh / (nh + nl), fh, fh + fl, fh / (fh + fl)))
 
-    def run(T, skip):
+    MODES = (("off", False, False), ("block", True, False), ("sub", True, True)) + ((("off2", False, False),) if args.control else ())
+
+    def run(T, mode):
         t = _Timer(names)
-        prev = ops.SPADE_SKIP, ops.CONV_HOOK
-        ops.SPADE_SKIP, ops.CONV_HOOK = skip, t
+        prev = ops.SPADE_SKIP, ops.SPADE_SKIP_FINE, ops.CONV_HOOK
+        ops.SPADE_SKIP, ops.SPADE_SKIP_FINE, ops.CONV_HOOK = mode[1], mode[2], t
         try:
             gen.run_tsf(tsf8, feats, T, bg=bg, want_pred=True, want_mask=True)
         finally:
-            ops.SPADE_SKIP, ops.CONV_HOOK = prev
+            ops.SPADE_SKIP, ops.SPADE_SKIP_FINE, ops.CONV_HOOK = prev
         return t.times()
 
-    for T, tag in ((Tst, "clip"), (Tfg, "all-foreground batch (worst case: every block heavy)")):
-        for skip in (False, True):                            # warm-up: panels, calibration frames, clocks
-            run(T, skip)
-        rows = {False: [], True: []}
+    med = statistics.median
+    for T, tag in ((Tst, "clip"), (Tfg, "all-foreground batch (worst case: everything heavy)")):
+        for mode in MODES:                                    # warm-up: panels, calibration frames, clocks
+            run(T, mode)
+        rows = {m[0]: [] for m in MODES}
         for _ in range(args.reps):
-            for skip in (False, True):
-                rows[skip].append(run(T, skip))
-        print("\nper-launch ms, %s: median of %d alternated runs (off = lwg_conv2d_winograd4_f32, on = list-driven)" % (tag, args.reps))
-        tot = {False: [0.0] * args.reps, True: [0.0] * args.reps}
-        for j, (name, _) in enumerate(rows[False][0]):
-            off = [r[j][1] for r in rows[False]]
-            on = [r[j][1] for r in rows[True]]
-            for k in range(args.reps):
-                tot[False][k] += off[k]
-                tot[True][k] += on[k]
-            print("  %-13s off %7.3f (min %7.3f max %7.3f)   on %7.3f (min %7.3f max %7.3f)   on - off %+7.3f" %
-                  (name, statistics.median(off), min(off), max(off), statistics.median(on), min(on), max(on), statistics.median(on) - statistics.median(off)))
-        print("  sum of the %d launches: off %s   on %s" % (len(rows[False][0]), " ".join("%.2f" % v for v in tot[False]), " ".join("%.2f" % v for v in tot[True])))
-        print("  medians: off %.2f ms  on %.2f ms  (on - off %+.2f ms; spread of off %.2f ms)" %
-              (statistics.median(tot[False]), statistics.median(tot[True]), statistics.median(tot[True]) - statistics.median(tot[False]), max(tot[False]) - min(tot[False])))
+            for mode in MODES:
+                rows[mode[0]].append(run(T, mode))
+        print("\nper-launch ms, %s: median of %d alternated runs (off = lwg_conv2d_winograd4_f32, block = 32 x 16 lists, sub = 16 x 8 lists)" % (tag, args.reps))
+        tot = {m[0]: [0.0] * args.reps for m in MODES}
+        for j, (name, _) in enumerate(rows["off"][0]):
+            v = {m[0]: [r[j][1] for r in rows[m[0]]] for m in MODES}
+            for m in v:
+                for k in range(args.reps):
+                    tot[m][k] += v[m][k]
+            print("  %-13s " % name + "   ".join("%s %7.3f (min %7.3f max %7.3f)" % (m, med(v[m]), min(v[m]), max(v[m])) for m in v) +
+                  "   sub - block %+7.3f   sub - off %+7.3f" % (med(v["sub"]) - med(v["block"]), med(v["sub"]) - med(v["off"])))
+        for m in tot:
+            print("  sum of the %d launches, %-5s: %s" % (len(rows["off"][0]), m, " ".join("%.2f" % x for x in tot[m])))
+        print("  medians: off %.2f ms  block %.2f ms  sub %.2f ms  (sub - off %+.2f ms, sub - block %+.2f ms; spread of off %.2f ms)" %
+              (med(tot["off"]), med(tot["block"]), med(tot["sub"]), med(tot["sub"]) - med(tot["off"]), med(tot["sub"]) - med(tot["block"]),
+               max(tot["off"]) - min(tot["off"])))
+        if args.control:
+            print("  control: off2 %.2f ms (off2 - off %+.2f ms; spread of off and off2 together %.2f ms)" %
+                  (med(tot["off2"]), med(tot["off2"]) - med(tot["off"]), max(tot["off"] + tot["off2"]) - min(tot["off"] + tot["off2"])))
 
 
 if __name__ == "__main__":
