@@ -48,16 +48,16 @@ class conv_precision(object):
         self.mode = mode
 
     def __enter__(self):
-        global CONV_PRECISION, WINO4
-        self.prev = CONV_PRECISION, WINO4
-        if self.mode == "winograd2x2":
-            CONV_PRECISION, WINO4 = "winograd", False
-        else:
-            CONV_PRECISION = self.mode
+        global CONV_PRECISION, _MODE_WINO4
+        self.prev = CONV_PRECISION, _MODE_WINO4
+        CONV_PRECISION, _MODE_WINO4 = ("winograd", False) if self.mode == "winograd2x2" else (self.mode, True)
 
     def __exit__(self, *exc):
-        global CONV_PRECISION, WINO4
-        CONV_PRECISION, WINO4 = self.prev
+        global CONV_PRECISION, _MODE_WINO4
+        CONV_PRECISION, _MODE_WINO4 = self.prev
+
+
+_MODE_WINO4 = True      # the mode's say on the F(4x4, 3x3) kernel (False inside "winograd2x2"): set on every enter, never the lab switch WINO4
 
 
 # bench.py installs a callable(begin, M, spec, epi, info) to bracket conv entry-point calls with HIP events; info (the closing call only, else
@@ -72,7 +72,7 @@ def _stream():
 
 class ConvSpec:
     """Host description of one packed convolution (weights already in the kernel's layout)."""
-    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_w16v2", "_w16hr", "_w16x3", "_w16c8", "_w16up", "_w32up", "_wwino", "_wwino_t", "_wwino_t24", "_wwino4", "_wwino16")
+    __slots__ = ("w", "bias", "N", "Cin", "ntaps", "dy", "dx", "stride", "cshift", "omul", "ooy", "oox", "algo_kn", "_panels")
 
     def __init__(self, w, bias, N, Cin, taps, stride=1, omul=1, ooy=0, oox=0, algo_kn=None):
         self.w, self.bias, self.N, self.Cin = w, bias, int(N), int(Cin)
@@ -82,17 +82,7 @@ class ConvSpec:
         self.dy = [int(t[0]) for t in taps]
         self.dx = [int(t[1]) for t in taps]
         self.stride, self.omul, self.ooy, self.oox = stride, omul, ooy, oox
-        self._w16v2 = None
-        self._w16hr = None
-        self._w16x3 = None
-        self._w16c8 = None
-        self._w16up = None
-        self._w32up = None
-        self._wwino = None
-        self._wwino_t = None
-        self._wwino_t24 = None
-        self._wwino4 = None
-        self._wwino16 = None
+        self._panels = {}       # kernel-specific panels derived from w (and bias): read and written by _derived only
         self.cshift = 0
         if self.Cin % 32 != 0:
             q = self.Cin // 4
@@ -100,11 +90,42 @@ class ConvSpec:
             self.cshift = q.bit_length() - 1
 
 
+def _derived(specs, key, build, bias=False):
+    """The panel ``build()`` derives from one spec's fp32 GEMM panel, or from those of the four parity specs of a transposed convolution, built
+    once and kept on the (first) spec under ``key`` = (panel kind, whatever else selects a variant).  An entry records every tensor it was built
+    from - ``w`` of each spec, and the spec's ``bias`` where the entry hands a bias back (bias=True) - and is valid only while each of them IS
+    still the spec's current tensor (packing.spec_to to another device, a replaced weight); otherwise it is rebuilt.
+    The one thing this rule does not see is an in-place write to ``spec.w``: the trainer's persistent GEMM panels are refreshed in place
+    (PanelCache.refresh), which is sound because training specs are rebuilt by packing.pack_conv* on every step."""
+    specs = specs if isinstance(specs, (list, tuple)) else (specs,)
+    src = [s.w for s in specs] + ([specs[0].bias] if bias else [])
+    hit = specs[0]._panels.get(key)
+    if hit is None or len(hit[0]) != len(src) or any(a is not b for a, b in zip(hit[0], src)):
+        hit = specs[0]._panels[key] = (src, build())
+    return hit[1]
+
+
+def _tap_order9(spec):
+    """The 3x3 tap order of a spec: position 3 * (dy + 1) + (dx + 1) -> tap index in the GEMM panel."""
+    order = [0] * 9
+    for t in range(spec.ntaps):
+        order[3 * (spec.dy[t] + 1) + spec.dx[t] + 1] = t
+    return order
+
+
+def _spade_columns(N, blk, device):
+    """SPADE panels: for every column of a panel that interleaves gamma | beta in blocks of ``blk``, the column of the GEMM panel (blocks of 32)
+    that holds it."""
+    j = torch.arange(N, device=device)
+    ch, beta = blk * (j // (2 * blk)) + j % blk, (j % (2 * blk)) // blk
+    return 64 * (ch // 32) + (ch % 32) + 32 * beta
+
+
 def _w16v2(spec):
     """The bf16 panel of lwg_conv2d_nhwc_bf16, built once per spec from the fp32 panel [K/4][N][4] (K order: 32-channel chunk major,
     tap minor): [ntaps*Cin/64][N][64] with k = ((c/64)*ntaps + tap)*64 + c%64, the eight 16-byte k-octets of row n stored at slot
     octet ^ ((n >> 1) & 7) (include/lwg_hip.h)."""
-    if spec._w16v2 is None or spec._w16v2.device != spec.w.device:
+    def build():
         K4, N, _ = spec.w.shape
         cin, nt = spec.Cin, spec.ntaps
         assert cin % 64 == 0 and K4 * 4 == nt * cin, (cin, nt, K4)
@@ -115,8 +136,8 @@ def _w16v2(spec):
         slot = torch.arange(8, device=spec.w.device)
         src = slot[None, :] ^ ((n[:, None] >> 1) & 7)                              # octet stored at slot s of row n
         rows = torch.gather(rows, 2, src[None, :, :, None].expand(rows.shape[0], N, 8, 8))
-        spec._w16v2 = rows.reshape(cin // 64 * nt, N, 64).contiguous().to(torch.bfloat16)
-    return spec._w16v2
+        return rows.reshape(cin // 64 * nt, N, 64).contiguous().to(torch.bfloat16)
+    return _derived(spec, "w16v2", build)
 
 
 def _hr_eligible(spec, x0, y, out_hw):
@@ -139,23 +160,18 @@ def _w16hr(spec, spade):
     """(panel, bias) of lwg_conv2d_nhwc_bf16_hr: [ntaps*Cin/64][4][N][16] bf16, k = ((c/64)*ntaps + tap)*64 + c%64 split as
     ks*16 + e; for the SPADE epilogue the gamma | beta columns (and the bias) are re-interleaved from blocks of 32 to blocks of 16
     (include/lwg_hip.h).  Built once per (spec, spade)."""
-    key = bool(spade)
-    if spec._w16hr is None or spec._w16hr[0] != key or spec._w16hr[1].device != spec.w.device:
+    def build():
         K4, N, _ = spec.w.shape
         cin, nt = spec.Cin, spec.ntaps
         wk = spec.w.permute(0, 2, 1).reshape(cin // 64, 2, nt, 32, N).permute(0, 2, 1, 3, 4).reshape(cin // 64, nt, 64, N)    # [chunk][tap][k%64][n]
         wk = wk[:, _hr_tap_order(spec)].reshape(cin // 64 * nt, 64, N)                                                          # taps ascending in (dy, dx)
         bias = spec.bias
         if spade:
-            j = torch.arange(N, device=spec.w.device)
-            q, r = j // 32, j % 32
-            ch = 16 * q + (r % 16)
-            old = 64 * (ch // 32) + (ch % 32) + 32 * (r // 16)
+            old = _spade_columns(N, 16, spec.w.device)
             wk = wk[:, :, old]
             bias = None if bias is None else bias[old].contiguous()
-        panel = wk.reshape(cin // 64 * nt, 4, 16, N).permute(0, 1, 3, 2).contiguous().to(torch.bfloat16)
-        spec._w16hr = (key, panel, bias)
-    return spec._w16hr[1], spec._w16hr[2]
+        return wk.reshape(cin // 64 * nt, 4, 16, N).permute(0, 1, 3, 2).contiguous().to(torch.bfloat16), bias
+    return _derived(spec, ("w16hr", bool(spade)), build, bias=True)
 
 
 BF16_WINO_MIN_CIN = 64  # "bf16_winograd": layers with fewer input channels stay on the direct kernel (a rule on the LAYER, never on the batch)
@@ -196,30 +212,23 @@ def _wwino16(spec, spade):
     """(panel, bias) of lwg_conv2d_winograd_bf16, built once per (spec, spade) from the fp32 GEMM panel with torch ops on whatever device spec.w
     is on: U = G w G^T per (input channel, output column) in fp64, rounded ONCE to bf16, stored Upk[Cin/16][16][N][16] (wwino16_index); for the
     SPADE epilogue the gamma | beta columns (and the bias) go from the GEMM panel's blocks of 32 to blocks of 4 (wwino16_spade_column)."""
-    key = bool(spade)
-    if spec._wwino16 is None or spec._wwino16[0] != key or spec._wwino16[1].device != spec.w.device:
+    def build():
         K4, N, _ = spec.w.shape
         cin, nt = spec.Cin, spec.ntaps
         assert nt == 9 and cin % 64 == 0 and N % 64 == 0 and K4 * 4 == nt * cin, (cin, nt, K4, N)
         dev = spec.w.device
         # fp32 GEMM panel [K/4][N][4], k = ((c / 32) * 9 + tap) * 32 + c % 32  ->  w[tap][c][n]
         wk = spec.w.permute(0, 2, 1).reshape(cin // 32, nt, 32, N).permute(1, 0, 2, 3).reshape(nt, cin, N)
-        order = [0] * 9
-        for t in range(nt):
-            order[3 * (spec.dy[t] + 1) + spec.dx[t] + 1] = t
-        w33 = wk[order].reshape(3, 3, cin, N).to(torch.float64)                                    # [r][s][c][n], tap (dy, dx) = (r - 1, s - 1)
+        w33 = wk[_tap_order9(spec)].reshape(3, 3, cin, N).to(torch.float64)                        # [r][s][c][n], tap (dy, dx) = (r - 1, s - 1)
         G = torch.tensor(_WINO_G, dtype=torch.float64, device=dev)
         U = torch.einsum("ar,rscn,bs->abcn", G, w33, G)                                            # [xi][nu][c][n]
         bias = spec.bias
         if spade:
-            j = torch.arange(N, device=dev)
-            ch, beta = 4 * (j // 8) + j % 4, (j % 8) // 4
-            old = 64 * (ch // 32) + (ch % 32) + 32 * beta
+            old = _spade_columns(N, 4, dev)
             U = U[:, :, :, old]
             bias = None if bias is None else bias[old].contiguous()
-        panel = U.reshape(16, cin // 16, 16, N).permute(1, 0, 3, 2).contiguous().to(torch.bfloat16)   # [ks][p][n][e]
-        spec._wwino16 = (key, panel, bias)
-    return spec._wwino16[1], spec._wwino16[2]
+        return U.reshape(16, cin // 16, 16, N).permute(1, 0, 3, 2).contiguous().to(torch.bfloat16), bias   # [ks][p][n][e]
+    return _derived(spec, ("wwino16", bool(spade)), build, bias=True)
 
 
 BF16_HR = True          # lab switch: False routes every bf16 convolution to lwg_conv2d_nhwc_bf16 (LDS-DMA kernels)
@@ -239,27 +248,27 @@ def _pw_eligible(spec, x0, y, x1, epi, out_hw):
 
 def _w16c8(spec):
     """bf16 panel of lwg_conv2d_nhwc_c8_bf16: [ceil(ntaps/2)][N][16], k = tap*8 + c (the small-Cin K order of the fp32 panel)."""
-    if spec._w16c8 is None or spec._w16c8.device != spec.w.device:
+    def build():
         K4, N, _ = spec.w.shape
         nks = (spec.ntaps + 1) // 2
         wk = spec.w.permute(0, 2, 1).reshape(K4 * 4, N)
         if wk.shape[0] < nks * 16:
             wk = torch.cat([wk, wk.new_zeros(nks * 16 - wk.shape[0], N)], dim=0)
-        spec._w16c8 = wk[:nks * 16].reshape(nks, 16, N).permute(0, 2, 1).contiguous().to(torch.bfloat16)
-    return spec._w16c8
+        return wk[:nks * 16].reshape(nks, 16, N).permute(0, 2, 1).contiguous().to(torch.bfloat16)
+    return _derived(spec, "w16c8", build)
 
 
 def _w16x3(spec):
     """The three-plane bf16 panel [3][K/8][N][8] of a spec: w = hi + mid + lo exactly (round-to-nearest residual splits)."""
-    if spec._w16x3 is None or spec._w16x3.device != spec.w.device:
+    def build():
         K4, N, _ = spec.w.shape
         wk = spec.w.permute(0, 2, 1).reshape(K4 * 4, N)
         hi = wk.to(torch.bfloat16)
         r1 = wk - hi.float()
         mid = r1.to(torch.bfloat16)
         lo = (r1 - mid.float()).to(torch.bfloat16)
-        spec._w16x3 = torch.stack([hi, mid, lo]).view(3, K4 // 2, 8, N).permute(0, 1, 3, 2).contiguous()
-    return spec._w16x3
+        return torch.stack([hi, mid, lo]).view(3, K4 // 2, 8, N).permute(0, 1, 3, 2).contiguous()
+    return _derived(spec, "w16x3", build)
 
 
 _WINO_TAPS = sorted((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))
@@ -307,24 +316,26 @@ def _wwino(spec):
     """The transformed-weight fragment panel of lwg_conv2d_winograd_f32, built once per spec from the fp32 GEMM panel by ONE launch
     (lwg_winograd_panel_f32): U = G w G^T per (input, output) channel pair in fp64, rounded once, stored [16][Cin/8][2][N][4] - element
     (p, s, kh, n, kk) = U[p // 4][p % 4] of input channel 8 s + 2 kk + kh."""
-    if spec._wwino is None or spec._wwino.device != spec.w.device:
-        K4, N, _ = spec.w.shape
-        cin, nt = spec.Cin, spec.ntaps
-        assert nt == 9 and cin % 32 == 0 and K4 * 4 == nt * cin, (cin, nt, K4)
-        if not spec.w.is_cuda:
-            raise RuntimeError("ipercore_amd ops need CUDA (HIP) tensors: the MI355X path has no CPU fallback")
-        tap9 = (ctypes.c_int * 9)()
-        for t in range(nt):
-            tap9[3 * (spec.dy[t] + 1) + spec.dx[t] + 1] = t
+    def build():
+        cin, N, tap9 = _wino_panel_source(spec)
         if PANEL_CACHE is not None:                          # a training step: panels of registered weights are refreshed once per step
             U = PANEL_CACHE.winograd(spec, list(tap9))
             if U is not None:
-                spec._wwino = U
                 return U
         U = torch.empty(16, cin // 8, 2, N, 4, device=spec.w.device, dtype=torch.float32)
         _lib.check(_lib.lib().lwg_winograd_panel_f32(_ptr(spec.w), _ptr(U), cin, N, tap9, _stream()), "lwg_winograd_panel_f32")
-        spec._wwino = U
-    return spec._wwino
+        return U
+    return _derived(spec, "wwino", build)
+
+
+def _wino_panel_source(spec):
+    """(Cin, N, the tap order as the C array) of a 3x3 spec whose fp32 GEMM panel a panel-building launch may read."""
+    K4, N, _ = spec.w.shape
+    cin, nt = spec.Cin, spec.ntaps
+    assert nt == 9 and cin % 32 == 0 and K4 * 4 == nt * cin, (cin, nt, K4)
+    if not spec.w.is_cuda:
+        raise RuntimeError("ipercore_amd ops need CUDA (HIP) tensors: the MI355X path has no CPU fallback")
+    return cin, N, (ctypes.c_int * 9)(*_tap_order9(spec))
 
 
 WINO4 = True            # lab switch: in the "winograd" mode the synthesis path's eligible launches with Cin >= WINO4_MIN_CIN run the F(4x4, 3x3) kernel
@@ -335,25 +346,18 @@ def _wino4_use(spec, splitk):
     """Which launches of the "winograd" mode run lwg_conv2d_winograd4_f32 (F(4x4, 3x3): 2.25 multiplies per output instead of 4): a rule on the LAYER
     (its Cin), never on the batch - a frame's result must not depend on how many frames share its launch.  Training launches (splitk=True) keep the
     F(2x2, 3x3) kernel and its split plan."""
-    return WINO4 and not splitk and spec.Cin >= WINO4_MIN_CIN
+    return WINO4 and _MODE_WINO4 and not splitk and spec.Cin >= WINO4_MIN_CIN
 
 
 def _wwino4(spec):
     """The fragment panel of lwg_conv2d_winograd4_f32, built once per spec from the fp32 GEMM panel by ONE launch (lwg_winograd4_panel_f32):
     U = G w G^T (6 x 6) per (input, output) channel pair in fp64, rounded once, stored [4][Cin/8][4][2][9 N] (include/lwg_hip.h)."""
-    if spec._wwino4 is None or spec._wwino4.device != spec.w.device:
-        K4, N, _ = spec.w.shape
-        cin, nt = spec.Cin, spec.ntaps
-        assert nt == 9 and cin % 32 == 0 and K4 * 4 == nt * cin, (cin, nt, K4)
-        if not spec.w.is_cuda:
-            raise RuntimeError("ipercore_amd ops need CUDA (HIP) tensors: the MI355X path has no CPU fallback")
-        tap9 = (ctypes.c_int * 9)()
-        for t in range(nt):
-            tap9[3 * (spec.dy[t] + 1) + spec.dx[t] + 1] = t
+    def build():
+        cin, N, tap9 = _wino_panel_source(spec)
         U = torch.empty(4, cin // 8, 4, 2, 9 * N, device=spec.w.device, dtype=torch.float32)
         _lib.check(_lib.lib().lwg_winograd4_panel_f32(_ptr(spec.w), _ptr(U), cin, N, tap9, _stream()), "lwg_winograd4_panel_f32")
-        spec._wwino4 = U
-    return spec._wwino4
+        return U
+    return _derived(spec, "wwino4", build)
 
 
 SPADE_SKIP = True       # switch: the SPADE convolutions of the attention sites ("winograd" mode, fp32, F(4x4, 3x3) launches of the 8-wave form) run
@@ -558,32 +562,38 @@ def _wwino_t(specs):
     load time, like the packing itself): Upk[4][Cin/8][4][2][9 N] - per (parity 2 py + px, s, kk, kh) [N][4] products 0-3, [N][4] products 4-7, [N] product 8 -, product 3 xi + nu of column n = sgn (G g G^T)[xi][nu] for input
     channel 8 s + 2 kk + kh - g the parity's 2 x 2 sub-kernel in input-offset order, G = [[1,0],[1,1],[0,1]], formed in fp64 and rounded once; the
     sign (-1 where a parity-1 row / column takes the form the parity-0 one already holds negated) is documented in include/lwg_hip.h."""
-    s0 = specs[0]
-    U = s0._wwino_t
-    if U is not None and U.device == s0.w.device:
-        return U
-    Cin, N = s0.Cin, s0.N
-    G = torch.tensor([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=torch.float64, device=s0.w.device)
-    parts = []
+    def build():
+        Cin, N = specs[0].Cin, specs[0].N
+        G = torch.tensor([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=torch.float64, device=specs[0].w.device)
+        parts = []
+        for par, g in enumerate(_parity_subkernels(specs)):
+            u = torch.einsum("ar,rqcn,bq->abcn", G, g, G)                          # (3, 3, Cin, N)
+            if par >> 1:
+                u[0] = -u[0]
+            if par & 1:
+                u[:, 0] = -u[:, 0]
+            parts.append(u.reshape(9, Cin, N))
+        U9 = torch.stack(parts).float()                                              # (4, 9, Cin, N)
+        # per (parity, input channel): 9 N floats - [N][4] products 0-3, [N][4] products 4-7, [N] product 8 (every load of the kernel reads contiguous memory)
+        U = torch.cat([U9[:, 0:4].permute(0, 2, 3, 1).reshape(4, Cin, 4 * N), U9[:, 4:8].permute(0, 2, 3, 1).reshape(4, Cin, 4 * N), U9[:, 8]], dim=2)
+        return U.view(4, Cin // 8, 4, 2, 9 * N).contiguous()                         # c = 8 s + 2 kk + kh
+    return _derived(specs, "wwino_t", build)
+
+
+def _parity_subkernels(specs):
+    """The four parity GEMM panels of a ConvTranspose2d(4, 2, 1) as fp64 2 x 2 sub-kernels in input-offset order: per parity 2 py + px a tensor
+    g (2, 2, Cin, N), g[r][q] the weight that multiplies x[i + py - 1 + r][j + px - 1 + q]."""
+    Cin, N = specs[0].Cin, specs[0].N
+    out = []
     for par, sp in enumerate(specs):
         py, px = par >> 1, par & 1
         W = sp.w.double().permute(0, 2, 1).reshape(4 * Cin, N)                  # rows k = ((c / 32) 4 + tap) 32 + c % 32
         W = W.view(Cin // 32, 4, 32, N).permute(1, 0, 2, 3).reshape(4, Cin, N)  # [tap][c][n]
         g = torch.zeros(2, 2, Cin, N, dtype=torch.float64, device=W.device)
         for t, (dy, dx) in enumerate(zip(sp.dy, sp.dx)):
-            g[dy - (py - 1), dx - (px - 1)] = W[t]                               # g[r][q] multiplies x[i + py - 1 + r][j + px - 1 + q]
-        u = torch.einsum("ar,rqcn,bq->abcn", G, g, G)                          # (3, 3, Cin, N)
-        if py:
-            u[0] = -u[0]
-        if px:
-            u[:, 0] = -u[:, 0]
-        parts.append(u.reshape(9, Cin, N))
-    U9 = torch.stack(parts).float()                                              # (4, 9, Cin, N)
-    # per (parity, input channel): 9 N floats - [N][4] products 0-3, [N][4] products 4-7, [N] product 8 (every load of the kernel reads contiguous memory)
-    U = torch.cat([U9[:, 0:4].permute(0, 2, 3, 1).reshape(4, Cin, 4 * N), U9[:, 4:8].permute(0, 2, 3, 1).reshape(4, Cin, 4 * N), U9[:, 8]], dim=2)
-    U = U.view(4, Cin // 8, 4, 2, 9 * N).contiguous()                            # c = 8 s + 2 kk + kh
-    s0._wwino_t = U
-    return U
+            g[dy - (py - 1), dx - (px - 1)] = W[t]
+        out.append(g)
+    return out
 
 
 # F(4, 2) along the columns of the F(2x4, 2x2) kernel (csrc/convt_winograd24.hip): the points {0, 1, -1, 1/2, inf}, the scale factors of its data
@@ -597,31 +607,21 @@ def _wwino_t24(specs):
     [N] product 13, [N] product 14 (every load of the kernel reads contiguous memory).  Product 3 xi + nu (nu < 3) / 9 + 2 xi + nu - 3 (nu >= 3) of column n =
     sgn (G_y g G_x^T)[xi][nu] for input channel 8 s + 2 kk + kh, g the parity's 2 x 2 sub-kernel in input-offset order, G_y = [[1,0],[1,1],[0,1]],
     G_x = _G_X24, sgn = -1 for the parity-1 row form the parity-0 one already holds negated (xi = 0, py = 1); formed in fp64 and rounded once."""
-    s0 = specs[0]
-    U = s0._wwino_t24
-    if U is not None and U.device == s0.w.device:
-        return U
-    Cin, N = s0.Cin, s0.N
-    Gy = torch.tensor([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=torch.float64, device=s0.w.device)
-    Gx = torch.tensor(_G_X24, dtype=torch.float64, device=s0.w.device)
-    parts = []
-    for par, sp in enumerate(specs):
-        py, px = par >> 1, par & 1
-        W = sp.w.double().permute(0, 2, 1).reshape(4 * Cin, N)                  # rows k = ((c / 32) 4 + tap) 32 + c % 32
-        W = W.view(Cin // 32, 4, 32, N).permute(1, 0, 2, 3).reshape(4, Cin, N)  # [tap][c][n]
-        g = torch.zeros(2, 2, Cin, N, dtype=torch.float64, device=W.device)
-        for t, (dy, dx) in enumerate(zip(sp.dy, sp.dx)):
-            g[dy - (py - 1), dx - (px - 1)] = W[t]                               # g[r][q] multiplies x[i + py - 1 + r][j + px - 1 + q]
-        u = torch.einsum("ar,rqcn,bq->abcn", Gy, g, Gx)                        # (3, 5, Cin, N)
-        if py:
-            u[0] = -u[0]
-        parts.append(torch.cat([u[:, :3].reshape(9, Cin, N), u[:, 3:].reshape(6, Cin, N)]))
-    U15 = torch.stack(parts).float()                                             # (4, 15, Cin, N)
-    quad = lambda lo, hi: U15[:, lo:hi].permute(0, 2, 3, 1).reshape(4, Cin, (hi - lo) * N)     # noqa: E731
-    U = torch.cat([quad(0, 4), quad(4, 8), U15[:, 8], quad(9, 13), U15[:, 13], U15[:, 14]], dim=2)
-    U = U.view(4, Cin // 8, 4, 2, 15 * N).contiguous()                           # c = 8 s + 2 kk + kh
-    s0._wwino_t24 = U
-    return U
+    def build():
+        Cin, N = specs[0].Cin, specs[0].N
+        Gy = torch.tensor([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=torch.float64, device=specs[0].w.device)
+        Gx = torch.tensor(_G_X24, dtype=torch.float64, device=specs[0].w.device)
+        parts = []
+        for par, g in enumerate(_parity_subkernels(specs)):
+            u = torch.einsum("ar,rqcn,bq->abcn", Gy, g, Gx)                        # (3, 5, Cin, N)
+            if par >> 1:
+                u[0] = -u[0]
+            parts.append(torch.cat([u[:, :3].reshape(9, Cin, N), u[:, 3:].reshape(6, Cin, N)]))
+        U15 = torch.stack(parts).float()                                             # (4, 15, Cin, N)
+        quad = lambda lo, hi: U15[:, lo:hi].permute(0, 2, 3, 1).reshape(4, Cin, (hi - lo) * N)     # noqa: E731
+        U = torch.cat([quad(0, 4), quad(4, 8), U15[:, 8], quad(9, 13), U15[:, 13], U15[:, 14]], dim=2)
+        return U.view(4, Cin // 8, 4, 2, 15 * N).contiguous()                        # c = 8 s + 2 kk + kh
+    return _derived(specs, "wwino_t24", build)
 
 
 WINO_UP4_24 = True          # lab switch: the synthesis path's eligible transposed convolutions run the F(2x4, 2x2) kernel (False: F(2x2, 2x2))
@@ -646,6 +646,33 @@ class _FusedTransposeSpec(object):
         self.algo_kn, self.w = 4 * s0.algo_kn, panel
 
 
+def _fused_transpose_launch(a, s0, panel, entry, kind, sliced=True, extra=(), kernels=None):
+    """One launch = a whole transposed convolution (16 taps, 4 N output values per input pixel): ``entry(a, *extra, stream)`` of the library on
+    ``panel``, bracketed by the accounting hook with ONE pseudo-spec for the layer.  kernels: the closing hook call's launch count where the caller
+    knows it (else the C rule of ``_hook_end``; sliced=False: one launch at any batch size)."""
+    a.w = _ptr(panel, panel.dtype)
+    if CONV_HOOK is not None:
+        whole = _FusedTransposeSpec(s0, panel)
+        CONV_HOOK(True, a.M, whole, EPI_NONE, None)
+    _lib.check(getattr(_lib.lib(), entry)(a, *extra, _stream()), entry)
+    if CONV_HOOK is not None:
+        if kernels is None:
+            _hook_end(a, whole, EPI_NONE, kind, sliced)
+        else:
+            CONV_HOOK(False, a.M, whole, EPI_NONE, {"kernels": kernels, "kind": kind})
+
+
+def _w16up(specs):
+    """The panel of the fused bf16 transposed convolutions (lwg_conv_transpose4_nhwc_bf16, lwg_up4_head_compose_bf16): the four parity specs'
+    register-streamed panels (_w16hr) stacked, [parity][Cin/64 * 4][4][N][16] bf16."""
+    return _derived(specs, "w16up", lambda: torch.stack([_w16hr(s, False)[0] for s in specs]).contiguous())
+
+
+def _w32up(specs):
+    """The panel of lwg_conv_transpose4_nhwc_f32: the four parity specs' fp32 GEMM panels, flattened and stacked."""
+    return _derived(specs, "w32up", lambda: torch.stack([s.w.reshape(-1) for s in specs]).contiguous())
+
+
 def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=False):
     """y (B,2H,2W,N) <- ConvTranspose2d(4, 2, 1) of x (B,H,W,Cin) given its four parity specs (packing.pack_conv_transpose).
     bf16 activations with Cin <= 128: ONE launch (lwg_conv_transpose4_nhwc_bf16: the input block is staged once for the four
@@ -657,18 +684,7 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
     s0 = specs[0]
     if (BF16_UP4 and BF16_HR and x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and len(specs) == 4 and s0.Cin in (64, 128)
             and s0.N % 64 == 0 and all(s.ntaps == 4 and s.omul == 2 and (s.ooy, s.oox) == (i >> 1, i & 1) for i, s in enumerate(specs))):
-        a = conv_args(x, s0, y, act=act)
-        panel = getattr(s0, "_w16up", None)
-        if panel is None or panel.device != s0.w.device:
-            panel = torch.stack([_w16hr(s, False)[0] for s in specs]).contiguous()
-            s0._w16up = panel
-        a.w = _ptr(panel, torch.bfloat16)
-        if CONV_HOOK is not None:                # one launch = the whole transposed convolution: 16 taps, 4 N output values per input pixel
-            whole = _FusedTransposeSpec(s0, panel)
-            CONV_HOOK(True, a.M, whole, EPI_NONE, None)
-        _lib.check(_lib.lib().lwg_conv_transpose4_nhwc_bf16(a, _stream()), "lwg_conv_transpose4_nhwc_bf16")
-        if CONV_HOOK is not None:
-            _hook_end(a, whole, EPI_NONE, "up4")
+        _fused_transpose_launch(conv_args(x, s0, y, act=act), s0, _w16up(specs), "lwg_conv_transpose4_nhwc_bf16", "up4")
         return y
     if (WINO_UP4 and CONV_PRECISION == "winograd" and not splitk and out_hw is None and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32
             and s0.Cin % 32 == 0 and s0.N % 32 == 0 and _parity_specs_ok(specs)):
@@ -676,18 +692,10 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
         # of 64; per-image work in a fixed order: a frame does not depend on its batch).  Training callers (splitk=True) keep the direct forms.
         # Images of >= WINO_UP4_24_MIN_HW input pixels: F(2x4, 2x2) (60 products per 2 x 4 input patch instead of 72).
         a = conv_args(x, s0, y, act=act, q4=q4)
-        f24 = _up4_24(x)
-        panel = _wwino_t24(specs) if f24 else _wwino_t(specs)
-        a.w = _ptr(panel)
-        if CONV_HOOK is not None:
-            whole = _FusedTransposeSpec(s0, panel)
-            CONV_HOOK(True, a.M, whole, EPI_NONE, None)
-        if f24:
-            _lib.check(_lib.lib().lwg_conv_transpose4_winograd24_f32(a, _stream()), "lwg_conv_transpose4_winograd24_f32")
+        if _up4_24(x):
+            _fused_transpose_launch(a, s0, _wwino_t24(specs), "lwg_conv_transpose4_winograd24_f32", "winograd_up4", False)
         else:
-            _lib.check(_lib.lib().lwg_conv_transpose4_winograd_f32(a, _stream()), "lwg_conv_transpose4_winograd_f32")
-        if CONV_HOOK is not None:
-            _hook_end(a, whole, EPI_NONE, "winograd_up4", False)
+            _fused_transpose_launch(a, s0, _wwino_t(specs), "lwg_conv_transpose4_winograd_f32", "winograd_up4", False)
         return y
     if (F32_UP4 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION in ("fp32", "winograd") and s0.Cin % 32 == 0
             and _parity_specs_ok(specs)):
@@ -696,17 +704,7 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
         # values are those of the four conv2d calls bit for bit (same tiles, same K order).
         a = conv_args(x, s0, y, act=act, q4=q4)
         if _lib.lib().lwg_conv_transpose4_is_one_grid(a):
-            panel = getattr(s0, "_w32up", None)
-            if panel is None or panel.device != s0.w.device:
-                panel = torch.stack([s.w.reshape(-1) for s in specs]).contiguous()
-                s0._w32up = panel
-            a.w = _ptr(panel)
-            if CONV_HOOK is not None:
-                whole = _FusedTransposeSpec(s0, panel)
-                CONV_HOOK(True, a.M, whole, EPI_NONE, None)
-            _lib.check(_lib.lib().lwg_conv_transpose4_nhwc_f32(a, _stream()), "lwg_conv_transpose4_nhwc_f32")
-            if CONV_HOOK is not None:
-                _hook_end(a, whole, EPI_NONE, "up4")
+            _fused_transpose_launch(a, s0, _w32up(specs), "lwg_conv_transpose4_nhwc_f32", "up4")
             return y
     for s in specs:
         conv2d(x, s, y, act=act, splitk=splitk, out_hw=None if out_hw is None else out_hw(s), q4=q4)
@@ -997,19 +995,11 @@ def up4_head_compose_bf16(x, specs, head16, bg, want_pred=True, want_mask=True, 
         bstride = 3 * S2h * S2w
     # the layer's output does not exist: a zero-batch tensor gives the launch description its geometry
     a = conv_args(x, s0, torch.empty(0, S2h, S2w, s0.N, device=dev, dtype=torch.bfloat16), act=ACT_RELU, out_hw=(H, W))
-    panel = getattr(s0, "_w16up", None)
-    if panel is None or panel.device != s0.w.device:
-        panel = torch.stack([_w16hr(s, False)[0] for s in specs]).contiguous()
-        s0._w16up = panel
-    a.w = _ptr(panel, torch.bfloat16)
-    if CONV_HOOK is not None:          # accounted as the transposed convolution it contains (16 taps, 4 N outputs per input pixel) + nothing for the head (as before)
-        whole = _FusedTransposeSpec(s0, panel)
-        CONV_HOOK(True, a.M, whole, EPI_NONE, None)
-    _lib.check(_lib.lib().lwg_up4_head_compose_bf16(a, _ptr(head16, torch.bfloat16), _ptr(bg), bstride, _ptr(pred), _ptr(mask), _ptr(img), _stream()),
-               "lwg_up4_head_compose_bf16")
-    if CONV_HOOK is not None:
-        per = H * W * 256
-        CONV_HOOK(False, a.M, whole, EPI_NONE, {"kernels": max(1, -(-B // max(1, (0xC0000000 - 1) // per))), "kind": "up4_head"})
+    # accounted as the transposed convolution it contains (16 taps, 4 N outputs per input pixel) + nothing for the head (as before)
+    per = H * W * 256
+    _fused_transpose_launch(a, s0, _w16up(specs), "lwg_up4_head_compose_bf16", "up4_head",
+                            extra=(_ptr(head16, torch.bfloat16), _ptr(bg), bstride, _ptr(pred), _ptr(mask), _ptr(img)),
+                            kernels=max(1, -(-B // max(1, (0xC0000000 - 1) // per))))
     return pred, mask, img
 
 

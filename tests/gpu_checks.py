@@ -1306,7 +1306,7 @@ def check_bf16_up4_head():
         assert out[tag]["pred_vs_fp64_max"] <= 2e-2, (tag, out[tag])          # (an fp32-vs-fp64 sum that rounds to the other bf16 neighbour moves a pre-activation by 2^-9 of it)
     # the contract: what the kernel does not take is refused before any launch
     a = ops.conv_args(xd, specs[0], torch.empty(0, 2 * H, 2 * W, 64, device=DEV, dtype=torch.bfloat16), act=ops.ACT_RELU, out_hw=(H, W))
-    a.w = ops._ptr(specs[0]._w16up, torch.bfloat16)
+    a.w = ops._ptr(ops._w16up(specs), torch.bfloat16)
     hp = ops._ptr(head16, torch.bfloat16)
     pp = ops._ptr(p1)
     for field, val in (("C0", 64), ("N", 128), ("act", ops.ACT_NONE), ("ntaps", 9), ("omul", 1)):

@@ -298,7 +298,7 @@ def test_fused_transpose_dispatch_and_flow_cache(monkeypatch):
     assert calls == [("fused", 4)]
     assert hooked == [(True, 128, 256, 16, 4 * specs128[0].algo_kn), (False, 128, 256, 16, 4 * specs128[0].algo_kn)]
     assert infos == [None, {"kernels": 1, "kind": "up4"}]          # the closing call says what ran: launches behind the call, kernel family
-    assert specs128[0]._w16up.shape == (4, 2 * 4, 4, 64, 16)                   # [parity][Cin/64 * taps][ks][N][16]
+    assert ops._w16up(specs128).shape == (4, 2 * 4, 4, 64, 16)                   # [parity][Cin/64 * taps][ks][N][16]
 
     calls.clear()
     specs256 = packing.pack_conv_transpose(_w((256, 128, 4, 4), 21), torch.zeros(128))
@@ -317,6 +317,54 @@ def test_fused_transpose_dispatch_and_flow_cache(monkeypatch):
     c = sc.flow(T, 32, 32)
     assert a is b and a.shape == (2, 2, 16, 16, 2) and c.shape == (2, 2, 32, 32, 2) and resized == [(16, 16), (32, 32)]
     assert sc.flow(T, 64, 64) is T and sc.flow(T, 16, 32) is T                # same size / non-square: passed through
+
+
+@pytest.mark.parametrize("name,cin,n", [("_wwino_t", 32, 32), ("_wwino_t24", 32, 32), ("_w16up", 64, 64), ("_w32up", 64, 64)])
+def test_parity_panels_follow_all_four_sources(name, cin, n):
+    """A panel built from the four parity specs is cached on specs[0] but valid only while EVERY spec's ``w`` is the tensor it was built from:
+    replacing specs[2].w gives a new panel, equal to the one fresh specs with those weights give; packing.spec_to leaves a correct panel."""
+    build = getattr(ops, name)
+    w, w2, b = _w((cin, n, 4, 4), 30), _w((cin, n, 4, 4), 31), _w((n,), 32)
+    specs = packing.pack_conv_transpose(w, b)
+    U = build(specs)
+    assert build(specs) is U
+    specs[2].w = packing.pack_conv_transpose(w2, b)[2].w
+    assert specs[2].w.shape == specs[0].w.shape
+    U2 = build(specs)
+    fresh = packing.pack_conv_transpose(w, b)
+    fresh[2] = packing.pack_conv_transpose(w2, b)[2]
+    assert U2 is not U and not torch.equal(U2, U) and torch.equal(U2, build(fresh))
+    assert build(specs) is U2
+    for s in specs:
+        packing.spec_to(s, s.w.device)
+    assert torch.equal(build(specs), build(fresh))
+
+
+def test_precision_mode_leaves_the_lab_switch_alone():
+    """conv_precision selects the engine through its own flag: "winograd" inside "winograd2x2" runs the F(4x4, 3x3) kernel again, and the lab
+    switch ops.WINO4 is neither written by a context nor restored by one."""
+    spec64 = packing.pack_conv(torch.zeros(64, 64, 3, 3), None, stride=1, pad=1)
+    prev = ops.WINO4
+    try:
+        assert ops.WINO4 and ops._wino4_use(spec64, False)
+        with ops.conv_precision("winograd2x2"):
+            assert ops.CONV_PRECISION == "winograd" and ops.WINO4 and not ops._wino4_use(spec64, False)
+            with ops.conv_precision("winograd"):
+                assert ops._wino4_use(spec64, False)
+            assert not ops._wino4_use(spec64, False)
+        assert ops._wino4_use(spec64, False)
+        ops.WINO4 = False
+        with ops.conv_precision("winograd"):
+            assert not ops._wino4_use(spec64, False)
+        assert ops.WINO4 is False
+        with ops.conv_precision("winograd"):
+            ops.WINO4 = True                             # a lab setting made inside a context survives the exit
+        assert ops.WINO4 is True
+        with ops.conv_precision("winograd2x2"):
+            ops.WINO4 = False
+        assert ops.WINO4 is False
+    finally:
+        ops.WINO4 = prev
 
 
 def test_winograd_panel_and_eligibility():

@@ -55,7 +55,7 @@ def test_panel_layout(cin, n):
     got = flat[ops.wwino16_index(ks, p, nn, e, n)]                                               # EVERY element through the documented formula
     assert torch.equal(got, want[p // 4, p % 4, 16 * ks + e, nn])
     assert ops._wwino16(spec, False)[0] is panel                                                 # cached
-    assert spec._wwino16 is not None and spec._w16hr is None
+    assert set(spec._panels) == {("wwino16", False)}                                             # this panel and no other engine's
 
 
 def test_panel_spade_interleave():
@@ -73,8 +73,13 @@ def test_panel_spade_interleave():
         assert torch.equal(col, want), j
         assert bias[j] == (bb if beta else bg)[ch]
     assert ops._wwino16(spec, True)[0] is panel
-    plain, _ = ops._wwino16(spec, False)                                                         # the other key rebuilds
+    plain, _ = ops._wwino16(spec, False)                                                         # the other key: its own panel
     assert plain is not panel and not torch.equal(plain, panel)
+    assert ops._wwino16(spec, True)[0] is panel and ops._wwino16(spec, False)[0] is plain        # the variants coexist on the spec
+    hr, hr_bias = ops._w16hr(spec, True)
+    hr_plain, _ = ops._w16hr(spec, False)
+    assert hr_plain is not hr and not torch.equal(hr_plain, hr)
+    assert ops._w16hr(spec, True)[0] is hr and ops._w16hr(spec, True)[1] is hr_bias and ops._w16hr(spec, False)[0] is hr_plain
 
 
 def test_mode_plumbing():

@@ -182,4 +182,4 @@ def test_winograd24_dispatch(monkeypatch):
         monkeypatch.setattr(ops, "WINO_UP4_24", False)
         ops.conv_transpose2d(torch.zeros(1, 64, 64, 32).as_subclass(_Cuda), specs, torch.zeros(1, 128, 128, 32))
         assert calls[-1] == "f22"
-    assert specs[0]._wwino_t24.shape == (4, 4, 4, 2, 15 * 32) and specs[0]._wwino_t.shape == (4, 4, 4, 2, 9 * 32)
+    assert ops._wwino_t24(specs).shape == (4, 4, 4, 2, 15 * 32) and ops._wwino_t(specs).shape == (4, 4, 4, 2, 9 * 32)

@@ -430,10 +430,10 @@ def _convt_direct(x, specs, y, ycoff, act):
     a = ops.conv_args(x, specs[0], y, act=act)
     a.ycoff = ycoff
     if x.dtype == torch.bfloat16:
-        panel = torch.stack([ops._w16hr(s, False)[0] for s in specs]).contiguous()
+        panel = ops._w16up(specs)
         a.w = ops._ptr(panel, torch.bfloat16)
         return _lib.lib().lwg_conv_transpose4_nhwc_bf16(a, ops._stream()), a, panel
-    panel = torch.stack([s.w.reshape(-1) for s in specs]).contiguous()
+    panel = ops._w32up(specs)
     a.w = ops._ptr(panel)
     return _lib.lib().lwg_conv_transpose4_nhwc_f32(a, ops._stream()), a, panel
 

@@ -20,7 +20,7 @@ y = torch.empty(B, 2 * H, 2 * H, N, device=dev, dtype=BF)
 for _ in range(3):
     ops.conv_transpose2d(x, specs, y, act=ops.ACT_RELU)
 a = ops.conv_args(x, specs[0], y, act=ops.ACT_RELU)
-panel = torch.stack([ops._w16hr(s, False)[0] for s in specs]).contiguous()
+panel = ops._w16up(specs)
 a.w = ops._ptr(panel, BF)
 tiles = B * (H // 8) * (H // 16)
 ts = torch.zeros(tiles, 12, dtype=torch.int64, device=dev)
