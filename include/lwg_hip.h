@@ -188,6 +188,31 @@ int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, con
  * C -> C with C in {64, 128, 256}, no second input, LWG_EPI_NONE): the weights stay in registers and persistent workgroups
  * stream the rows - same panel layout with one step per 64-channel chunk. */
 int lwg_conv2d_nhwc_bf16_hr(const LwgConvArgs* args, lwg_stream_t stream);
+/* The 3 x 3 launch of lwg_conv2d_nhwc_bf16_hr driven by the SUB-TILE lists of lwg_spade_skip_fine_lists_f32 (csrc/conv_igemm_bf16.hip,
+ * csrc/lwg_bf16_hr_list.h) - the bf16 engine's form of lwg_conv2d_winograd4_fine_f32.  The kernel's 8-row x 16-column pixel block is
+ * exactly one 16 x 8 sub-tile: lists->heavy / light / counts are fheavy / flight / fcounts as the classifier leaves them in DEVICE memory (int ids in
+ * ascending order; the host never reads them), built with the window reach d of the DIRECT kernel - an output pixel depends on its own 3 x 3 window, so
+ * d = 1 for a convolution of the attention output and d = 2 for the convolution behind it.  One workgroup per (in-image sub-tile, 128 output columns):
+ * heavy sub-tiles run the prologue, K loop and epilogue of lwg_conv2d_nhwc_bf16_hr unchanged, light sub-tiles are filled from lists->cal, sub-tiles in
+ * neither list are left alone.  lists->cal (declared const float*, the element type follows the epilogue):
+ *   LWG_EPI_NONE   bf16, (1, H, W, YC): the OUTPUT of the same launch (same panel, bias, activation, ycoff) on the all-background frame; copied;
+ *   LWG_EPI_SPADE  fp32, (1, H, W, N): the ACCUMULATORS of the same convolution of the all-background frame as lwg_conv2d_nhwc_bf16_hr_acc writes them
+ *                  (the SPADE epilogue consumes fp32 accumulators and rounds once: a bf16 frame would lose bits) - per pixel the N panel columns,
+ *                  each 32-column tile stored [h][r], h = 0, 1, r = 0..15 = column 8 (r / 4) + 4 h + r % 4 of the tile; modulated with the
+ *                  frame's own xn / mean / rstd by the heavy path's epilogue code.
+ * Bitwise the result of lwg_conv2d_nhwc_bf16_hr wherever every light sub-tile's input window (the sub-tile grown by one pixel) equals the
+ * all-background frame's.  Contract (lwg_conv2d_nhwc_bf16_hr_list_applies: 1 if the SHAPES meet it, 0 otherwise and for NULL; no pointer is read):
+ * xdt = ydt = LWG_DT_BF16, one input (C1 = 0, C0 % 64 == 0), nine taps = the 3 x 3 grid ascending in (dy, dx), stride = omul = 1, OH = YH = H,
+ * OW = YW = W, ooy = oox = 0, M = B H W, N % 128 == 0, YC % 8 == 0, ycoff % 8 == 0; LWG_EPI_NONE (ycoff + N <= YC) or LWG_EPI_SPADE (N = 2 YC,
+ * ycoff = 0, columns as for lwg_conv2d_nhwc_bf16_hr).  The input is addressed per IMAGE, never in batch slices: any batch in ONE launch, one image
+ * (H W C0 2 bytes) and the panel below 3 GiB - larger is refused.  Everything is validated on the host: lwg_conv2d_nhwc_bf16_hr_list returns
+ * hipErrorInvalidValue (1) before any launch for a NULL argument, list or needed tensor pointer, or a shape outside the contract. */
+int lwg_conv2d_nhwc_bf16_hr_list(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
+int lwg_conv2d_nhwc_bf16_hr_list_applies(const LwgConvArgs* args);
+/* The calibration path of that kernel: the same K loop on a launch of the contract above with LWG_EPI_NONE, LWG_ACTIVATION_NONE, ydt = LWG_DT_F32,
+ * YC = N, ycoff = 0; args->y receives B * H * W * N floats - the raw accumulators (no bias, no activation, no rounding) in the layout lists->cal of
+ * an LWG_EPI_SPADE list launch has.  The whole batch is one buffer (B H W C0 2 bytes below 3 GiB; the calibration has B = 1). */
+int lwg_conv2d_nhwc_bf16_hr_acc(const LwgConvArgs* args, lwg_stream_t stream);
 /* The 3 x 3 subset of the launches above (nine taps, stride = omul = 1, pad 1, OH = YH = H, OW = YW = W, ooy = oox = 0) as a fused F(2x2, 3x3)
  * Winograd convolution on the bf16 matrix pipe (csrc/conv_winograd_bf16.hip; ops.conv_precision("bf16_winograd")): 4 multiplies per output instead
  * of 9.  xdt = ydt = LWG_DT_BF16; one input or a skip concatenation (C0 % 64 == 0 and x1 given when C1 > 0); Cin % 64 == 0, N % 64 == 0,

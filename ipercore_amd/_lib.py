@@ -78,6 +78,9 @@ _SIGS = {
     "lwg_spade_skip_fine_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "lwg_winograd4_panel_f32": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_f]),
     "lwg_conv2d_nhwc_bf16_hr": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
+    "lwg_conv2d_nhwc_bf16_hr_list": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
+    "lwg_conv2d_nhwc_bf16_hr_list_applies": (c_i, [ctypes.POINTER(LwgConvArgs)]),
+    "lwg_conv2d_nhwc_bf16_hr_acc": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
     "lwg_conv2d_winograd_bf16": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
     "lwg_conv2d_nhwc_c8_bf16": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
     "lwg_conv_transpose4_nhwc_bf16": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),

@@ -27,6 +27,7 @@
 #define LWG_BF16_NT_ST 0     // lab: the epilogue's 16-byte output stores non-temporal (worth 0.5 % in conv_winograd4.hip)
 #endif
 #include "lwg_conv_slices.h"
+#include "lwg_bf16_hr_list.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -54,7 +55,7 @@ __device__ __forceinline__ float lwg_bf16_hi(unsigned u) { return __builtin_bit_
 // (lwg_common.h, LwgActC: a runtime code inside the innermost loops costs a uniform branch ladder per group of outputs).
 // pre (halo-tile kernels only; nullptr: read from global memory here): the workgroup's epilogue operands parked in LDS by the kernel's prologue -
 // [0, BN): bias of columns n_base ..; SPADE: [BN, BN + BN/2) mean, [BN + BN/2, 2 BN) rstd of image tb, channels n_base / 2 ..
-template <int TM, int TN, int EPI, int SPATIAL, int EA>
+template <int TM, int TN, int EPI, int SPATIAL, int EA, int TAG = 0>
 __device__ __forceinline__ void lwg_bf16_epilogue_a(const LwgConvArgs& a, floatx16 (&acc)[TM][TN], int m_base, int n_base, int wm, int wn,
                                                     int lane, int tb, int ty0, int tx0, const float* pre = nullptr, int pre_bn = 0) {
     const int khalf = lane >> 5;
@@ -312,12 +313,13 @@ __device__ __forceinline__ void lwg_bf16_epilogue_a(const LwgConvArgs& a, floatx
     }
 }
 
-template <int TM, int TN, int EPI, int SPATIAL = 0>
+// TAG: nothing but a separate instantiation of the same code for a caller that wants one (hr2_light below)
+template <int TM, int TN, int EPI, int SPATIAL = 0, int TAG = 0>
 __device__ __forceinline__ void lwg_bf16_epilogue(const LwgConvArgs& a, floatx16 (&acc)[TM][TN], int m_base, int n_base, int wm, int wn,
                                                   int lane, int tb = 0, int ty0 = 0, int tx0 = 0, const float* pre = nullptr, int pre_bn = 0) {
-    if (a.act == LWG_ACT_RELU) lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, LWG_ACT_RELU>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
-    else if (a.act == LWG_ACT_NONE) lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, LWG_ACT_NONE>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
-    else lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, -1>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
+    if (a.act == LWG_ACT_RELU) lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, LWG_ACT_RELU, TAG>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
+    else if (a.act == LWG_ACT_NONE) lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, LWG_ACT_NONE, TAG>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
+    else lwg_bf16_epilogue_a<TM, TN, EPI, SPATIAL, -1, TAG>(a, acc, m_base, n_base, wm, wn, lane, tb, ty0, tx0, pre, pre_bn);
 }
 
 template <int WAVES_M, int WAVES_N, int TM, int TN, int EPI, bool DMA_A>
@@ -543,8 +545,92 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, WAVES_M * WAVES_N == 4 ? 2 
 #define LWG_HALO_PIECES 23                 // 8 pixels per DMA piece; the 23rd is half used
 #define LWG_HALO_BYTES (LWG_HALO_PIECES * 1024)
 
-template <int NDY, int NDX, int EPI, int WAVES_M>
-__global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void lwg_conv_bf16_hr2_kernel(const LwgConvArgs a) {
+// the epilogue's operands (bias; SPADE: mean / rstd of this image) parked in LDS behind the halo buffers, as the kernel below parks them before its K
+// loop - here for a workgroup that has none (hr2_light).  (The kernel keeps its own copy of these lines, and the light path its own instantiation of
+// the epilogue template: shared, the plain instantiations' code changed - flat loads in the SPADE epilogue; profiles/spade_skip_bf16_isa.txt.)
+template <int EPI, int BN>
+__device__ __forceinline__ void hr2_park_pre(const LwgConvArgs& a, float* pre, int tid, int tb, int n_base) {
+    if (tid < BN) pre[tid] = a.bias ? a.bias[n_base + tid] : 0.f;
+    if (EPI == LWG_EPI_SPADE && tid < BN) {
+        const int c = (n_base >> 1) + (tid & (BN / 2 - 1));
+        pre[BN + tid] = tid < BN / 2 ? a.mean[(size_t)tb * a.YC + c] : a.rstd[(size_t)tb * a.YC + c];
+    }
+}
+
+// A light sub-tile of the list form (HR2_LIST below): what the K loop would compute is in the calibration frame at the block's own position.
+//   LWG_EPI_NONE: sk.cal = the bf16 output frame (1, H, W, YC) of the same launch on the all-background input - bias, activation and rounding are
+// in it; the block's channels [ycoff + n_base, + 128) copied, every lane the 2 x 16 bytes per row tile that the epilogue would store.  No barrier.
+//   LWG_EPI_SPADE: sk.cal = the fp32 accumulator frame (1, H, W, N) (hrl_acc_offset): the lane's accumulator tile in four 16-byte loads per row
+// tile, then the heavy path's epilogue with this image's xn / mean / rstd - one barrier (the parked operands), as the heavy path has before its exit.
+template <int EPI>
+__device__ __forceinline__ void hr2_light(const LwgConvArgs& a, const LwgConvLists& sk, char* smem, int tid, int lane, int wn, int tb, int x0, int y0,
+                                          int n_base) {
+    const int khalf = lane >> 5;
+    bool live[HRL_TM];
+    int oy[HRL_TM], ox[HRL_TM];
+#pragma unroll
+    for (int i = 0; i < HRL_TM; ++i) {
+        int py, px;
+        hrl_lane_pixel(lane, i, py, px);
+        oy[i] = y0 + py, ox[i] = x0 + px;
+        live[i] = oy[i] < a.OH && ox[i] < a.OW;
+    }
+    if constexpr (EPI == LWG_EPI_NONE) {
+        const __bf16* const cal = reinterpret_cast<const __bf16*>(sk.cal);
+        __bf16* const yb = reinterpret_cast<__bf16*>(a.y) + (size_t)tb * a.OH * a.OW * a.YC;
+        uintx4 v[HRL_TM][2];
+        size_t off[HRL_TM];
+#pragma unroll
+        for (int i = 0; i < HRL_TM; ++i) {                   // (dead lanes: the frame's first bytes, never stored)
+            off[i] = live[i] ? hrl_copy_offset(oy[i], ox[i], a.OW, a.YC, a.ycoff + n_base + wn * 32, khalf) : 0;
+            v[i][0] = *reinterpret_cast<const uintx4*>(cal + off[i]);
+            v[i][1] = *reinterpret_cast<const uintx4*>(cal + off[i] + 8);
+        }
+#pragma unroll
+        for (int i = 0; i < HRL_TM; ++i)
+            if (live[i]) {
+                *reinterpret_cast<uintx4*>(yb + off[i]) = v[i][0];
+                *reinterpret_cast<uintx4*>(yb + off[i] + 8) = v[i][1];
+            }
+    } else {
+        float* const pre = reinterpret_cast<float*>(smem + 2 * LWG_HALO_BYTES);
+        hr2_park_pre<EPI, HRL_BN>(a, pre, tid, tb, n_base);
+        floatx16 acc[HRL_TM][1];
+#pragma unroll
+        for (int i = 0; i < HRL_TM; ++i) {
+            const floatx4* const p = reinterpret_cast<const floatx4*>(sk.cal + (live[i] ? hrl_acc_offset(oy[i], ox[i], a.OW, a.N, n_base + wn * 32, khalf) : 0));
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const floatx4 q = p[g];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[i][0][4 * g + c] = q[c];
+            }
+        }
+        __syncthreads();
+        lwg_bf16_epilogue<HRL_TM, 1, EPI, 2, 1>(a, acc, 0, n_base, 0, wn, lane, tb, y0, x0, pre, HRL_BN);
+    }
+}
+
+// MODE (one kernel template; the list form's extra argument is a parameter pack that is EMPTY in the other modes, so the plain instantiations keep the
+// signature, the instruction stream and the register counts they had as a kernel of their own - profiles/spade_skip_bf16_isa.txt):
+//   HR2_PLAIN  the launch described above: one workgroup per (image, 8 x 16 block, column tile) in row-major order;
+//   HR2_LIST   lwg_conv2d_nhwc_bf16_hr_list (lwg_bf16_hr_list.h holds the id arithmetic): the block is a 16 x 8 SUB-TILE of the
+//              lists of lwg_spade_skip_fine_lists_f32.  Workgroup lid = (entry e = lid / tiles_n, column tile lid % tiles_n): e < counts[0] - heavy
+//              sub-tile heavy[e], the prologue, K loop and epilogue below unchanged; e - counts[0] < counts[1] - light sub-tile light[e - counts[0]]:
+//              no halo, no weights, no K loop.  LWG_EPI_NONE: the bf16 calibration frame's block copied (16-byte accesses, no barrier);
+//              LWG_EPI_SPADE: the accumulator tile loaded from the fp32 accumulator frame (HR2_ACC wrote it) and handed to the SAME epilogue
+//              with the same parked operands.  Anything else exits; counts[0] = every sub-tile: the plain tile order.  The tile id comes out of
+//              memory, so it and what is derived from it go through readfirstlane (no waterfall loops around the buffer operations).  The input
+//              is one buffer PER IMAGE (base x + tb H W C 2, range one image): a device-resident list cannot be cut into batch slices;
+//   HR2_ACC    lwg_conv2d_nhwc_bf16_hr_acc: the plain launch with the accumulators stored as fp32 (lwg_bf16_hr_list.h: hrl_acc_offset) - no
+//              bias, no activation, no rounding: the calibration frame of the gamma | beta convolution (B = 1, once per weight version).
+enum { HR2_PLAIN = 0, HR2_LIST = 1, HR2_ACC = 2 };
+
+__device__ __forceinline__ const LwgConvLists& hr2_lists(const LwgConvLists& sk) { return sk; }
+
+template <int NDY, int NDX, int EPI, int WAVES_M, int MODE = HR2_PLAIN, class... SK>
+__global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void lwg_conv_bf16_hr2_kernel(const LwgConvArgs a, const SK... sk_) {
+    static_assert(sizeof...(SK) == (MODE == HR2_LIST ? 1 : 0), "the lists: the list form's argument only");
     constexpr int NTAPS = NDY * NDX;
     constexpr int WAVES_N = 4 / WAVES_M, TM = 4 / WAVES_M, BN = WAVES_N * 32;
     constexpr int NE = TM + NDY - 1;                         // fragments per (tap column, k-step)
@@ -564,20 +650,53 @@ __global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void
     const int tiles_n = a.N / BN;
     const int tiles_x = (a.OW + 15) >> 4, tiles_y = (a.OH + 7) >> 3;
     const int lid = lwg_xcd_remap(blockIdx.x, gridDim.x);
-    const int tile_n = lid % tiles_n;
-    int rest = lid / tiles_n;
-    const int tix = rest % tiles_x;
-    rest /= tiles_x;
-    const int tiy = rest % tiles_y, tb = rest / tiles_y;
-    const int x0 = tix * 16, y0 = tiy * 8;
+    int tile_n, tb, x0, y0;
+    bool light = false;
+    if constexpr (MODE == HR2_LIST) {
+        static_assert(WAVES_M == 1 && NDY == 3 && NDX == 3 && (EPI == LWG_EPI_NONE || EPI == LWG_EPI_SPADE), "the list form: what the SPADE launches reach");
+        static_assert(BN == HRL_BN && TM == HRL_TM && CW4F_SX == 16 && CW4F_SY == 8, "the workgroup's pixel block is the classifier's sub-tile");
+        const LwgConvLists& sk = hr2_lists(sk_...);
+        const int total = cw4f_in_image_total(a.B, a.OH, a.OW);
+        int e, nh, nl, idx;
+        hrl_entry(lid, tiles_n, e, tile_n);
+        hrl_counts(__builtin_amdgcn_readfirstlane(sk.counts[0]), __builtin_amdgcn_readfirstlane(sk.counts[1]), total, nh, nl);
+        const int kind = hrl_kind(e, nh, nl, idx);
+        if (kind == HRL_EXIT) return;
+        if (nh >= total) {                                   // nothing is light: the plain kernel's tile order
+            hrl_plain_corner(e, a.OH, a.OW, tb, x0, y0);
+        } else {
+            const int u = __builtin_amdgcn_readfirstlane(kind == HRL_HEAVY ? sk.heavy[idx] : sk.light[idx]);
+            if (!hrl_locate(u, a.B, a.OH, a.OW, tb, x0, y0)) return;
+        }
+        tile_n = __builtin_amdgcn_readfirstlane(tile_n), tb = __builtin_amdgcn_readfirstlane(tb);
+        x0 = __builtin_amdgcn_readfirstlane(x0), y0 = __builtin_amdgcn_readfirstlane(y0);
+        light = kind == HRL_LIGHT;
+    } else {
+        tile_n = lid % tiles_n;
+        int rest = lid / tiles_n;
+        const int tix = rest % tiles_x;
+        rest /= tiles_x;
+        const int tiy = rest % tiles_y;
+        tb = rest / tiles_y;
+        x0 = tix * 16, y0 = tiy * 8;
+    }
     const int n_base = tile_n * BN;
+
+    if constexpr (MODE == HR2_LIST) {
+        if (light) {
+            hr2_light<EPI>(a, hr2_lists(sk_...), smem_r2, tid, lane, wn, tb, x0, y0, n_base);
+            return;
+        }
+    }
 
     const int Cin = a.C0 + a.C1;
     const int nchunks = Cin >> 6;
     const int nfrags = nchunks * FPC;
-    const unsigned bytes0 = (unsigned)a.B * a.H * a.W * a.C0 * 2u;
-    const unsigned bytes1 = (unsigned)a.B * a.H * a.W * a.C1 * 2u;
+    // HR2_LIST: image tb of the input is the buffer (the host holds ONE image below the marker, any batch)
+    const unsigned bytes0 = (unsigned)(MODE == HR2_LIST ? 1 : a.B) * a.H * a.W * a.C0 * 2u;
+    const unsigned bytes1 = (unsigned)(MODE == HR2_LIST ? 1 : a.B) * a.H * a.W * a.C1 * 2u;
     const unsigned wbytes = (unsigned)nchunks * NTAPS * (unsigned)a.N * 128u;
+    const size_t img0 = MODE == HR2_LIST ? (size_t)tb * a.H * a.W * a.C0 * 2u : 0, img1 = MODE == HR2_LIST ? (size_t)tb * a.H * a.W * a.C1 * 2u : 0;
 
     int hpixlin[PAH];
     unsigned hoct[PAH];
@@ -587,7 +706,7 @@ __global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void
         const int hy = hp / LWG_HALO_W, hx = hp - hy * LWG_HALO_W;
         const int gy = y0 + hy - 1, gx = x0 + hx - 1;
         const bool ok = hp < LWG_HALO_PIX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-        hpixlin[p] = ok ? (tb * a.H + gy) * a.W + gx : -1;
+        hpixlin[p] = ok ? ((MODE == HR2_LIST ? 0 : tb) * a.H + gy) * a.W + gx : -1;      // (the list form: the pixel's place inside ITS image)
         hoct[p] = (unsigned)((lane & 7) ^ ((hx >> 1) & 7)) * 16u;
     }
     uintx4 hreg[PAH];
@@ -595,6 +714,7 @@ __global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void
         const int cc = chunk << 6;
         const bool use1 = cc >= a.C0;
         const void* src = use1 ? (const void*)a.x1 : (const void*)a.x0;
+        if constexpr (MODE == HR2_LIST) src = static_cast<const char*>(src) + (use1 ? img1 : img0);
         const unsigned cs = (unsigned)(use1 ? a.C1 : a.C0);
         const unsigned soff = (unsigned)(cc - (use1 ? a.C0 : 0)) * 2u;
         __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(src), 0, (int)(use1 ? bytes1 : bytes0), 0x00020000);
@@ -690,7 +810,22 @@ __global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void
         }
     }
     HTS(2);
-    lwg_bf16_epilogue<TM, 1, EPI, 2>(a, acc, 0, n_base, wm, wn, lane, tb, y0, x0, pre, BN);
+    if constexpr (MODE == HR2_ACC) {
+        static_assert(WAVES_M == 1, "the accumulator frame: the list form's layout");
+        float* const yf = a.y + (size_t)tb * a.OH * a.OW * a.N;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            int py, px;
+            hrl_lane_pixel(lane, i, py, px);
+            if (y0 + py < a.OH && x0 + px < a.OW) {
+                floatx4* const p = reinterpret_cast<floatx4*>(yf + hrl_acc_offset(y0 + py, x0 + px, a.OW, a.N, n_base + wn * 32, khalf));
+#pragma unroll
+                for (int g = 0; g < 4; ++g) p[g] = floatx4{acc[i][0][4 * g], acc[i][0][4 * g + 1], acc[i][0][4 * g + 2], acc[i][0][4 * g + 3]};
+            }
+        }
+    } else {
+        lwg_bf16_epilogue<TM, 1, EPI, 2>(a, acc, 0, n_base, wm, wn, lane, tb, y0, x0, pre, BN);
+    }
     HTS(3);
 }
 
@@ -1135,6 +1270,37 @@ extern "C" int lwg_conv2d_nhwc_bf16_hr(const LwgConvArgs* pa, lwg_stream_t strea
     }
     if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
     return (int)launch_epi_bf16_hr<LWG_EPI_NONE>(a, stream);
+}
+
+// The list-driven 3 x 3 launch (include/lwg_hip.h): hrl_contract_ok on the shapes; the grid is the host's number - every in-image
+// sub-tile x column tile -, the lists' counts are read by the kernel only.  Never sliced: the kernel addresses the input per image.
+extern "C" int lwg_conv2d_nhwc_bf16_hr_list_applies(const LwgConvArgs* pa) { return pa && hrl_contract_ok(*pa) ? 1 : 0; }
+
+extern "C" int lwg_conv2d_nhwc_bf16_hr_list(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
+    if (!pa || !pl || !hrl_contract_ok(*pa) || !pa->x0 || !pa->w || !pa->y || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
+    const LwgConvArgs& a = *pa;
+    if (a.epi == LWG_EPI_SPADE && (!a.xn || !a.mean || !a.rstd || !a.bias)) return (int)hipErrorInvalidValue;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    constexpr size_t lds = (size_t)2 * LWG_HALO_BYTES + 2 * 128 * sizeof(float);
+    const dim3 grid((unsigned)hrl_grid(a.B, a.OH, a.OW, a.N / HRL_BN));
+    if (a.epi == LWG_EPI_SPADE) hipLaunchKernelGGL((lwg_conv_bf16_hr2_kernel<3, 3, LWG_EPI_SPADE, 1, HR2_LIST, LwgConvLists>), grid, dim3(256), lds, stream, a, *pl);
+    else hipLaunchKernelGGL((lwg_conv_bf16_hr2_kernel<3, 3, LWG_EPI_NONE, 1, HR2_LIST, LwgConvLists>), grid, dim3(256), lds, stream, a, *pl);
+    return (int)hipGetLastError();
+}
+
+// The accumulators of the same convolution as fp32 (the calibration frame of a list-driven LWG_EPI_SPADE launch): the contract above with
+// LWG_EPI_NONE / LWG_ACTIVATION_NONE, args->y = B * H * W * N floats in the kernel's own order (hrl_acc_offset), bias unread.  A cold path: the
+// batch in one buffer (B * H * W * C0 * 2 below the marker - the calibration has B = 1).
+extern "C" int lwg_conv2d_nhwc_bf16_hr_acc(const LwgConvArgs* pa, lwg_stream_t stream_) {
+    if (!pa || !pa->x0 || !pa->w || !pa->y) return (int)hipErrorInvalidValue;
+    LwgConvArgs a = *pa;
+    if (a.ydt != LWG_DT_F32 || a.epi != LWG_EPI_NONE || a.act != LWG_ACTIVATION_NONE || a.YC != a.N || a.ycoff != 0) return (int)hipErrorInvalidValue;
+    a.ydt = LWG_DT_BF16;                             // (the shape rules of the list form; the kernel stores floats)
+    if (!hrl_contract_ok(a) || (unsigned long long)a.B * a.H * a.W * (unsigned long long)a.C0 * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    constexpr size_t lds = (size_t)2 * LWG_HALO_BYTES + 2 * 128 * sizeof(float);
+    hipLaunchKernelGGL((lwg_conv_bf16_hr2_kernel<3, 3, LWG_EPI_NONE, 1, HR2_ACC>), dim3((unsigned)hrl_grid(a.B, a.OH, a.OW, a.N / HRL_BN)), dim3(256), lds, stream, a);
+    return (int)hipGetLastError();
 }
 
 template <int WAVES_M, int WAVES_N, int TM, int TN, int EPI, bool DMA_A>

@@ -188,21 +188,25 @@ def _skip_lists(lists, cal):
 def spade_calibration(st, x):
     """The calibration frames of one attention site at x's feature size, by the product kernels from ONE all-background frame (every flow -2):
     att_cal = lwb_attention_x, actv_cal = shared(att_cal), gb_cal (1, h, w, 2C) = the gamma | beta convolution of actv_cal with no epilogue and no
-    activation (the same stacked panel and bias).  Built once per packed weight version and size - st belongs to one _Packed - never per call."""
+    activation (the same stacked panel and bias).  Built once per packed weight version, size and storage type - st belongs to one _Packed -
+    never per call.  bf16 x (the "bf16" mode): actv_cal is bf16 - exact, actv is stored so anyway -, gb_cal holds the fp32
+    ACCUMULATORS of the gamma | beta convolution in the kernel's column order (ops.conv2d_acc_frame): the SPADE epilogue consumes fp32
+    accumulators and rounds once, a bf16 frame would lose bits."""
     _, h, w, C = x.shape
     cal = st.setdefault("cal", {})
-    if (h, w) not in cal:
+    key = (h, w) if x.dtype == torch.float32 else (h, w, x.dtype)
+    if key not in cal:
         hook, ops.CONV_HOOK = ops.CONV_HOOK, None          # (not a launch of the frame batch: outside the benchmark's launch accounting)
         try:
             z = x.new_zeros(1, h, w, C)
-            T = x.new_full((1, 1, h, w, 2), -2.0)
-            att = ops.lwb_attention_x(z, z, x.new_zeros(1, h, w), z, st["bv"], T, torch.empty_like(z))
+            T = x.new_full((1, 1, h, w, 2), -2.0, dtype=torch.float32)
+            att = ops.lwb_attention_x(z, z, x.new_zeros(1, h, w, dtype=torch.float32), z, st["bv"], T, torch.empty_like(z))
             actv = ops.conv2d(att, st["shared"], x.new_empty(1, h, w, st["shared"].N), act=ops.ACT_RELU)
-            gb = ops.conv2d(actv, st["gb"], x.new_empty(1, h, w, st["gb"].N))
+            gb = ops.conv2d(actv, st["gb"], x.new_empty(1, h, w, st["gb"].N)) if x.dtype == torch.float32 else ops.conv2d_acc_frame(actv, st["gb"])
         finally:
             ops.CONV_HOOK = hook
-        cal[(h, w)] = (actv, gb)
-    return cal[(h, w)]
+        cal[key] = (actv, gb)
+    return cal[key]
 
 
 def _param_version(gen):
@@ -350,12 +354,14 @@ class AttentionLWBGenerator(nn.Module):
         ops.instnorm_finalize(ws, B, C, nrec, mean, rstd, eps=1e-5)
         actv, out = tsf_x.new_empty(B, h, w, st["shared"].N), torch.empty_like(tsf_x)
         # ops.SPADE_SKIP: where a launch takes the list-driven F(4x4, 3x3) form - a rule on configuration and launch size - the
-        # blocks whose input window is all background (flow -2: att = one vector) are filled from the site's calibration frames
+        # blocks whose input window is all background (flow -2: att = one vector) are filled from the site's calibration frames.  The "bf16" mode
+        # (3.12f) takes the list-driven form of its direct kernel the same way, with that kernel's window reach
+        d1, d5 = ops.SPADE_SKIP_D_BF16 if tsf_x.dtype == torch.bfloat16 else ops.SPADE_SKIP_D
         l1 = l5 = None
         if ops.conv2d_lists_apply(att, st["shared"], actv, act=ops.ACT_RELU):
-            l1 = _skip_lists(scratch.lists(flow, ops.SPADE_SKIP_D[0]), spade_calibration(st, tsf_x)[0])
+            l1 = _skip_lists(scratch.lists(flow, d1), spade_calibration(st, tsf_x)[0])
         if ops.conv2d_lists_apply(actv, st["gb"], out, epi=ops.EPI_SPADE, xn=tsf_x, mean=mean, rstd=rstd):
-            l5 = _skip_lists(scratch.lists(flow, ops.SPADE_SKIP_D[1]), spade_calibration(st, tsf_x)[1])
+            l5 = _skip_lists(scratch.lists(flow, d5), spade_calibration(st, tsf_x)[1])
         # (the keyword only where it is used: the CPU emulation of the tests installs a conv2d of its own, which knows no lists)
         ops.conv2d(att, st["shared"], actv, act=ops.ACT_RELU, **({} if l1 is None else {"lists": l1}))
         return ops.conv2d(actv, st["gb"], out, epi=ops.EPI_SPADE, xn=tsf_x, mean=mean, rstd=rstd, **({} if l5 is None else {"lists": l5}))

@@ -363,6 +363,10 @@ def _wwino4(spec):
 SPADE_SKIP = True       # switch: the SPADE convolutions of the attention sites ("winograd" mode, fp32, F(4x4, 3x3) launches of the 8-wave form) run
                         # list-driven - blocks whose input window is all background are filled from a calibration frame
 SPADE_SKIP_D = (1, 5)   # pixels a block's window reaches beyond the block: the `shared` convolution, the gamma | beta convolution behind it
+SPADE_SKIP_BF16 = False # ... and, with SPADE_SKIP, the 3 x 3 SPADE launches of the "bf16" mode (lwg_conv2d_nhwc_bf16_hr_list).  OFF by default: on BASELINE
+                        # configs[3]'s batch the eighteen launches gain 6.8 %, the generator pass as a whole loses 0.7 % (DESIGN.md 3.12f has the A/B)
+SPADE_SKIP_D_BF16 = (1, 2)      # ... in the "bf16" mode (lwg_conv2d_nhwc_bf16_hr_list): the direct kernel has no Winograd patches - an
+                                # output pixel depends on its own 3 x 3 window, and the second convolution reads one pixel further
 
 
 SPADE_SKIP_FINE = True  # ... at the granularity of 16 x 8 sub-tiles (four per block) where ``spade_skip_fine_apply`` says so; False: block lists everywhere
@@ -402,7 +406,16 @@ def spade_skip_lists(flow, d):
 
 def conv2d_lists_apply(x0, spec, y, epi=EPI_NONE, act=ACT_NONE, xn=None, mean=None, rstd=None):
     """Would ``conv2d`` run this launch list-driven if it were given lists?  A rule on the configuration (precision mode, switches, layer) and the
-    launch's size (lwg_conv2d_winograd4_list_applies: the 8-wave form) - never on the tensors' content."""
+    launch's size (lwg_conv2d_winograd4_list_applies: the 8-wave form) - never on the tensors' content.  bf16 tensors in the "bf16" mode: the 3 x 3
+    launches of lwg_conv2d_nhwc_bf16_hr that lwg_conv2d_nhwc_bf16_hr_list_applies takes (one input, N % 128 == 0, LWG_EPI_NONE / LWG_EPI_SPADE; any
+    batch); never in "bf16_winograd", whose 3 x 3 layers run another kernel."""
+    if x0.dtype == torch.bfloat16 or y.dtype == torch.bfloat16:
+        if not SPADE_SKIP or not SPADE_SKIP_BF16 or CONV_PRECISION != "bf16" or not x0.is_cuda or x0.dtype != y.dtype or not _hr_eligible(spec, x0, y, None):
+            return False
+        key = ("bf16", x0.shape, y.shape, spec.Cin, spec.N, spec.ntaps, epi, act)
+        if key not in _LISTS_APPLY:
+            _LISTS_APPLY[key] = bool(_lib.lib().lwg_conv2d_nhwc_bf16_hr_list_applies(_hr_args(conv_args(x0, spec, y, None, epi, act, None, xn, mean, rstd), spec, epi)))
+        return _LISTS_APPLY[key]
     if not SPADE_SKIP or CONV_PRECISION != "winograd" or not x0.is_cuda or x0.dtype != torch.float32 or not _wino4_use(spec, False) or \
             not _wino_eligible(spec, x0, y, None, epi, act, None, False):
         return False
@@ -451,6 +464,29 @@ def conv_args(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=Non
     return a
 
 
+def _hr_args(a, spec, epi):
+    """The launch description as lwg_conv2d_nhwc_bf16_hr (and its list / accumulator forms) takes it: the register-streamed panel, its bias and
+    its tap order."""
+    panel, bias = _w16hr(spec, epi == EPI_SPADE)
+    a.w, a.bias = _ptr(panel, torch.bfloat16), _ptr(bias)
+    for i, t in enumerate(_hr_tap_order(spec)):                      # the panel's tap order
+        a.dy[i], a.dx[i] = spec.dy[t], spec.dx[t]
+    return a
+
+
+def conv2d_acc_frame(x0, spec, spade=True):
+    """The fp32 ACCUMULATORS of the bf16 3 x 3 convolution of x0 (B, H, W, Cin) as lwg_conv2d_nhwc_bf16_hr_acc leaves them - no bias, no activation,
+    no rounding, columns in the kernel's own order (spade: the gamma | beta panel): the calibration frame of a list-driven EPI_SPADE launch,
+    (B, H, W, N) fp32.  A cold path: not announced to CONV_HOOK."""
+    B, H, W, _ = x0.shape
+    y = torch.empty(B, H, W, spec.N, device=x0.device, dtype=torch.float32)
+    a = conv_args(x0, spec, y)
+    a.ydt = _lib.DT_F32
+    _hr_args(a, spec, EPI_SPADE if spade else EPI_NONE)
+    _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr_acc(a, _stream()), "lwg_conv2d_nhwc_bf16_hr_acc")
+    return y
+
+
 def _hook_end(a, spec, epi, kind, slices=True, extra=0):
     """Closing hook call: how many kernel launches the entry point made (the C rule: lwg_conv_slice_count; extra: a split launch's finishing
     kernel) and which kernel family ran."""
@@ -462,7 +498,9 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
            out_hw=None, ycoff=0, splitk=False, q4=False, lists=None):
     """y <- conv(cat[x0, x1]) per ``spec``; x*: (B,H,W,C) NHWC; y: (B,YH,YW,YC) NHWC (written in place).
     lists: (heavy, light, counts, cal) - ``spade_skip_lists`` and the calibration frame - for a launch ``conv2d_lists_apply`` accepted; or
-    (SkipLists, cal): the sub-tile lists where ``spade_skip_fine_apply`` says so, else the block lists.
+    (SkipLists, cal): the sub-tile lists where ``spade_skip_fine_apply`` says so, else the block lists.  bf16 ("bf16" mode): always the sub-tile
+    triple (``SkipLists.fine``, or given as the 4-tuple); cal = the bf16 output frame of the all-background input, for EPI_SPADE the fp32
+    accumulator frame of ``conv2d_acc_frame``.
     splitk: let the library split small-M / large-K launches over K (the training step's one-sample launches).  Off on the
     synthesis path: a frame's result must not depend on how many frames share its launch (batch invariance is a parity check).
     q4: y is (B, YC/4, YH, YW, 4), channel-quad planes (the fp32 MFMA path only: what ``head_compose(..., q4=True)`` reads)."""
@@ -471,8 +509,10 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         raise ValueError("channel-quad-plane outputs: fp32 activations on the fp32 MFMA path, no split-K")
     if CONV_HOOK is not None:
         CONV_HOOK(True, a.M, spec, epi, None)
-    if lists is not None and not (x0.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION == "winograd" and _wino4_use(spec, splitk)):
-        raise ValueError("lists: the F(4x4, 3x3) launches of the \"winograd\" mode only (conv2d_lists_apply)")
+    if lists is not None and not (x0.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION == "winograd" and _wino4_use(spec, splitk)) and \
+            not (x0.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and CONV_PRECISION == "bf16" and x1 is None and spec.ntaps == 9 and
+                 _hr_eligible(spec, x0, y, out_hw)):
+        raise ValueError("lists: the F(4x4, 3x3) launches of the \"winograd\" mode and the 3 x 3 launches of the \"bf16\" mode only (conv2d_lists_apply)")
     kind, sliced, extra = "direct", True, 0
     if x0.dtype == torch.bfloat16:
         kind = "bf16"
@@ -487,11 +527,22 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
                 a.dy[i], a.dx[i] = dy, dx
             _lib.check(_lib.lib().lwg_conv2d_winograd_bf16(a, _stream()), "lwg_conv2d_winograd_bf16")
         elif _hr_eligible(spec, x0, y, out_hw) or _pw_eligible(spec, x0, y, x1, epi, out_hw):
-            panel, bias = _w16hr(spec, epi == EPI_SPADE)
-            a.w, a.bias = _ptr(panel, torch.bfloat16), _ptr(bias)
-            for i, t in enumerate(_hr_tap_order(spec)):              # the panel's tap order
-                a.dy[i], a.dx[i] = spec.dy[t], spec.dx[t]
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr(a, _stream()), "lwg_conv2d_nhwc_bf16_hr")
+            _hr_args(a, spec, epi)
+            if lists is not None:
+                # the sub-tile lists (the kernel's 8 x 16 pixel block is one sub-tile) and the calibration frame: ONE kernel, never sliced
+                sliced = False
+                if len(lists) == 2 and isinstance(lists[0], SkipLists):
+                    lists = tuple(lists[0].fine) + (lists[1],)
+                i32 = torch.int32
+                nsub = x0.shape[0] * ((x0.shape[1] + 7) // 8) * ((x0.shape[2] + 15) // 16)
+                if min(lists[0].numel(), lists[1].numel()) < nsub or lists[2].numel() < 2 or \
+                        lists[3].numel() != x0.shape[1] * x0.shape[2] * (spec.N if epi == EPI_SPADE else y.shape[3]):
+                    raise ValueError("lists: the sub-tile lists of this frame batch and ONE calibration frame at its feature size")
+                ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32),
+                                       _ptr(lists[3], torch.float32 if epi == EPI_SPADE else torch.bfloat16))
+                _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr_list(a, ctypes.byref(ld), _stream()), "lwg_conv2d_nhwc_bf16_hr_list")
+            else:
+                _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr(a, _stream()), "lwg_conv2d_nhwc_bf16_hr")
         else:
             a.w = _ptr(_w16v2(spec), torch.bfloat16)
             _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16(a, _stream()), "lwg_conv2d_nhwc_bf16")
