@@ -180,6 +180,28 @@ int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, i
                                   int* fheavy, int* flight, int* fcounts, lwg_stream_t stream);
 /* That panel from the fp32 GEMM panel of the same convolution (arguments as lwg_winograd_panel_f32): U = G w G^T in fp64, rounded once. */
 int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream);
+/* The same for every registered F(4x4, 3x3) panel of a training step in ONE launch (ops.PanelCache; the weights change every step): descs_dev = ndesc
+ * LwgWinoDesc records in DEVICE memory, each the argument list of one lwg_winograd4_panel_f32 call plus first_block = the sum of
+ * ceil(N / 64) * ceil(Cin / 4) over the records before it; total_blocks = that sum over all records.  The same arithmetic per (input channel, output
+ * column) as the single launch: bitwise its values.  Returns 1 (hipErrorInvalidValue) before any launch for a NULL table, ndesc < 1 or
+ * total_blocks < 1; the records themselves are read by the device only. */
+int lwg_winograd4_panels_f32(const LwgWinoDesc* descs_dev, int ndesc, int total_blocks, lwg_stream_t stream);
+/* lwg_conv2d_winograd4_f32 with an optional workspace (the training step's one-sample launches; trainers.TrainOpts.conv_tiles = "4x4"):
+ * ws = NULL runs the call above.  Otherwise a launch whose 4-wave blocks (32 x 16 pixels x 32 output channels) would cover half the compute units or
+ * less - LWG_EPI_NONE, or LWG_EPI_RESIDUAL with LWG_ACTIVATION_RELU_MASK: what the finishing kernel finishes - runs its K loop in
+ * lwg_conv2d_winograd4_ws_floats(args) / (M N) = 2 .. 8 slices of contiguous K stages (8 input channels each; every slice an even number of stages, at
+ * least 8 but for a ragged last one): one workgroup per (block, slice) writes its partial outputs - behind the output transform, no bias - to its dense
+ * (M, N) slab ws + slice M N, and the finishing kernel of lwg_conv2d_nhwc_f32_ws adds the slabs in slice order (deterministic), then bias, ReLU mask /
+ * activation.  fp32-grade as the whole launch, not its bits (another summation order).  lwg_conv2d_winograd4_ws_floats returns 0 when the launch would
+ * run whole, for an epilogue the split form does not take (LWG_EPI_SPADE, a plain residual), for a slab image of H W N 4 + 256 bytes >= 3 GiB, or
+ * outside lwg_conv2d_winograd4_f32's contract.  The synthesis path never passes a workspace: a frame must not depend on its batch.
+ * lwg_conv2d_winograd4_plan mirrors lwg_conv2d_winograd_plan: *blocks = 32 x 16-pixel blocks of *nbv (64 | 32) output channels, times the K slices
+ * when with_ws != 0 and the split plan applies; *slices = K slices (0 = whole); *workgroups = workgroups launched (whole launches: persistent,
+ * min(blocks, compute units)).  Any pointer may be NULL.  All three validate on the host and return 1 (hipErrorInvalidValue; ws_floats: 0) before any
+ * launch when args is NULL or outside the contract. */
+int lwg_conv2d_winograd4_f32_ws(const LwgConvArgs* args, float* ws, lwg_stream_t stream);
+int lwg_conv2d_winograd4_plan(const LwgConvArgs* args, int with_ws, long long* blocks, int* slices, int* nbv, int* workgroups);
+size_t lwg_conv2d_winograd4_ws_floats(const LwgConvArgs* args);
 /* The same convolution for the 3x3 (9 taps) and 2x2 (4 taps, transposed-conv parity) stride-1 launches, as the
  * halo-tile kernel with register-streamed weights: args->w = the bf16 panel [ntaps*Cin/64][4][N][16] - element
  * [step][ks][n][e] = weight of GEMM column n at k = step*64 + ks*16 + e (k order as above) - and, for LWG_EPI_SPADE, columns

@@ -77,6 +77,11 @@ _SIGS = {
     "lwg_conv2d_winograd4_fine_f32": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
     "lwg_spade_skip_fine_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "lwg_winograd4_panel_f32": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_f]),
+    "lwg_winograd4_panels_f32": (c_i, [c_f, c_i, c_i, c_f]),
+    "lwg_conv2d_winograd4_f32_ws": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f]),
+    "lwg_conv2d_winograd4_plan": (c_i, [ctypes.POINTER(LwgConvArgs), c_i, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_i), ctypes.POINTER(c_i),
+                                        ctypes.POINTER(c_i)]),
+    "lwg_conv2d_winograd4_ws_floats": (ctypes.c_size_t, [ctypes.POINTER(LwgConvArgs)]),
     "lwg_conv2d_nhwc_bf16_hr": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
     "lwg_conv2d_nhwc_bf16_hr_list": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
     "lwg_conv2d_nhwc_bf16_hr_list_applies": (c_i, [ctypes.POINTER(LwgConvArgs)]),

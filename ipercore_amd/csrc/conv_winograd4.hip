@@ -135,9 +135,15 @@ __device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[NR]) {
 // frames, any positions - in the four slots of its 4 x 8 patches (cw4f_slot_of_patch).  Only the halo staging (four 18 x 10 sub-planes per channel
 // plane, a wave stages the halo of one slot = one image descriptor), the transform's base addresses and the epilogue's output bases (the reader's slot is
 // wave-uniform per pass) differ; the K loop is the same code.
-template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false>
+// SPLIT (lwg_conv2d_winograd4_f32_ws: the training step's one-sample launches; the 4-wave form, plain epilogue): ONE block per workgroup, blockIdx.z owns
+// the K stages [z a.cshift, (z + 1) a.cshift) of it (lwg_conv_wino.h: cw4_slice_begin / _end; an even number of them) and writes its raw partial outputs -
+// behind the output transform - to slab z of the workspace, a.y + z M N (the host passes YC = N, ycoff = 0, no bias, no activation): the slab goes into
+// the BASE of the block's image buffer, the stores' offsets are the whole launch's.  The K loop is the same code on absolute stage indices; the panel's
+// strides stay the layer's.  lwg_splitk_finish_kernel adds the slabs in slice order and finishes.
+template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false, bool SPLIT = false>
 __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists& sk) {
     static_assert(!FINE || (LIST && !SM && !TWO && LWG_W4_RDMAP), "the sub-tile form: a list-driven 8-wave launch");
+    static_assert(!SPLIT || (SM && !LIST && EPI == LWG_EPI_NONE), "the split form: 4-wave blocks, plain epilogue");
     constexpr int RS = W4_RS;                                // the halo planes' geometry in LDS
     constexpr int PLANE = FINE ? W4F_PLANE : W4_PLANE;
     constexpr int RAW = W4_KS * PLANE;
@@ -154,7 +160,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const float* __restrict__ bias = a.bias;
     const int H = a.H, W = a.W, Cin = a.C0 + a.C1, N = a.N;
-    float* __restrict__ y = a.y;
+    float* __restrict__ y = SPLIT ? a.y + cw4_slab_offset((int)blockIdx.z, a.M, N) : a.y;
     float* const raw0 = smem;                                // [2][RAW], then [2][VS]
     float* const Ms = smem;                                  // the epilogue's exchange buffer (after the K loop)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -175,6 +181,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     const bool lst = FINE ? true : LIST ? nht < nall : false;
     const bool run = lst ? blk < nhe : true;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
+    const int sbeg = SPLIT ? cw4_slice_begin((int)blockIdx.z, a.cshift) : 0;       // this workgroup's stages [sbeg, send): the layer's, or its slice
+    const int send = SPLIT ? cw4_slice_end((int)blockIdx.z, a.cshift, nst) : nst;
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)(144u * (unsigned)Cin * (unsigned)N), 0x00020000);
     const int q = wid & 3, ct = SM ? 0 : wid >> 2;           // this wave's product set and 32-channel tile
     const int half = SM ? 0 : wid >> 2;                      // ... and its half of the input transform (rows 3 half .. 3 half + 2 of B^T d B; SM: both)
@@ -364,7 +372,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     auto iteration = [&](int s, auto SET, auto NXT) {
         constexpr int set = decltype(SET)::value;            // s % 2
         constexpr bool nxt = decltype(NXT)::value != 0;      // the last stage has no next one to prepare (peeled: no branches in the loop)
-        const int s3 = s + 3 < nst ? s + 3 : nst - 1;        // past the end: a harmless re-load of the last stage (its halo store lands in a dead buffer)
+        const int s3 = s + 3 < send ? s + 3 : send - 1;      // past the end: a harmless re-load of the last stage (its halo store lands in a dead buffer)
         float X[6], P[6], Q[6], dR[3][6];
         auto mf = [&](int kk, int j, bool refill) {          // product j of k-pair kk; then its register takes the fragment of the next k-pair
             acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(j < 4 ? ufa[kk][j & 3] : j < 8 ? ufb[kk][j & 3] : ufc[kk], fb[j], acc[j], 0, 0, 0);
@@ -500,20 +508,20 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     };
 
     // prologue loads of a block: stages 0 and 1 (-> raw[0], raw[1]), stage 2's halo (kept in registers), the first two k-pairs' weights - requested here for
-    // the workgroup's first block, for every later one from inside the previous block's epilogue
+    // the workgroup's first block, for every later one from inside the previous block's epilogue (SPLIT: the slice's first stages - sbeg + 0, 1, 2)
     floatx4 r0[NQ], r1[NQ];
     float bq;                                                // the block's bias, one value per lane of wave 0: requested with the first loads, parked in LDS by the prologue
     auto issue_loads = [&]() {
         bq = bias ? bias[SMS ? bk.n0 + (((tid & 31) >> 4) << 5) + (tid & 15) : bk.n0 + (tid & (NBV - 1))] : 0.f;
 #pragma unroll
         for (int k = 0; k < NQ; ++k) {
-            r0[k] = rld1(0, k);
-            r1[k] = rld1(1, k);
+            r0[k] = rld1(sbeg, k);
+            r1[k] = rld1(sbeg + 1, k);
         }
-        uldset(0, 0, 0);
-        uldset(1, 0, 1);
+        uldset(0, sbeg, 0);
+        uldset(1, sbeg, 1);
 #pragma unroll
-        for (int k = 0; k < NQ; ++k) rreg[k] = rld1(nst > 2 ? 2 : 1, k);
+        for (int k = 0; k < NQ; ++k) rreg[k] = rld1(send - sbeg > 2 ? sbeg + 2 : sbeg + 1, k);
     };
     if (run) issue_loads();
 #ifdef LWG_W4_TS
@@ -549,8 +557,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     }
     W4TS(1);
     {
-        int s = 0;
-        for (; s + 2 < nst; s += 2) {
+        int s = sbeg;
+        for (; s + 2 < send; s += 2) {
             iteration(s, IntC<0>(), IntC<1>());
             iteration(s + 1, IntC<1>(), IntC<1>());
         }
@@ -672,6 +680,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             // the next block of this workgroup: its first loads go out here - the accumulators are dead - and land under the second pass's output
             // (unconditional: the last block re-requests its own first stages, nobody waits for them; see conv_winograd.hip)
             W4TS(8);
+            if constexpr (!SPLIT) {                          // (a split launch's workgroup has one block)
             nblk = blk + (int)gridDim.x;
             if constexpr (FINE) more = nblk < nhe;
             else if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
@@ -680,6 +689,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             W4TS(9);
             issue_loads();
             W4TS(10);
+            }
         }
         __syncthreads();
         if (ph == 0) W4TS(5); else W4TS(7);
@@ -834,6 +844,10 @@ template <int EPI, bool TWO, bool SM = false>
 __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_kernel(const LwgConvArgs a) {
     w4_body<EPI, TWO, SM, false>(a, LwgConvLists{});
 }
+template <bool TWO>
+__global__ __launch_bounds__(256, 1) void lwg_conv_winograd4_split_kernel(const LwgConvArgs a) {
+    w4_body<LWG_EPI_NONE, TWO, true, false, false, true>(a, LwgConvLists{});
+}
 template <int EPI>
 __global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_list_kernel(const LwgConvArgs a, const LwgConvLists sk) {
     w4_body<EPI, false, false, true>(a, sk);
@@ -890,6 +904,65 @@ __global__ __launch_bounds__(256) void lwg_winograd4_panel_kernel(const float* _
     }
 }
 
+// every registered panel of a training step in one launch (the weights change every step; conv_winograd.hip: lwg_winograd_panels_kernel): workgroup b
+// serves descriptor d = the last one with first_block <= b (binary search), block lb of its ceil(N / 64) x ceil(Cin / 4) grid.  Bitwise the values of
+// the single launch: the kernel above is left to the compiler's contraction (its code is unchanged), which evaluates every three-term sum
+// a0 b0 + a1 b1 + a2 b2 as fma(a2, b2, fma(a1, b1, a0 * b0)) - one rounded product, two fused steps, in this order (terms with a zero coefficient
+// add an exact zero wherever the compiler places them); this copy writes that order out and forbids any other contraction.
+__device__ __forceinline__ double w4_panel_sum3(double a0, double b0, double a1, double b1, double a2, double b2) {
+#pragma clang fp contract(off)
+    const double p = a0 * b0;
+    return __builtin_fma(a2, b2, __builtin_fma(a1, b1, p));
+}
+__device__ __forceinline__ void lwg_winograd4_panels_pair(const float* __restrict__ wp, float* __restrict__ U, int Cin, int N, const int* t9, int c, int n) {
+    double g[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const int k = ((c >> 5) * 9 + t9[3 * r + s]) * 32 + (c & 31);
+            g[r][s] = (double)wp[((size_t)(k >> 2) * N + n) * 4 + (k & 3)];
+        }
+    const double G[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6}, {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    double t[6][3];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) t[i][s] = w4_panel_sum3(G[i][0], g[0][s], G[i][1], g[1][s], G[i][2], g[2][s]);
+    const int s8 = c >> 3, kk = (c & 7) >> 1, kh = c & 1;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        float* dst = U + ((((size_t)qq * (Cin >> 3) + s8) * 4 + kk) * 2 + kh) * 9 * (size_t)N;
+        float o[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const int xi = j < 6 ? qq : 4 + (qq >> 1), nu = j < 6 ? j : 3 * (qq & 1) + (j - 6);
+            o[j] = (float)w4_panel_sum3(t[xi][0], G[nu][0], t[xi][1], G[nu][1], t[xi][2], G[nu][2]);
+        }
+        *reinterpret_cast<floatx4*>(dst + 4 * n) = floatx4{o[0], o[1], o[2], o[3]};
+        *reinterpret_cast<floatx4*>(dst + 4 * (size_t)N + 4 * n) = floatx4{o[4], o[5], o[6], o[7]};
+        dst[8 * (size_t)N + n] = o[8];
+    }
+}
+__global__ __launch_bounds__(256) void lwg_winograd4_panels_kernel(const LwgWinoDesc* __restrict__ descs, int ndesc) {
+    int lo = 0, hi = ndesc - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (descs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const LwgWinoDesc* d = descs + lo;
+    const int N = d->N, Cin = d->Cin, nbx = (N + 63) >> 6;
+    const int lb = (int)blockIdx.x - d->first_block;
+    const int n = (lb % nbx) * 64 + (threadIdx.x & 63), c = (lb / nbx) * 4 + (threadIdx.x >> 6);
+    if (n < N && c < Cin) lwg_winograd4_panels_pair(d->wpanel, d->upk, Cin, N, d->tap9, c, n);
+}
+
+extern "C" int lwg_winograd4_panels_f32(const LwgWinoDesc* descs_dev, int ndesc, int total_blocks, lwg_stream_t stream_) {
+    if (!descs_dev || ndesc < 1 || total_blocks < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(lwg_winograd4_panels_kernel, dim3((unsigned)total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), descs_dev, ndesc);
+    return (int)hipGetLastError();
+}
+
 extern "C" int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream_) {
     LwgWinoTaps taps;
     if (!cw_panel_args_ok(wpanel, upk, Cin, N, tap9, taps)) return (int)hipErrorInvalidValue;
@@ -921,6 +994,55 @@ extern "C" int lwg_conv2d_winograd4_f32(const LwgConvArgs* pa, lwg_stream_t stre
     if (a.epi == LWG_EPI_SPADE) return sm ? lwg_wino4_go<LWG_EPI_SPADE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_SPADE, false>(a, grid, lds, stream);
     if (a.epi == LWG_EPI_RESIDUAL) return sm ? lwg_wino4_go<LWG_EPI_RESIDUAL, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_RESIDUAL, false>(a, grid, lds, stream);
     return sm ? lwg_wino4_go<LWG_EPI_NONE, true>(a, grid, lds, stream) : lwg_wino4_go<LWG_EPI_NONE, false>(a, grid, lds, stream);
+}
+
+// The split-K launch of a training step (include/lwg_hip.h; lwg_conv_wino.h: cw4_split_plan): ws = NULL, or a launch the plan runs whole - the
+// entry point above.
+static Cw4Split lwg_wino4_split_plan(const LwgConvArgs& a) {
+    const bool mask = a.epi == LWG_EPI_RESIDUAL && a.act == LWG_ACT_RELU_MASK;
+    return cw4_split_plan(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, 32), (a.C0 + a.C1) / W4_KS, lwg_device_cus(),
+                          LWG_W4_SMALL && (a.epi == LWG_EPI_NONE || mask), cw4_slab_image_ok(a.H, a.W, a.N));
+}
+extern "C" size_t lwg_conv2d_winograd4_ws_floats(const LwgConvArgs* pa) {
+    if (!pa || !cw_contract_ok(*pa, 144ull, 256ll)) return 0;
+    return cw4_slab_offset(lwg_wino4_split_plan(*pa).slices, pa->M, pa->N);
+}
+// *blocks = 32 x 16-pixel blocks of the launch (times the K slices when with_ws and the split plan applies), *slices = K slices (0 = whole), *nbv =
+// output channels per block (64 | 32), *workgroups = workgroups launched.  Returns 0, or 1 when the launch does not meet the contract.
+extern "C" int lwg_conv2d_winograd4_plan(const LwgConvArgs* pa, int with_ws, long long* blocks, int* slices, int* nbv, int* workgroups) {
+    if (!pa || !cw_contract_ok(*pa, 144ull, 256ll)) return (int)hipErrorInvalidValue;
+    const LwgConvArgs& a = *pa;
+    const int sl = with_ws ? lwg_wino4_split_plan(a).slices : 0;
+    const int cus = lwg_device_cus();
+    const long long b64 = cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB);
+    const int v = sl > 1 || (LWG_W4_SMALL && 2 * b64 <= cus) ? 32 : W4_NB;
+    const long long nb = b64 * (W4_NB / v) * (sl > 1 ? sl : 1);
+    if (blocks) *blocks = nb;
+    if (slices) *slices = sl > 1 ? sl : 0;
+    if (nbv) *nbv = v;
+    if (workgroups) *workgroups = (int)(sl > 1 ? nb : (nb < cus ? nb : cus));
+    return 0;
+}
+extern "C" int lwg_conv2d_winograd4_f32_ws(const LwgConvArgs* pa, float* ws, lwg_stream_t stream_) {
+    if (!pa || !cw_contract_ok(*pa, 144ull, 256ll)) return (int)hipErrorInvalidValue;
+    const LwgConvArgs& a = *pa;
+    const Cw4Split sp = ws ? lwg_wino4_split_plan(a) : Cw4Split{0, 0};
+    if (sp.slices < 2) return lwg_conv2d_winograd4_f32(pa, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    LwgConvArgs part = a;                                    // raw sums into the slabs: dense (M, N) rows, no bias / residual / activation
+    part.y = ws;
+    part.YC = a.N;
+    part.ycoff = 0;
+    part.bias = nullptr;
+    part.epi = LWG_EPI_NONE;
+    part.act = LWG_ACT_NONE;
+    part.res = nullptr;
+    part.cshift = sp.sps;
+    const size_t lds = (size_t)(W4_BIAS_OFF + 64) * 4;
+    const dim3 grid((unsigned)cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, 32), 1u, (unsigned)sp.slices);
+    const int e = a.C1 > 0 ? cw_launch<lwg_conv_winograd4_split_kernel<true>>(grid, 256, lds, stream, part)
+                           : cw_launch<lwg_conv_winograd4_split_kernel<false>>(grid, 256, lds, stream, part);
+    return e != (int)hipSuccess ? e : (int)lwg_splitk_finish_launch(a, ws, sp.slices, stream);
 }
 
 // The list-driven launch (include/lwg_hip.h): the same contract, LWG_EPI_NONE / LWG_EPI_SPADE and one input only; the grid is sized from the launch's

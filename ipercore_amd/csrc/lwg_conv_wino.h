@@ -194,6 +194,32 @@ CW_FN void cw4f_light_pixel(int& px, int& py) {
     py = p / CW4F_SX, px = p - py * CW4F_SX;
 }
 
+// ---- split-K launches of F(4x4) (lwg_conv2d_winograd4_f32_ws): the training step's one-sample launches.  The 4-wave form's blocks
+// (32 x 16 pixels x 32 channels) x `slices` workgroups, slice z owns the K stages [z sps, min((z + 1) sps, nst)) of its block - sps even, so every
+// slice is an even number of stages - and writes its raw partial outputs to the dense (M, N) slab z of the workspace; the finishing kernel of the
+// direct engine adds the slabs in slice order.  The plan (slices = 0: run the launch whole): a launch whose blocks32 4-wave blocks cover half the
+// compute units or less, in min(8, cus / blocks32) slices of at least CW4_SPLIT_MIN_STAGES stages each (a slice pays the block's prologue and the
+// 28-plane epilogue again); finishable = an epilogue the finishing kernel finishes (plain, or the ReLU-mask data gradient); slab_ok = a slab image is
+// one buffer of the store path (cw4_slab_image_ok)
+#define CW4_SPLIT_MIN_STAGES 8
+#define CW4_SPLIT_MAX_SLICES 8
+struct Cw4Split { int slices, sps; };
+CW_FN Cw4Split cw4_split_plan(long long blocks32, int nst, int cus, bool finishable, bool slab_ok) {
+    if (!finishable || !slab_ok || blocks32 < 1 || 2 * blocks32 > (long long)cus) return Cw4Split{0, 0};
+    int want = (int)((long long)cus / blocks32);
+    if (want > CW4_SPLIT_MAX_SLICES) want = CW4_SPLIT_MAX_SLICES;
+    int sps = (nst + want - 1) / want;
+    if (sps < CW4_SPLIT_MIN_STAGES) sps = CW4_SPLIT_MIN_STAGES;
+    sps += sps & 1;
+    const int slices = (nst + sps - 1) / sps;
+    return slices < 2 ? Cw4Split{0, 0} : Cw4Split{slices, sps};
+}
+CW_FN int cw4_slice_begin(int slice, int sps) { return slice * sps; }
+CW_FN int cw4_slice_end(int slice, int sps, int nst) { return (slice + 1) * sps < nst ? (slice + 1) * sps : nst; }
+// slab `slice` of the workspace, in floats from its start (into the BASE POINTER of the slab's image buffers - never a scalar offset of the stores)
+CW_FN size_t cw4_slab_offset(int slice, int M, int N) { return (size_t)slice * (size_t)M * (size_t)N; }
+CW_FN bool cw4_slab_image_ok(int H, int W, int N) { return (unsigned long long)H * W * N * 4ull + 256ull < (unsigned long long)CW_OOB; }
+
 // ---- the host contracts.  fp32 (lwg_conv2d_winograd_f32 / _f32_ws, lwg_conv2d_winograd4_f32): the launch description of the 3 x 3 / stride 1 /
 // pad 1 convolution as lwg_conv2d_nhwc_f32 takes it (nine taps, omul = 1, OH = H, OW = W, one or two inputs with C0 % 8 == 0, C1 % 8 == 0 and
 // (C0 + C1) % 16 == 0, N % 64 == 0, YC % 4 == 0; LWG_EPI_NONE, LWG_EPI_RESIDUAL (ycoff % 4 == 0) or LWG_EPI_SPADE (N = 2 YC, columns gamma | beta

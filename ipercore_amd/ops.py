@@ -342,11 +342,72 @@ WINO4 = True            # lab switch: in the "winograd" mode the synthesis path'
 WINO4_MIN_CIN = 64      # below it the F(2x2, 3x3) kernel stays (a block's K loop must pay for the 28-plane exchange of the F(4x4, 3x3) epilogue)
 
 
+# The training step's Winograd tiles (trainers.TrainOpts.conv_tiles).  "2x2": every training launch (splitk=True) of the "winograd" mode keeps the
+# F(2x2, 3x3) kernel and its split plan, or the direct split-K kernel.  "4x4": the eligible ones with Cin >= WINO4_MIN_CIN that _wino4_plan takes run
+# the F(4x4, 3x3) kernel, whole or split over K (lwg_conv2d_winograd4_f32_ws); every other launch exactly as "2x2".  The synthesis
+# path (splitk=False) does not read it.
+TRAIN_CONV_TILES = "2x2"
+
+
+class train_conv_tiles(object):
+    """Context manager: ``with ops.train_conv_tiles("4x4"): ...`` (trainers.TrainOpts.conv_tiles)."""
+
+    def __init__(self, mode):
+        assert mode in ("2x2", "4x4")
+        self.mode = mode
+
+    def __enter__(self):
+        global TRAIN_CONV_TILES
+        self.prev = TRAIN_CONV_TILES
+        TRAIN_CONV_TILES = self.mode
+
+    def __exit__(self, *exc):
+        global TRAIN_CONV_TILES
+        TRAIN_CONV_TILES = self.prev
+
+
 def _wino4_use(spec, splitk):
     """Which launches of the "winograd" mode run lwg_conv2d_winograd4_f32 (F(4x4, 3x3): 2.25 multiplies per output instead of 4): a rule on the LAYER
     (its Cin), never on the batch - a frame's result must not depend on how many frames share its launch.  Training launches (splitk=True) keep the
-    F(2x2, 3x3) kernel and its split plan."""
-    return WINO4 and _MODE_WINO4 and not splitk and spec.Cin >= WINO4_MIN_CIN
+    F(2x2, 3x3) kernel and its split plan unless the step runs with ``train_conv_tiles("4x4")`` - then ``_wino4_plan`` has the last word."""
+    return WINO4 and _MODE_WINO4 and spec.Cin >= WINO4_MIN_CIN and (not splitk or TRAIN_CONV_TILES == "4x4")
+
+
+# Which of the library's F(4x4) forms a training launch takes - each only where it was FASTER than the parent's choice on the launch shapes of the
+# 512^2 personalization step (tools/train_conv_tiles_ab.py, profiles/train_conv_tiles_layers.txt; DESIGN.md 3.12g has the table):
+#  * whole, where the library plans no split and the launch is more than 128 units of 32 x 16 pixels x 32 channels (0.66 - 0.97 of the F(2x2) time
+#    on every such shape of the step, 224 units and up; the one measured below that, 32 units, lost: 1.57);
+#  * split over K, where every slice keeps at least 128 input channels (0.85 - 0.97 on the four such shapes: Cin 256 in two slices, 512 in four;
+#    slices of 64 channels pay the block's prologue and 28-plane epilogue for too little: 0.96 - 1.70, most of them losses).
+WINO4_TRAIN_MIN_GRID = 129      # units (times the K slices) a training launch needs for F(4x4)
+WINO4_TRAIN_MIN_SLICE_CIN = 128 # input channels per K slice a split launch needs
+WINO4_TRAIN_WHOLE = True        # lab switch: False = the training launches the library would run whole stay with the parent's choice
+WINO4_TRAIN_SPLITK = True       # lab switch: False = ... and so do the ones it would split over K
+
+
+def _wino4_plan(a):
+    """How a training launch (splitk=True) that ``_wino4_use`` admits runs: 0 = the F(4x4, 3x3) kernel whole, n > 0 = split over K through a
+    workspace of n floats (lwg_conv2d_winograd4_f32_ws), None = not on F(4x4) - the launch then falls through to ``_wino_plan`` exactly as with
+    ``train_conv_tiles("2x2")``.  The tile geometry and the split plan are the library's (lwg_conv2d_winograd4_plan); the thresholds above say
+    which of its answers the step takes."""
+    blocks, slices, nbv = ctypes.c_longlong(0), ctypes.c_int(0), ctypes.c_int(0)
+    if _lib.lib().lwg_conv2d_winograd4_plan(a, 1, ctypes.byref(blocks), ctypes.byref(slices), ctypes.byref(nbv), None) != 0:
+        return None
+    if not (WINO4_TRAIN_SPLITK if slices.value else WINO4_TRAIN_WHOLE) or blocks.value * (nbv.value // 32) < WINO4_TRAIN_MIN_GRID:
+        return None
+    if slices.value and a.C0 + a.C1 < WINO4_TRAIN_MIN_SLICE_CIN * slices.value:
+        return None
+    return slices.value * a.M * a.N
+
+
+def _wino_route(a, spec, y, splitk):
+    """(F(4x4) ?, workspace floats) of an eligible launch of the "winograd" mode, or None = not on a Winograd kernel."""
+    if _wino4_use(spec, splitk):
+        n4 = _wino4_plan(a) if splitk else 0
+        if n4 is not None:
+            return True, n4
+    n = _wino_plan(a, spec, y, splitk)
+    return None if n is None else (False, n)
 
 
 def _wwino4(spec):
@@ -354,6 +415,10 @@ def _wwino4(spec):
     U = G w G^T (6 x 6) per (input, output) channel pair in fp64, rounded once, stored [4][Cin/8][4][2][9 N] (include/lwg_hip.h)."""
     def build():
         cin, N, tap9 = _wino_panel_source(spec)
+        if PANEL_CACHE is not None:                          # a training step: panels of registered weights are refreshed once per step
+            U = PANEL_CACHE.winograd4(spec, list(tap9))
+            if U is not None:
+                return U
         U = torch.empty(4, cin // 8, 4, 2, 9 * N, device=spec.w.device, dtype=torch.float32)
         _lib.check(_lib.lib().lwg_winograd4_panel_f32(_ptr(spec.w), _ptr(U), cin, N, tap9, _stream()), "lwg_winograd4_panel_f32")
         return U
@@ -554,9 +619,10 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         else:
             _lib.check(_lib.lib().lwg_conv2d_nhwc_f32(a, _stream()), "lwg_conv2d_nhwc_f32")
     elif CONV_PRECISION == "winograd" and _wino_eligible(spec, x0, y, x1, epi, act, out_hw, q4, ycoff) and \
-            (nws := _wino_plan(a, spec, y, splitk)) is not None:
+            (route := _wino_route(a, spec, y, splitk)) is not None:
         kind, sliced = "winograd", False            # per-image buffer descriptors: one launch at any batch size
-        if _wino4_use(spec, splitk):
+        four, nws = route
+        if four:
             a.w = _ptr(_wwino4(spec))
             kind = "winograd4"
             if lists is not None:
@@ -571,6 +637,9 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
                     _lib.check(_lib.lib().lwg_conv2d_winograd4_fine_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_fine_f32")
                 else:
                     _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
+            elif nws:                               # a training launch (train_conv_tiles("4x4")) split over K
+                ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
+                _lib.check(_lib.lib().lwg_conv2d_winograd4_f32_ws(a, _ptr(ws), _stream()), "lwg_conv2d_winograd4_f32_ws")
             else:
                 _lib.check(_lib.lib().lwg_conv2d_winograd4_f32(a, _stream()), "lwg_conv2d_winograd4_f32")
         elif nws:
@@ -1309,6 +1378,8 @@ class PanelCache:
         # Winograd fragment panels derived from registered GEMM panels (ops._wwino): key (panel address, tap order) -> U; the ones whose
         # weights train are re-derived by ONE launch per step behind the GEMM panels' refresh (lwg_winograd_panels_f32)
         self.src_of, self.wino, self.wino_rows, self.wino_table, self.wino_blocks = {}, {}, [], None, 0
+        # ... and the F(4x4, 3x3) panels (ops._wwino4; train_conv_tiles("4x4")): one more launch behind that one (lwg_winograd4_panels_f32)
+        self.wino4, self.wino4_rows, self.wino4_table, self.wino4_blocks = {}, [], None, 0
         # frozen weights (the loss networks): packed once - but watched: [weight, tensor version at pack time, cache key]; refresh() re-packs a
         # panel whose weight was written since (load_state_dict / an un-freeze after the first step) instead of training against a stale one
         self.frozen = []
@@ -1358,12 +1429,17 @@ class PanelCache:
                 if pp == out.data_ptr():
                     arr9 = (ctypes.c_int * 9)(*tap9)
                     _lib.check(_lib.lib().lwg_winograd_panel_f32(_ptr(out), _ptr(U), cin_pad, out.shape[1], arr9, _stream()), "lwg_winograd_panel_f32")
+            for (pp, tap9), U in self.wino4.items():
+                if pp == out.data_ptr():
+                    arr9 = (ctypes.c_int * 9)(*tap9)
+                    _lib.check(_lib.lib().lwg_winograd4_panel_f32(_ptr(out), _ptr(U), cin_pad, out.shape[1], arr9, _stream()), "lwg_winograd4_panel_f32")
             f[1] = w._version
 
     def invalidate(self):
         """Forget every panel (weights re-allocated or reloaded wholesale): the next requests pack afresh."""
         self.out, self.rows, self.keep, self.table, self.blocks, self.frozen = {}, [], [], None, 0, []
         self.src_of, self.wino, self.wino_rows, self.wino_table, self.wino_blocks = {}, {}, [], None, 0
+        self.wino4, self.wino4_rows, self.wino4_table, self.wino4_blocks = {}, [], None, 0
 
     def refresh(self):
         """Re-pack every registered panel of a weight that trains (requires_grad when the cache was built) from the current weights: one launch
@@ -1387,39 +1463,57 @@ class PanelCache:
         _lib.check(_lib.lib().lwg_pack_panels_f32(self.table.data_ptr(), len(self.rows), self.blocks, _stream()), "lwg_pack_panels_f32")
         if self.wino_rows:
             if self.wino_table is None:
-                descs = (_lib.LwgWinoDesc * len(self.wino_rows))()
-                first = 0
-                for d, (wp, up, cin, N, tap9) in zip(descs, self.wino_rows):
-                    d.wpanel, d.upk, d.Cin, d.N, d.first_block = wp, up, cin, N, first
-                    for i in range(9):
-                        d.tap9[i] = tap9[i]
-                    first += ((N + 63) // 64) * ((cin + 15) // 16)
-                raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8)
-                self.wino_table = raw.to(self.keep[0].device)
-                self.wino_blocks = first
+                self.wino_table, self.wino_blocks = self._wino_table(self.wino_rows, 16)
             _lib.check(_lib.lib().lwg_winograd_panels_f32(self.wino_table.data_ptr(), len(self.wino_rows), self.wino_blocks, _stream()),
                        "lwg_winograd_panels_f32")
+        if self.wino4_rows:
+            if self.wino4_table is None:
+                self.wino4_table, self.wino4_blocks = self._wino_table(self.wino4_rows, 4)
+            _lib.check(_lib.lib().lwg_winograd4_panels_f32(self.wino4_table.data_ptr(), len(self.wino4_rows), self.wino4_blocks, _stream()),
+                       "lwg_winograd4_panels_f32")
+
+    def _wino_table(self, rows, cpb):
+        """rows of (GEMM panel, fragment panel, Cin, N, tap order) -> (the device table of LwgWinoDesc records, its total blocks); a block = 64
+        output columns x cpb input channels (lwg_winograd_panels_f32: 16, lwg_winograd4_panels_f32: 4)."""
+        descs = (_lib.LwgWinoDesc * len(rows))()
+        first = 0
+        for d, (wp, up, cin, N, tap9) in zip(descs, rows):
+            d.wpanel, d.upk, d.Cin, d.N, d.first_block = wp, up, cin, N, first
+            for i in range(9):
+                d.tap9[i] = tap9[i]
+            first += ((N + 63) // 64) * ((cin + cpb - 1) // cpb)
+        raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8)
+        return raw.to(self.keep[0].device), first
 
     def winograd(self, spec, tap9):
-        """The fragment panel of a spec whose GEMM panel is registered here, or None (a per-call temporary: single launch each time).  First
-        request: allocated, built by a single launch and - when the source weight trains - registered for the per-step refresh."""
+        """The F(2x2, 3x3) fragment panel [16][Cin/8][2][N][4] of a spec whose GEMM panel is registered here, or None (a per-call temporary: single
+        launch each time).  First request: allocated, built by a single launch and - when the source weight trains - registered for the per-step
+        refresh."""
+        return self._fragment_panel(spec, tap9, self.wino, self.wino_rows, "wino_table", lambda N: (16, spec.Cin // 8, 2, N, 4), "lwg_winograd_panel_f32")
+
+    def winograd4(self, spec, tap9):
+        """The same for the F(4x4, 3x3) fragment panel [4][Cin/8][4][2][9 N] (ops._wwino4)."""
+        return self._fragment_panel(spec, tap9, self.wino4, self.wino4_rows, "wino4_table", lambda N: (4, spec.Cin // 8, 4, 2, 9 * N),
+                                    "lwg_winograd4_panel_f32")
+
+    def _fragment_panel(self, spec, tap9, panels, rows, table, shape, single):
         w = self.src_of.get(spec.w.data_ptr())
         if w is None:
             return None
         key = (spec.w.data_ptr(), tuple(tap9))
-        U = self.wino.get(key)
+        U = panels.get(key)
         if U is None:
             trains = w.untyped_storage().data_ptr() in self.training_storages
-            if self.wino_table is not None and trains and torch.cuda.is_current_stream_capturing():
+            if getattr(self, table) is not None and trains and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("PanelCache: a Winograd panel was requested for the first time inside a hipGraph capture: run one eager step first")
             K4, N, _ = spec.w.shape
-            U = torch.empty(16, spec.Cin // 8, 2, N, 4, device=spec.w.device, dtype=torch.float32)
+            U = torch.empty(*shape(N), device=spec.w.device, dtype=torch.float32)
             arr = (ctypes.c_int * 9)(*tap9)
-            _lib.check(_lib.lib().lwg_winograd_panel_f32(_ptr(spec.w), _ptr(U), spec.Cin, N, arr, _stream()), "lwg_winograd_panel_f32")
-            self.wino[key] = U
+            _lib.check(getattr(_lib.lib(), single)(_ptr(spec.w), _ptr(U), spec.Cin, N, arr, _stream()), single)
+            panels[key] = U
             if trains:                                       # frozen weights (the loss networks): built once
-                self.wino_rows.append((spec.w.data_ptr(), U.data_ptr(), spec.Cin, N, tuple(tap9)))
-                self.wino_table = None
+                rows.append((spec.w.data_ptr(), U.data_ptr(), spec.Cin, N, tuple(tap9)))
+                setattr(self, table, None)
         return U
 
 

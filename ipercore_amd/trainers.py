@@ -646,6 +646,11 @@ class TrainOpts(object):
     # channel counts % 64 == 0 in F(2x2,3x3) Winograd form (ops.wgrad_precision, csrc/conv_wgrad_winograd.hip): fp32-grade,
     # not the direct kernel's bits; their bias gradients come from the column-sum kernel
     wgrad_precision = "direct"
+    # "2x2": the step's Winograd launches are F(2x2,3x3) ones, whole or split over K.  "4x4" (opt-in): the eligible forward and data-gradient
+    # launches with Cin >= ops.WINO4_MIN_CIN that the library's plan takes (lwg_conv2d_winograd4_plan) run the F(4x4,3x3) kernel - 2.25
+    # multiplies per output instead of 4 -, whole or split over K (ops.train_conv_tiles, csrc/conv_winograd4.hip): fp32-grade,
+    # not the F(2x2,3x3) kernel's bits; every other launch exactly as "2x2"
+    conv_tiles = "2x2"
     # "VGG19": the transfer loss is the VGG19 perceptual loss (deploy.toml:83, the reference's default) instead of L1;
     # vgg_loss_path: torchvision vgg19 state_dict (used when the file exists, seeded weights otherwise)
     use_vgg = "VGG19"
@@ -906,10 +911,16 @@ class LWGTrainer(object):
             self._panel_cache = ops.PanelCache([p for n in nets if n is not None for p in list(n.parameters()) + list(n.buffers())])
         if on_gpu and getattr(self.opts, "branch_streams", False) and getattr(self, "_branch_stream", None) is None:
             self._branch_stream = torch.cuda.Stream()
+        tiles = getattr(self.opts, "conv_tiles", "2x2")
+        if getattr(self, "_panel_cache", None) is not None and getattr(self, "_panel_tiles", tiles) != tiles:
+            self._panel_cache.invalidate()                  # the fragment panels of the other mode's kernels must not ride along in the per-step refresh
+            self._graphs = None                             # (a captured step holds the old panels' addresses: it is re-captured for the new mode anyway)
+        self._panel_tiles = tiles
         prev = ops.PANEL_CACHE, ops.BRANCH_STREAM
         ops.PANEL_CACHE, ops.BRANCH_STREAM = getattr(self, "_panel_cache", None), getattr(self, "_branch_stream", None)
         try:
-            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_precision(getattr(self.opts, "wgrad_precision", "direct")):
+            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_precision(getattr(self.opts, "wgrad_precision", "direct")), \
+                    ops.train_conv_tiles(tiles):
                 if self._graphable():
                     return self._graph_step()
                 if getattr(self.opts, "dp_schedule", "hooks") == "segmented" and self._multi():
@@ -1068,6 +1079,9 @@ class LWGTrainer(object):
         if self._graphs["wgrad"] != ops.WGRAD_PRECISION:     # the weight-gradient kernels are frozen into the graph too
             self._graphs = None
             return self._graph_step()
+        if self._graphs["tiles"] != ops.TRAIN_CONV_TILES:    # ... and so is the choice between the F(2x2,3x3) and F(4x4,3x3) launches
+            self._graphs = None
+            return self._graph_step()
         gr = self._graphs
         if multi:
             # [A: G fwd / bwd] -> {G's all-reduce on RCCL's stream || [D: D fwd / bwd on the second stream]} -> {Adam(G) || D's all-reduce}
@@ -1170,7 +1184,7 @@ class LWGTrainer(object):
                 self.optimizer_D.step()
         for o, sn in zip(opts_, snaps):                     # capturing step() advanced the host mirrors only; nothing ran on the device
             o.t = sn[4]
-        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION}
+        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION, "tiles": ops.TRAIN_CONV_TILES}
         self._captured_lr = (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr)
         self._static_losses = (loss_G.detach(), None if loss_D is None else loss_D.detach())
         self._static_inp = self.inp
