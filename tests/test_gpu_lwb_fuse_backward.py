@@ -13,7 +13,7 @@ import torch.nn.functional as F
 from ipercore_amd import ops, synthetic
 from ipercore_amd.networks import NetworksFactory, generator_param_shapes
 from ipercore_amd.networks.training import FuseFn, TrainableGenerator
-from tests import lwbfuse_emu
+from tests import attn_flows, lwbfuse_emu
 from tests import parity_utils as pu
 from tests.gpu_checks import DEV, _cmp, _rand
 from tests.test_lwb_fuse_backward_cpu import GPU_BGF as BGF
@@ -55,10 +55,29 @@ def _reach(T, h, w, nsrc, batched):
 def test_fuse_backward_kernel(C, B, ns, h, w, S_, gated, batched, sw, so):
     """FuseFn against fp64 CPU autograd of the eager chain (F.interpolate align_corners=True -> F.grid_sample zeros -> fuse); the error
     measure and its bound are check_attention_backward's: max |d| / max(|ref| max, 1e-3 of the largest gradient) <= 5e-4."""
+    _fuse_forward_backward(C, B, ns, h, w, S_, gated, batched, sw, so, adversarial_flows(B, ns, S_, seed=7 + C + h, dtype=torch.float32),
+                           need_unreached=True)
+
+
+#               B, ns, S,  h,  w   (tests/attn_flows.py: aligned without resize; in-kernel resize, h != w, a last partial block)
+FAMILY_GEOMS = ((2, 2, 16, 16, 16), (2, 3, 40, 9, 13))
+FAMILY_CASES = [(f, g) for g in FAMILY_GEOMS for f in attn_flows.FAMILIES if attn_flows.family_allowed(f, g)]
+
+
+@pytest.mark.parametrize("family,geom", FAMILY_CASES, ids=[f"{f}-{attn_flows.geom_id(g)}" for f, g in FAMILY_CASES])
+def test_fuse_forward_backward_on_flow_families(family, geom):
+    """lwg_lwb_fuse_f32 and lwg_lwb_fuse_bwd_f32 on the flow families of tests/attn_flows.py (pixel centres, half pixels, the border
+    band, one texel for all pixels, single foreground pixels, very large finite flows), gated, batched sources, under
+    test_fuse_backward_kernel's assertions and bounds."""
+    B, ns, S_, h, w = geom
+    _fuse_forward_backward(64, B, ns, h, w, S_, True, 1, 1.0 / ns, 1.0, attn_flows.flows(family, B, ns, S_, S_, seed=0, size=(h, w)),
+                           need_unreached=False)
+
+
+def _fuse_forward_backward(C, B, ns, h, w, S_, gated, batched, sw, so, T, need_unreached):
     nsrc = B * ns if batched else ns
     tsf, src, g = _rand((B, h, w, C), 960), _rand((nsrc, h, w, C), 961), _rand((B, h, w, C), 962)
     gate = torch.sigmoid(_rand((B, h, w, C), 963)) if gated else None
-    T = adversarial_flows(B, ns, S_, seed=7 + C + h, dtype=torch.float32)
     # ---- fp64 reference
     leaves = [t.double().requires_grad_(True) for t in ((tsf, src, gate) if gated else (tsf, src))]
     Td = T.double().reshape(B * ns, S_, S_, 2)
@@ -81,7 +100,7 @@ def test_fuse_backward_kernel(C, B, ns, h, w, S_, gated, batched, sw, so):
     _cmp(y.detach(), yr.detach().float(), 3e-4, "fuse forward")        # check_attention_backward's forward bound (fp32 flow resize / tap coordinates)
     assert torch.equal(dl[0].grad, gd * so), "d_tsf is not dout * scale_o bit for bit"
     unreached = ~_reach(T, h, w, nsrc, batched)
-    assert w < 12 or unreached.any(), "the case has no source row out of every flow's reach"
+    assert not need_unreached or w < 12 or unreached.any(), "the case has no source row out of every flow's reach"
     assert (dl[1].grad.cpu()[unreached] == 0).all(), "a source row no flow reaches received a gradient"
     gmax = max(t.grad.abs().max().item() for t in leaves)
     errs = {}

@@ -10,10 +10,11 @@ import torch
 
 from ipercore_amd import ops, synthetic
 from ipercore_amd.networks import NetworksFactory, generator_param_shapes
+from tests import attn_flows
 from tests import lwbfuse_bf16_emu as emu16
 from tests import parity_utils as pu
 from tests.gpu_checks import DEV, _rand
-from tests.test_gpu_lwb_fuse_backward import CASES
+from tests.test_gpu_lwb_fuse_backward import CASES, FAMILY_CASES
 from tests.test_lwb_fuse_backward_cpu import adversarial_flows
 
 pytestmark = pytest.mark.gpu
@@ -30,8 +31,19 @@ def test_fuse_bf16_kernel(C, B, ns, h, w, S_, gated, batched, sw, so):
     (ii) against the fp64 eager chain, ref: |out - ref| <= 2^-8 |ref| + 3e-4 max(1, max|ref|) - twice the half-ulp of the bf16 store plus
          the bound test_fuse_backward_kernel holds the fp32 forward to (fp32 flow resize / tap coordinates on adversarial flows).
     The output buffer is followed by a guard band that must stay untouched (the last partial block)."""
+    _fuse_bf16_kernel(C, B, ns, h, w, S_, gated, batched, sw, so, adversarial_flows(B, ns, S_, seed=7 + C + h, dtype=torch.float32))
+
+
+@pytest.mark.parametrize("family,geom", FAMILY_CASES, ids=[f"{f}-{attn_flows.geom_id(g)}" for f, g in FAMILY_CASES])
+def test_fuse_bf16_kernel_on_flow_families(family, geom):
+    """lwg_lwb_fuse_bf16 on the flow families of tests/attn_flows.py, gated, batched sources, under test_fuse_bf16_kernel's two bounds
+    (the fp32 kernel on the upcast operands, the fp64 eager chain) and its guard band."""
+    B, ns, S_, h, w = geom
+    _fuse_bf16_kernel(64, B, ns, h, w, S_, True, 1, 1.0 / ns, 1.0, attn_flows.flows(family, B, ns, S_, S_, seed=0, size=(h, w)))
+
+
+def _fuse_bf16_kernel(C, B, ns, h, w, S_, gated, batched, sw, so, T):
     tsf, src, gate = emu16.kernel_case(C, B, ns, h, w, S_, gated, batched, _rand)
-    T = adversarial_flows(B, ns, S_, seed=7 + C + h, dtype=torch.float32)
     ref = emu16.eager_chain(tsf, src, T, gate, sw, so, bool(batched), dtype=torch.float64)
     n = B * h * w * C
     buf = torch.full((n + 4096,), -7.0, device=DEV, dtype=BF)
