@@ -178,6 +178,14 @@ int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d,
 int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
 int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, int* fmarks,
                                   int* fheavy, int* flight, int* fcounts, lwg_stream_t stream);
+/* The same at 8 x 8 SUB-TILES (csrc/lwg_conv_wino.h CW4Q_*): a block is eight of them, id = 8 * tile + 4 * (sub-tile row) + sub-tile
+ * column.  lwg_spade_skip_q8_lists_f32 writes the block lists and the 16 x 8 lists exactly as lwg_spade_skip_fine_lists_f32 does AND the 8 x 8 lists
+ * (qmarks, qheavy, qlight: 8 * B * tiles ints each, qcounts: 2 ints), still in two launches; a 16 x 8 mark is the OR of its two halves.
+ * lwg_conv2d_winograd4_q8_f32 takes the 8 x 8 lists: groups of eight heavy sub-tiles through the unchanged K loop.  Contract, launch-size rule and
+ * result (bit for bit) are those of lwg_conv2d_winograd4_fine_f32; which of the two a large launch takes is the caller's rule (ops.SPADE_SKIP_Q8). */
+int lwg_conv2d_winograd4_q8_f32(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
+int lwg_spade_skip_q8_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, int* fmarks,
+                                int* fheavy, int* flight, int* fcounts, int* qmarks, int* qheavy, int* qlight, int* qcounts, lwg_stream_t stream);
 /* That panel from the fp32 GEMM panel of the same convolution (arguments as lwg_winograd_panel_f32): U = G w G^T in fp64, rounded once. */
 int lwg_winograd4_panel_f32(const float* wpanel, float* upk, int Cin, int N, const int* tap9, lwg_stream_t stream);
 /* The same for every registered F(4x4, 3x3) panel of a training step in ONE launch (ops.PanelCache; the weights change every step): descs_dev = ndesc

@@ -76,6 +76,8 @@ _SIGS = {
     "lwg_spade_skip_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),
     "lwg_conv2d_winograd4_fine_f32": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
     "lwg_spade_skip_fine_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "lwg_conv2d_winograd4_q8_f32": (c_i, [ctypes.POINTER(LwgConvArgs), ctypes.POINTER(LwgConvLists), c_f]),
+    "lwg_spade_skip_q8_lists_f32": (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "lwg_winograd4_panel_f32": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_f]),
     "lwg_winograd4_panels_f32": (c_i, [c_f, c_i, c_i, c_f]),
     "lwg_conv2d_winograd4_f32_ws": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f]),

@@ -57,6 +57,12 @@ static_assert(W4_RS / CW4F_NSX >= CW4F_HW && (W4_RS / CW4F_NSX) % 4 == 0 && W4F_
 #define W4F_LOOP (2 * W4_KS * W4F_PLANE + 2 * W4_VS + W4_THREADS + 3 * W4F_PLANE)
 #define W4F_BIAS_OFF (W4F_LOOP > W4_MS ? W4F_LOOP : W4_MS)
 static_assert(CW4F_SX == 16 && CW4F_SY == 8 && CW4F_NS * CW4F_ROUNDS * 64 == W4_NQ * W4_THREADS, "sub-tile halo: four slots x six wave rounds = the staged elements");
+// Q8 (the 8 x 8 sub-tile form, lwg_conv_wino.h CW4Q_*): eight 10 x 10 sub-planes per channel plane in rows of CW4Q_RS floats (cw4q_lds_slot has the
+// layout and its bank-quad rule), FOUR halo pieces per thread and stage (a slot's 200 elements = four rounds of its wave)
+#define W4Q_NQ CW4Q_ROUNDS
+#define W4Q_LOOP (2 * W4_KS * CW4Q_PLANE + 2 * W4_VS + W4_THREADS + 3 * CW4Q_PLANE)
+#define W4Q_BIAS_OFF (W4Q_LOOP > W4_MS ? W4Q_LOOP : W4_MS)
+static_assert(CW4Q_NS == 8 && W4Q_NQ == 4 && CW4Q_RS % 4 == 0 && CW4Q_RS >= 16 + CW4Q_HW && (W4Q_BIAS_OFF + 64) * 4 <= 160 * 1024, "8 x 8 sub-tile halo: one slot per wave, inside the LDS");
 #ifndef LWG_W4_XCD
 #define LWG_W4_XCD 1         // XCD-aware block order (see the kernel): 0 = off (lab)
 #endif
@@ -140,19 +146,23 @@ __device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[NR]) {
 // behind the output transform - to slab z of the workspace, a.y + z M N (the host passes YC = N, ycoff = 0, no bias, no activation): the slab goes into
 // the BASE of the block's image buffer, the stores' offsets are the whole launch's.  The K loop is the same code on absolute stage indices; the panel's
 // strides stay the layer's.  lwg_splitk_finish_kernel adds the slabs in slice order and finishes.
-template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false, bool SPLIT = false>
+// Q8 (lwg_conv2d_winograd4_q8_f32; a LIST form beside FINE, never with it): 8 x 8 sub-tiles, a group = EIGHT heavy sub-tiles in the eight slots of
+// 2 x 2 patches; wave w stages slot w.  Besides what differs in FINE, the epilogue's reader lanes are mapped so that a wave's patches of a pass are
+// ONE slot's (cw4q_reader: its half waves take two output columns instead of two patch columns) - the same loads, sums and stores per output element.
+template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false, bool SPLIT = false, bool Q8 = false>
 __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists& sk) {
     static_assert(!FINE || (LIST && !SM && !TWO && LWG_W4_RDMAP), "the sub-tile form: a list-driven 8-wave launch");
+    static_assert(!Q8 || (LIST && !FINE && !SM && !TWO && !SPLIT && LWG_W4_RDMAP), "the 8 x 8 sub-tile form: a list-driven 8-wave launch");
     static_assert(!SPLIT || (SM && !LIST && EPI == LWG_EPI_NONE), "the split form: 4-wave blocks, plain epilogue");
-    constexpr int RS = W4_RS;                                // the halo planes' geometry in LDS
-    constexpr int PLANE = FINE ? W4F_PLANE : W4_PLANE;
+    constexpr int RS = Q8 ? CW4Q_RS : W4_RS;                 // the halo planes' geometry in LDS
+    constexpr int PLANE = Q8 ? CW4Q_PLANE : FINE ? W4F_PLANE : W4_PLANE;
     constexpr int RAW = W4_KS * PLANE;
     constexpr int DUMP_OFF = 2 * RAW + 2 * W4_VS;
-    constexpr int BIAS_OFF = FINE ? W4F_BIAS_OFF : W4_BIAS_OFF;
+    constexpr int BIAS_OFF = Q8 ? W4Q_BIAS_OFF : FINE ? W4F_BIAS_OFF : W4_BIAS_OFF;
     constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;          // (its 32 accumulator rows: gamma | beta of the SAME 16 channels, cw4_n0_spade_small)
     constexpr int NVP = SM && !SMS ? 2 : 1;                  // patches per reader thread and pass
     constexpr int NTH = SM ? 256 : W4_THREADS;               // threads per workgroup
-    constexpr int NQ = SM ? 5 : W4_NQ;                       // halo pieces per thread and stage
+    constexpr int NQ = SM ? 5 : W4_NQ + (Q8 ? W4Q_NQ - W4_NQ : 0);                      // halo pieces per thread and stage
     constexpr int NBV = SM ? 32 : W4_NB;                     // output channels per block
     constexpr int MSR = SM ? 36 : W4_MSR;                    // floats per (plane, patch) row of the exchange buffer
     constexpr int NHF = SM ? 2 : 1;                          // halves of the input transform per thread
@@ -172,13 +182,13 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     // LIST: the heavy entries' number (the ids below it run the K loop); a workgroup may own none
     // (counts and tile ids are clamped to the launch's grid: lists that do not belong to this launch must not become addresses)
     // (FINE: the entries are sub-tiles, nhe counts their groups)
-    const int nall = FINE ? cw4f_in_image_total(a.B, H, W) : g.tiles;
+    const int nall = Q8 ? cw4q_in_image_total(a.B, H, W) : FINE ? cw4f_in_image_total(a.B, H, W) : g.tiles;
     const int nht = LIST ? min(max(__builtin_amdgcn_readfirstlane(sk.counts[0]), 0), nall) : 0;
-    const int nhe = (FINE ? cw4f_groups(nht) : nht) * (N / NBV);
+    const int nhe = (Q8 ? cw4q_groups(nht) : FINE ? cw4f_groups(nht) : nht) * (N / NBV);
     // a launch whose tiles are ALL heavy (a frame batch without background) walks its blocks in the plain entry point's order - decided here, on the
     // device: the list order costs such a launch 0.3-3 % (profiles/spade_skip_ab_tool_list_order.txt)
     // (FINE: the entry point's second kernel runs the plain body for such a launch - this body always walks its lists)
-    const bool lst = FINE ? true : LIST ? nht < nall : false;
+    const bool lst = FINE || Q8 ? true : LIST ? nht < nall : false;
     const bool run = lst ? blk < nhe : true;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
     const int sbeg = SPLIT ? cw4_slice_begin((int)blockIdx.z, a.cshift) : 0;       // this workgroup's stages [sbeg, send): the layer's, or its slice
@@ -192,7 +202,30 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     int fs0 = 0, fs1 = 0;                                    // FINE: the sub-tiles of this wave's reader patches, passes 0 | 1 (-1: an empty slot)
     auto setup = [&](int id) {
         int cb, t;
-        if constexpr (FINE) {
+        if constexpr (Q8) {
+            int tids = tid;
+            asm volatile("" : "+v"(tids));
+            int slot;
+            cw_list_entry(id, N / NBV, slot, cb);
+            auto sub = [&](int k) {                          // the group's sub-tile in slot k (wave-uniform), -1: an empty slot
+                const int ix = cw4q_slot_index(slot, k, nht);
+                return ix < 0 ? -1 : min(max(__builtin_amdgcn_readfirstlane(sk.heavy[ix]), 0), CW4Q_NS * g.tiles - 1);
+            };
+            bk.n0 = cw_n0(cb, NBV);
+            // a wave stages the halo of ONE slot (cw4q_halo_elem: slot wid): one image descriptor
+            const int u = sub(wid);
+            int b, x0, y0;
+            cw4q_corner(g, max(u, 0), b, x0, y0);
+            bk.rx0 = cw_image_rsrc(a.x0, __builtin_amdgcn_readfirstlane(b), H, W, a.C0, 4u);
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) {
+                int s, j;
+                cw4q_halo_elem(tids + NTH * k, s, j);
+                bk.voff0[k] = cw4q_halo_voff(u >= 0, j, x0, y0, H, W, a.C0);
+            }
+            // the epilogue's (cw4q_reader): pass ph, this wave - slot 4 ph + wid / 2
+            fs0 = sub(wid >> 1), fs1 = sub(CW4Q_NSX + (wid >> 1));
+        } else if constexpr (FINE) {
             int tids = tid;
             asm volatile("" : "+v"(tids));
             int fsub[CW4F_NS], slot;                         // the group's sub-tiles
@@ -227,7 +260,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         } else {
             cw_block(o, id, cb, t);
         }
-        if constexpr (!FINE) {
+        if constexpr (!FINE && !Q8) {
         bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV));
         int tids = tid;                                      // (through an empty asm: the halo geometry is recomputed per block - hoisted out of the block
         asm volatile("" : "+v"(tids));                       //  loop it would sit in registers through the K loop)
@@ -242,7 +275,12 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
         const int i = tid + NTH * k;
-        if constexpr (FINE) {
+        if constexpr (Q8) {
+            int s, j, hy, hx, hq;
+            cw4q_halo_elem(i, s, j);
+            cw4q_halo_place(j, hy, hx, hq);
+            wst[k] = j < CW4Q_NEL ? 4 * hq * PLANE + cw4q_lds_slot(s) + hy * RS + hx : DUMP_OFF + tid;
+        } else if constexpr (FINE) {
             int s, j, hy, hx, hq;
             cw4f_halo_elem(i, s, j);
             cw4f_halo_place(j, hy, hx, hq);
@@ -297,6 +335,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         cw4f_patch_in_slot(pty, ptx, pby, pbx);
         pslot = W4F_SLOT(cw4f_slot_of_patch(pty, ptx));
     }
+    if constexpr (Q8) pby = 0, pbx = 0, pslot = cw4q_lds_patch(pty, ptx);
     unsigned dbs = (unsigned)(tc * PLANE + pslot + (4 * pby) * RS + 4 * pbx) >> 2;      // its 6 x 6 input patch inside raw[0] (float index; 16-byte aligned)
     asm volatile("" : "+v"(dbs));
     dbs <<= 2;
@@ -447,6 +486,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             mf(0, 4, true); ul(0, 2); tr(0, 2);
             mf(0, 5, true); halo(2);
             mf(0, 6, true); tr(0, 3);
+            if constexpr (Q8) halo(3);                       // (the fourth piece: lanes 0-7 of every wave)
             mf(0, 7, true); tr(0, 4);
             mf(0, 8, true); tr(0, 5);
             // k-pair 1: the rest of the column pass, the row pass
@@ -566,7 +606,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         iteration(s + 1, IntC<1>(), IntC<0>());
     }
     W4TS(2);
-    int eb = FINE ? 0 : bk.b, ex0 = FINE ? 0 : bk.x0, ey0 = FINE ? 0 : bk.y0;     // this block's coordinates (the state moves on to the next block below)
+    int eb = FINE || Q8 ? 0 : bk.b, ex0 = FINE || Q8 ? 0 : bk.x0, ey0 = FINE || Q8 ? 0 : bk.y0;     // this block's coordinates (the state moves on to the next block below)
     const int en0 = bk.n0;
     const int es0 = fs0, es1 = fs1;
     // epilogue.  (1) M A in registers: row q -> F[b] (b = 0..3, into acc[0..3]); the half row -> three partial sums (into acc[6..8]):
@@ -604,7 +644,9 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     int tide = tid;                                          // (through an empty asm per block: the epilogue's address arithmetic must not be hoisted out
     asm volatile("" : "+v"(tide));                           //  of the block loop - it would sit in registers through the K loop)
     const int lanee = tide & 63;
-    const int rb = wid & 3;                                  // reader: output column inside a patch (wave-uniform)
+    int rb = wid & 3;                                        // reader: output column inside a patch (wave-uniform; Q8: per half wave)
+    int p16q = 0;
+    if constexpr (Q8) cw4q_reader(wid, lanee, rb, p16q);
     // ... patch inside the pass and channel quad (and 32 + n4).  8-wave form: a ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27} and
     // {4-11, 16-19, 28-31} of either half wave (MI355X_MICROARCH: LDS), and a 16-byte slot of the exchange buffer lies in bank quad (patch + quad) % 16
     // (rows of 68 floats): a group reads the eight quads of patches a and a + 8 - sixteen distinct bank quads (eight lanes per patch in lane order
@@ -612,7 +654,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     // SM: patches lanee >> 3 and 8 + lanee >> 3, the block's only 32 channels; SM + SPADE: gamma | beta rows n4 and 16 + n4
     const unsigned l5 = (unsigned)lanee & 31u, gsel = (0x0FF0F00Fu >> l5) & 1u;                    // in the first group of its half wave?
     const int gidx = __builtin_popcount((gsel ? 0x0FF0F00Fu : 0xF00F0FF0u) & ((1u << l5) - 1u));   // its place in the group: 0..15
-    const int p16 = LWG_W4_RDMAP && !SM ? (wid >> 2) * 4 + 2 * (lanee >> 5) + (gsel ? 0 : 1) + 8 * (gidx >> 3) : (wid >> 2) * 8 + (lanee >> 3);
+    const int p16 = Q8 ? p16q : LWG_W4_RDMAP && !SM ? (wid >> 2) * 4 + 2 * (lanee >> 5) + (gsel ? 0 : 1) + 8 * (gidx >> 3) : (wid >> 2) * 8 + (lanee >> 3);
     const int n4 = SMS ? (lanee & 3) * 4 : LWG_W4_RDMAP && !SM ? (gidx & 7) * 4 : (lanee & 7) * 4;
     const int cbase = SMS ? (en0 >> 6) * 32 + ((en0 >> 4) & 1) * 16 : en0 >> 1;       // SPADE: the block's first output channel
     floatx4 mu, rs;
@@ -630,7 +672,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
         re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(esrc) + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
     };
-    if constexpr (!FINE) eframe();
+    if constexpr (!FINE && !Q8) eframe();
     const int chan = EPI == LWG_EPI_SPADE ? cbase + n4 : a.ycoff + en0 + n4;
     bool more = false;
     int nblk = blk;
@@ -639,6 +681,14 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         // (pass 0 needs no barrier in front of its writes: the last LDS reads of the K loop - the fragments of its last k-pair - were issued in front of
         // the last stage's barrier; pass 1 waits for the readers of pass 0)
         if (ph == 1) __syncthreads();
+        if constexpr (Q8) {
+            const int u = ph ? es1 : es0;
+            int ub;
+            cw4q_corner(g, max(u, 0), ub, ex0, ey0);
+            eb = __builtin_amdgcn_readfirstlane(ub);
+            if (u < 0) ex0 = W, ey0 = H;                     // an empty slot: every store out of range
+            eframe();
+        }
         if constexpr (FINE) {
             const int u = ph ? es1 : es0;
             int ub;
@@ -664,7 +714,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
         for (int hp = 0; hp < NVP; ++hp) {
             const int p = ph * 16 + (SMS ? lanee >> 2 : SM ? 8 * hp + (lanee >> 3) : p16);
-            const int ox = ex0 + 4 * (FINE ? (p & 7) % (CW4F_SX / 4) : (p & 7)) + rb, oyb = ey0 + 4 * (FINE ? (p >> 3) % (CW4F_SY / 4) : (p >> 3));
+            const int ox = ex0 + 4 * (Q8 ? (p & 7) % (CW4Q_SX / 4) : FINE ? (p & 7) % (CW4F_SX / 4) : (p & 7)) + rb;
+            const int oyb = ey0 + 4 * (Q8 ? (p >> 3) % (CW4Q_SY / 4) : FINE ? (p >> 3) % (CW4F_SY / 4) : (p >> 3));
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 vo[hp][i] = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan);
@@ -682,7 +733,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             W4TS(8);
             if constexpr (!SPLIT) {                          // (a split launch's workgroup has one block)
             nblk = blk + (int)gridDim.x;
-            if constexpr (FINE) more = nblk < nhe;
+            if constexpr (FINE || Q8) more = nblk < nhe;
             else if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
             else more = cw_has_block(o, nblk);
             setup(more ? nblk : blk);
@@ -770,7 +821,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
         // FINE: a light entry is a sub-tile, 128 pixels (cw4f_light_pixel): NPASS passes in all, NI at a time
         constexpr int NQD = EPI == LWG_EPI_SPADE ? 8 : 16;
-        constexpr int NPASS = (FINE ? CW4F_SX * CW4F_SY : 512) * NQD / W4_THREADS, NI = NPASS < 4 ? NPASS : 4;
+        constexpr int NPASS = (Q8 ? CW4Q_SX * CW4Q_SY : FINE ? CW4F_SX * CW4F_SY : 512) * NQD / W4_THREADS, NI = NPASS < 4 ? NPASS : 4;
         const int ncb = N / NBV;
         const int nend = nhe + min(max(__builtin_amdgcn_readfirstlane(sk.counts[1]), 0), nall - nht) * ncb;
         const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
@@ -780,10 +831,13 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         for (int id = cw_list_first_light((int)blockIdx.x, (int)gridDim.x, nhe); id < nend; id += (int)gridDim.x) {
             int slot, cb;
             cw_list_entry(id - nhe, ncb, slot, cb);
-            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), (FINE ? CW4F_NS : 1) * g.tiles - 1);
+            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), (Q8 ? CW4Q_NS : FINE ? CW4F_NS : 1) * g.tiles - 1);
             const int en0 = cw_n0(cb, NBV);
             int eb, ex0, ey0;
-            if constexpr (FINE) {
+            if constexpr (Q8) {
+                cw4q_corner(g, t, eb, ex0, ey0);
+                eb = __builtin_amdgcn_readfirstlane(eb);
+            } else if constexpr (FINE) {
                 cw4f_corner(g, t, eb, ex0, ey0);
                 eb = __builtin_amdgcn_readfirstlane(eb);
             } else {
@@ -806,6 +860,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
                     for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
                         if constexpr (FINE) cw4f_light_pixel(px, py);
+                        if constexpr (Q8) cw4q_light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, cbase + 4 * q4);
                         const unsigned vc = cw4_out_voff(ex0 + px, ey0 + py, H, W, N, en0 + 4 * q4);
                         gam[i] = cw_buf_load(rc, cw4_out_group(vc, 0, true), 0u);
@@ -829,6 +884,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
                     for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
                         if constexpr (FINE) cw4f_light_pixel(px, py);
+                        if constexpr (Q8) cw4q_light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, a.ycoff + en0 + 4 * q4);
                         o[i] = cw_buf_load(rc, vo[i], 0u);
                     }
@@ -863,6 +919,18 @@ __global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_kernel(
 template <int EPI>
 __global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
     if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < cw4f_in_image_total(a.B, a.H, a.W)) return;
+    w4_body<EPI, false, false, false>(a, LwgConvLists{});
+}
+
+// The 8 x 8 sub-tile form and its all-heavy companion (as the pair above)
+template <int EPI>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_q8_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) >= cw4q_in_image_total(a.B, a.H, a.W)) return;
+    w4_body<EPI, false, false, true, false, false, true>(a, sk);
+}
+template <int EPI>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_q8_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < cw4q_in_image_total(a.B, a.H, a.W)) return;
     w4_body<EPI, false, false, false>(a, LwgConvLists{});
 }
 
@@ -1080,4 +1148,20 @@ extern "C" int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* pa, const LwgCon
     if (e != 0) return e;
     return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, ldsp, stream, a, *pl)
                                   : cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, ldsp, stream, a, *pl);
+}
+
+// The 8 x 8 sub-tile form (include/lwg_hip.h): pl->heavy / light / counts = the 8 x 8 lists of lwg_spade_skip_q8_lists_f32; the same contract, the same
+// launch-size rule and the same result as the two forms above
+extern "C" int lwg_conv2d_winograd4_q8_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
+    if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
+    if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const LwgConvArgs& a = *pa;
+    const size_t lds = (size_t)(W4Q_BIAS_OFF + 64) * 4, ldsp = (size_t)(W4_BIAS_OFF + 64) * 4;
+    const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
+    const int e = a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_q8_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
+                                         : cw_launch_lists<lwg_conv_winograd4_q8_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
+    if (e != 0) return e;
+    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_q8_plain_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, ldsp, stream, a, *pl)
+                                  : cw_launch_lists<lwg_conv_winograd4_q8_plain_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, ldsp, stream, a, *pl);
 }

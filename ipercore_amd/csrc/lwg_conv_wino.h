@@ -194,6 +194,82 @@ CW_FN void cw4f_light_pixel(int& px, int& py) {
     py = p / CW4F_SX, px = p - py * CW4F_SX;
 }
 
+// ---- 8 x 8 sub-tile lists of F(4x4) (lwg_conv2d_winograd4_q8_f32, lwg_spade_skip_q8_lists_f32): the same scheme at half the sub-tile
+// width beside the 16 x 8 form - a block is CW4Q_NS = 8 sub-tiles of 2 x 2 patches, sub-tile u = 8 * block + 4 * (sub-tile row) + sub-tile column, a
+// group = eight heavy sub-tiles in the eight slots of the workgroup's 4 x 8 patches, slot of patch (pty, ptx) = 4 (pty / 2) + ptx / 2.  A 16 x 8
+// sub-tile is the sub-tiles 4 r + 2 c, 4 r + 2 c + 1 of its block: its window is the union of theirs, its mark their OR.
+#define CW4Q_SX 8
+#define CW4Q_SY 8
+#define CW4Q_NSX (32 / CW4Q_SX)
+#define CW4Q_NS (CW4Q_NSX * (16 / CW4Q_SY))
+#define CW4Q_HW (CW4Q_SX + 2)                // a sub-tile's halo: 10 x 10 pixels
+#define CW4Q_HH (CW4Q_SY + 2)
+#define CW4Q_NEL (CW4Q_HW * CW4Q_HH * 2)     // ... (pixel, channel quad) elements of a stage
+#define CW4Q_ROUNDS ((CW4Q_NEL + 63) / 64)   // ... in wave rounds of 64: four, all of ONE wave - wave w stages slot w (one image descriptor)
+CW_FN int cw4q_slot_of_patch(int pty, int ptx) { return (pty / (CW4Q_SY / 4)) * CW4Q_NSX + ptx / (CW4Q_SX / 4); }
+CW_FN void cw4q_patch_in_slot(int pty, int ptx, int& ly, int& lx) { ly = pty % (CW4Q_SY / 4), lx = ptx % (CW4Q_SX / 4); }
+CW_FN void cw4q_corner(const CwGrid& g, int u, int& b, int& x0, int& y0) {
+    const int t = u / CW4Q_NS, s = u - t * CW4Q_NS;
+    b = cw_image(g, t);
+    cw_corner(g, t - b * g.bx * g.by, 32, 16, x0, y0);
+    x0 += (s % CW4Q_NSX) * CW4Q_SX, y0 += (s / CW4Q_NSX) * CW4Q_SY;
+}
+CW_FN bool cw4q_in_image(int x0, int y0, int H, int W) { return x0 < W && y0 < H; }
+CW_FN int cw4q_in_image_total(int B, int H, int W) { return B * ((W + CW4Q_SX - 1) / CW4Q_SX) * ((H + CW4Q_SY - 1) / CW4Q_SY); }
+CW_FN int cw4q_groups(int nh) { return (nh + CW4Q_NS - 1) / CW4Q_NS; }
+CW_FN int cw4q_slot_index(int grp, int k, int nh) { return grp * CW4Q_NS + k < nh ? grp * CW4Q_NS + k : -1; }      // the heavy list's index, -1: empty
+// the classifier: which sub-tiles of the block at (x0, y0) hold the image pixel (x, y) in their window (bit s)
+CW_FN unsigned cw4q_reached(int x, int y, int x0, int y0, int d) {
+    unsigned m = 0;
+    for (int s = 0; s < CW4Q_NS; ++s) {
+        const int sx = x0 + (s % CW4Q_NSX) * CW4Q_SX, sy = y0 + (s / CW4Q_NSX) * CW4Q_SY;
+        m |= (x >= sx - d && x < sx + CW4Q_SX + d && y >= sy - d && y < sy + CW4Q_SY + d ? 1u : 0u) << s;
+    }
+    return m;
+}
+// the 16 x 8 marks from the 8 x 8 ones of a block (bit s: sub-tile s)
+CW_FN unsigned cw4q_marks16(unsigned m8) { return ((m8 | (m8 >> 1)) & 1u) | (((m8 >> 2) | (m8 >> 3)) & 1u) << 1 | (((m8 >> 4) | (m8 >> 5)) & 1u) << 2 | (((m8 >> 6) | (m8 >> 7)) & 1u) << 3; }
+// halo element i = tid + 512 k of a stage (wave (i / 64) % 8, its round k = 0..3) -> its slot - the wave - and its element j inside the slot's halo
+// (j >= CW4Q_NEL: none - the last 56 lanes of round 3)
+CW_FN void cw4q_halo_elem(int i, int& slot, int& j) { slot = (i >> 6) & 7, j = (i >> 9) * 64 + (i & 63); }
+CW_FN void cw4q_halo_place(int j, int& hy, int& hx, int& hq) {
+    const int pix = j >> 1;
+    hq = j & 1, hy = pix / CW4Q_HW, hx = pix - hy * CW4Q_HW;
+}
+CW_FN unsigned cw4q_halo_voff(bool present, int j, int x0, int y0, int H, int W, int C) {
+    int hy, hx, hq;
+    cw4q_halo_place(j, hy, hx, hq);
+    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+    return present && j < CW4Q_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W ? (unsigned)((gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
+}
+// a slot's sub-plane inside a channel plane of the LDS halo buffer (floats): rows of CW4Q_RS floats, two slots side by side 16 floats apart, four slot
+// rows of ten halo rows with 0 / 8 / 16 floats between them - so that the sixteen patches of either ds_read_b128 lane group of the input transform
+// (lanes 0-3, 12-15, 20-27 | the rest of a half wave, lane = patch) start in sixteen distinct bank quads (tests/test_spade_skip_q8_cpu.py enumerates them;
+// four slots side by side in rows of 48 - 60 floats have no such padding: a patch row is a multiple of four bank quads)
+#define CW4Q_RS 28
+#define CW4Q_PLANE (4 * CW4Q_HH * CW4Q_RS + 24 + 4)        // + 4: 4 PLANE = 16 mod 32, the two channel quads of a pixel fall into different banks
+CW_FN int cw4q_lds_slot(int s) { const int r = s >> 1; return r * (CW4Q_HH * CW4Q_RS) + 4 * r * (r - 1) + (s & 1) * 16; }
+CW_FN int cw4q_lds_patch(int pty, int ptx) {               // the first float of patch (pty, ptx)'s 6 x 6 input window inside a channel plane
+    int ly, lx;
+    cw4q_patch_in_slot(pty, ptx, ly, lx);
+    return cw4q_lds_slot(cw4q_slot_of_patch(pty, ptx)) + 4 * ly * CW4Q_RS + 4 * lx;
+}
+// the epilogue's reader: wave wid, lane -> its output column rb inside a patch and its patch inside the pass (0..15: patch row p / 8 of the pass, patch
+// column p % 8).  A wave's patches of a pass are the 2 x 2 of ONE slot, 4 pass + wid / 2 - image, corner, mean / rstd and the buffer descriptors stay
+// wave-uniform -, its half waves own the output columns 2 (wid % 2) and + 1 (the 16 x 8 form: one column per wave, a slot's 4 x 2 patches per wave pair).
+// gsel / gidx: the lane's ds_read_b128 lane group and its place in it, as in the plain reader - a group reads the eight channel quads of patches a, a + 8
+CW_FN void cw4q_reader(int wid, int lane, int& rb, int& p16) {
+    const unsigned l5 = (unsigned)lane & 31u, gsel = (0x0FF0F00Fu >> l5) & 1u;
+    const int gidx = __builtin_popcount((gsel ? 0x0FF0F00Fu : 0xF00F0FF0u) & ((1u << l5) - 1u));
+    rb = 2 * (wid & 1) + (lane >> 5);
+    p16 = 2 * (wid >> 1) + (gsel ? 0 : 1) + 8 * (gidx >> 3);
+}
+// a light sub-tile's elements from cw4_light_elem's (px, py) of the first CW4Q_SX * CW4Q_SY pixels
+CW_FN void cw4q_light_pixel(int& px, int& py) {
+    const int p = py * 32 + px;
+    py = p / CW4Q_SX, px = p - py * CW4Q_SX;
+}
+
 // ---- split-K launches of F(4x4) (lwg_conv2d_winograd4_f32_ws): the training step's one-sample launches.  The 4-wave form's blocks
 // (32 x 16 pixels x 32 channels) x `slices` workgroups, slice z owns the K stages [z sps, min((z + 1) sps, nst)) of its block - sps even, so every
 // slice is an even number of stages - and writes its raw partial outputs to the dense (M, N) slab z of the workspace; the finishing kernel of the

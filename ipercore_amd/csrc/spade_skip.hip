@@ -111,9 +111,8 @@ __device__ __forceinline__ void sk_for_marks(const int* __restrict__ marks, int 
         }
     for (; i < i1; ++i) f(i, marks[i]);
 }
-__global__ __launch_bounds__(1024) void lwg_spade_skip_scan2_kernel(SkScanJob j0, SkScanJob j1) {
+__device__ __forceinline__ void sk_scan_job(const SkScanJob j) {
     __shared__ int ph[1024], pl[1024];
-    const SkScanJob j = blockIdx.x == 0 ? j0 : j1;
     const int tid = threadIdx.x, n = j.n, per = ((n + 1023) / 1024 + 3) & ~3;
     const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
     const bool vec = (reinterpret_cast<size_t>(j.marks) & 15) == 0;
@@ -135,6 +134,52 @@ __global__ __launch_bounds__(1024) void lwg_spade_skip_scan2_kernel(SkScanJob j0
     if (tid == 1023) {
         j.counts[0] = ph[1023];
         j.counts[1] = pl[1023];
+    }
+}
+__global__ __launch_bounds__(1024) void lwg_spade_skip_scan2_kernel(SkScanJob j0, SkScanJob j1) {
+    const SkScanJob j = blockIdx.x == 0 ? j0 : j1;
+    sk_scan_job(j);
+}
+// ... three of them: the blocks, the 16 x 8 and the 8 x 8 sub-tiles
+__global__ __launch_bounds__(1024) void lwg_spade_skip_scan3_kernel(SkScanJob j0, SkScanJob j1, SkScanJob j2) {
+    const SkScanJob j = blockIdx.x == 0 ? j0 : blockIdx.x == 1 ? j1 : j2;
+    sk_scan_job(j);
+}
+
+// The classifier at 8 x 8 sub-tiles (lwg_conv_wino.h: CW4Q_*): the pass of lwg_spade_skip_mark_fine_kernel with eight window bits per pixel; the 16 x 8
+// marks are the ORs of their two halves (cw4q_marks16), the block's mark the OR of all - every granularity from ONE evaluation of each window pixel.
+// qmarks[CW4Q_NS t + s] as fmarks: 1 heavy, 0 light, 2 wholly outside the image.
+__global__ __launch_bounds__(256) void lwg_spade_skip_mark_q8_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks,
+                                                                     int* __restrict__ fmarks, int* __restrict__ qmarks) {
+    const CwGrid g = cw_grid(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
+    const int t = blockIdx.x, b = cw_image(g, t);
+    int x0, y0;
+    cw_corner(g, t - b * g.bx * g.by, SK_EX, SK_EY, x0, y0);
+    const CwWindow win = cw_block_window(x0, y0, SK_EX, SK_EY, d, h, w);
+    const int ww = win.x1 - win.x0, n = ww * (win.y1 - win.y0);
+    unsigned mine = 0;                                        // bit s: 8 x 8 sub-tile s, bit CW4Q_NS: the block
+    for (int s = 0; s < ns; ++s) {
+        const float2* Ts = T + ((size_t)b * ns + s) * h * w;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int yy = i / ww, y = win.y0 + yy, x = win.x0 + (i - yy * ww);
+            float wt[4];
+            int tx0, ty0;
+            lwb_taps_of(Ts[(size_t)y * w + x], w, h, wt, tx0, ty0);
+            if (lwb_tap_in_image(tx0, ty0, w, h)) mine |= (1u << CW4Q_NS) | cw4q_reached(x, y, x0, y0, d);
+        }
+    }
+    unsigned all = 0;
+    for (int s = 0; s <= CW4Q_NS; ++s) all |= __syncthreads_or((int)((mine >> s) & 1u)) ? 1u << s : 0u;
+    const int s = threadIdx.x;
+    if (s < CW4Q_NS) {
+        const bool in = cw4q_in_image(x0 + (s % CW4Q_NSX) * CW4Q_SX, y0 + (s / CW4Q_NSX) * CW4Q_SY, h, w);
+        qmarks[CW4Q_NS * t + s] = in ? (int)((all >> s) & 1u) : 2;
+    } else if (s < CW4Q_NS + CW4F_NS) {
+        const int f = s - CW4Q_NS;
+        const bool in = cw4f_in_image(x0 + (f % CW4F_NSX) * CW4F_SX, y0 + (f / CW4F_NSX) * CW4F_SY, h, w);
+        fmarks[CW4F_NS * t + f] = in ? (int)((cw4q_marks16(all) >> f) & 1u) : 2;
+    } else if (s == CW4Q_NS + CW4F_NS) {
+        marks[t] = (int)((all >> CW4Q_NS) & 1u);
     }
 }
 
@@ -159,5 +204,23 @@ extern "C" int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, in
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(lwg_spade_skip_mark_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks);
     hipLaunchKernelGGL(lwg_spade_skip_scan_kernel, dim3(1), dim3(1024), 0, stream, marks, (int)tiles, heavy, light, counts);
+    return (int)hipGetLastError();
+}
+
+// The block lists, the 16 x 8 lists (both as lwg_spade_skip_fine_lists_f32 leaves them) AND the 8 x 8 lists (qmarks, qheavy, qlight: 8 * B * tiles ints
+// each, qcounts: 2 ints) in the same two launches
+extern "C" int lwg_spade_skip_q8_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
+                                           int* fmarks, int* fheavy, int* flight, int* fcounts, int* qmarks, int* qheavy, int* qlight, int* qcounts,
+                                           lwg_stream_t stream_) {
+    if (!T || !marks || !heavy || !light || !counts || !fmarks || !fheavy || !flight || !fcounts || !qmarks || !qheavy || !qlight || !qcounts || B <= 0 ||
+        ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64)
+        return (int)hipErrorInvalidValue;
+    const long long tiles = cw_total_blocks(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
+    if (tiles * CW4Q_NS >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(lwg_spade_skip_mark_q8_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks, fmarks,
+                       qmarks);
+    hipLaunchKernelGGL(lwg_spade_skip_scan3_kernel, dim3(3), dim3(1024), 0, stream, SkScanJob{marks, (int)tiles, heavy, light, counts},
+                       SkScanJob{fmarks, (int)tiles * CW4F_NS, fheavy, flight, fcounts}, SkScanJob{qmarks, (int)tiles * CW4Q_NS, qheavy, qlight, qcounts});
     return (int)hipGetLastError();
 }

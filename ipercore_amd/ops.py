@@ -436,12 +436,20 @@ SPADE_SKIP_D_BF16 = (1, 2)      # ... in the "bf16" mode (lwg_conv2d_nhwc_bf16_h
 
 SPADE_SKIP_FINE = True  # ... at the granularity of 16 x 8 sub-tiles (four per block) where ``spade_skip_fine_apply`` says so; False: block lists everywhere
 
+SPADE_SKIP_Q8 = True    # ... and at 8 x 8 sub-tiles (eight per block, lwg_conv2d_winograd4_q8_f32) where ``spade_skip_q8_apply`` says so:
+SPADE_SKIP_Q8_MIN = 640         # ... launches of at least this many (in-image block, column block) entries - the smallest measured, still a gain
+                                #  - ...
+SPADE_SKIP_Q8_MAX_HW = 64 * 64  # ... on feature maps of at most this many pixels: at 128^2 and 256^2 the body is a small part of the frame, the launch
+                                # is mostly light entries, and twice as many of half the size cost more than the smaller heavy share returns
+
 _LISTS_APPLY = {}
 
 
 class SkipLists(tuple):
-    """``spade_skip_lists``'s result: the block-level (heavy, light, counts), and as ``.fine`` the sub-tile-level triple from the same launches."""
+    """``spade_skip_lists``'s result: the block-level (heavy, light, counts), and as ``.fine`` the sub-tile-level triple from the same launches; as
+    ``.fine8`` the 8 x 8 triple where a launch on these frames can take it (``spade_skip_q8_lists_apply``), else None."""
     fine = None
+    fine8 = None
 
 
 def spade_skip_fine_apply(x0):
@@ -449,18 +457,43 @@ def spade_skip_fine_apply(x0):
     return SPADE_SKIP_FINE
 
 
+def spade_skip_q8_apply(x0, ncb):
+    """Does a list-driven launch on this input with ncb column blocks take the 8 x 8 lists?  A rule on the configuration and the launch's size only."""
+    B, H, W = x0.shape[:3]
+    return SPADE_SKIP_FINE and SPADE_SKIP_Q8 and H * W <= SPADE_SKIP_Q8_MAX_HW and B * ((H + 15) // 16) * ((W + 31) // 32) * ncb >= SPADE_SKIP_Q8_MIN
+
+
+def spade_skip_q8_lists_apply(tiles, h, w):
+    """Are the 8 x 8 lists built for a frame batch of this many blocks at h x w?  Where a launch of up to eight column blocks (N <= 512) could take them."""
+    return SPADE_SKIP_FINE and SPADE_SKIP_Q8 and CONV_PRECISION == "winograd" and h * w <= SPADE_SKIP_Q8_MAX_HW and tiles * 8 >= SPADE_SKIP_Q8_MIN
+
+
 def spade_skip_lists(flow, d):
     """The heavy / light tile lists of one frame batch for ``conv2d(..., lists=)`` from its resized flows (B, ns, h, w, 2): two launches, everything
     stays in device memory (lwg_spade_skip_fine_lists_f32).  Returns (heavy, light, counts) int32 tensors of the 32 x 16 blocks - a ``SkipLists``,
-    whose ``.fine`` holds the same triple for the 16 x 8 sub-tiles."""
+    whose ``.fine`` holds the same triple for the 16 x 8 sub-tiles and ``.fine8`` the one for the 8 x 8 sub-tiles (lwg_spade_skip_q8_lists_f32, the same
+    two launches) where ``spade_skip_q8_lists_apply`` says so."""
     B, ns, h, w, two = flow.shape
     assert two == 2 and flow.dtype == torch.float32
     tiles = B * ((h + 15) // 16) * ((w + 31) // 32)
-    buf = torch.empty(15 * tiles + 4, device=flow.device, dtype=torch.int32)
+    q8 = spade_skip_q8_lists_apply(tiles, h, w)
+    buf = torch.empty((39 if q8 else 15) * tiles + 8, device=flow.device, dtype=torch.int32)
+    if q8:
+        qb, buf = buf[:24 * tiles], buf[24 * tiles:]         # (marks first: 16-byte aligned)
+        qmarks, qheavy, qlight = qb[:8 * tiles], qb[8 * tiles:16 * tiles], qb[16 * tiles:]
     fmarks, fheavy, flight = buf[:4 * tiles], buf[4 * tiles:8 * tiles], buf[8 * tiles:12 * tiles]      # (the sub-tiles' marks first: 16-byte aligned)
     bb = buf[12 * tiles:]
-    marks, heavy, light, counts, fcounts = bb[:tiles], bb[tiles:2 * tiles], bb[2 * tiles:3 * tiles], bb[3 * tiles:3 * tiles + 2], bb[3 * tiles + 2:]
+    marks, heavy, light, counts, fcounts = bb[:tiles], bb[tiles:2 * tiles], bb[2 * tiles:3 * tiles], bb[3 * tiles:3 * tiles + 2], bb[3 * tiles + 2:3 * tiles + 4]
     i32 = torch.int32
+    if q8:
+        qcounts = bb[3 * tiles + 4:3 * tiles + 6]
+        _lib.check(_lib.lib().lwg_spade_skip_q8_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
+                                                          _ptr(counts, i32), _ptr(fmarks, i32), _ptr(fheavy, i32), _ptr(flight, i32), _ptr(fcounts, i32),
+                                                          _ptr(qmarks, i32), _ptr(qheavy, i32), _ptr(qlight, i32), _ptr(qcounts, i32), _stream()),
+                   "lwg_spade_skip_q8_lists_f32")
+        out = SkipLists((heavy, light, counts))
+        out.fine, out.fine8 = (fheavy, flight, fcounts), (qheavy, qlight, qcounts)
+        return out
     _lib.check(_lib.lib().lwg_spade_skip_fine_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
                                                         _ptr(counts, i32), _ptr(fmarks, i32), _ptr(fheavy, i32), _ptr(flight, i32), _ptr(fcounts, i32),
                                                         _stream()), "lwg_spade_skip_fine_lists_f32")
@@ -631,9 +664,14 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
                 if fine:
                     sl, cal = lists
                     fine = sl.fine is not None and spade_skip_fine_apply(x0)
-                    lists = tuple(sl.fine if fine else sl) + (cal,)
+                    q8 = fine and sl.fine8 is not None and spade_skip_q8_apply(x0, spec.N // 64)
+                    lists = tuple(sl.fine8 if q8 else sl.fine if fine else sl) + (cal,)
+                else:
+                    q8 = False
                 ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32), _ptr(lists[3]))
-                if fine:
+                if q8:
+                    _lib.check(_lib.lib().lwg_conv2d_winograd4_q8_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_q8_f32")
+                elif fine:
                     _lib.check(_lib.lib().lwg_conv2d_winograd4_fine_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_fine_f32")
                 else:
                     _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
