@@ -169,7 +169,7 @@ int lwg_conv2d_winograd4_list_applies(const LwgConvArgs* args);
  * of its block's window - the block grown by d pixels, clipped to the image - has an in-image tap of any source by lwg_lwb_attention_x's own predicate
  * (csrc/lwg_lwb_taps.h).  marks: B * tiles ints of scratch; heavy, light: B * tiles ints each; counts: 2 ints.  Two launches, a deterministic scan. */
 int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, lwg_stream_t stream);
-/* The same at the granularity of 16 x 8 SUB-TILES (csrc/lwg_conv_wino.h CW4F_*): a 32 x 16 block is four sub-tiles, sub-tile id =
+/* The same at the granularity of 16 x 8 SUB-TILES (csrc/lwg_conv_wino.h Cw4F = Cw4Sub<16, 8>): a 32 x 16 block is four sub-tiles, sub-tile id =
  * 4 * tile + 2 * (sub-tile row) + sub-tile column; a sub-tile is heavy / light by the same rule applied to ITS window, sub-tiles wholly outside the image
  * are in neither list.  lwg_spade_skip_fine_lists_f32 writes the block lists as above AND the sub-tile lists (fmarks, fheavy, flight: 4 * B * tiles ints
  * each, fcounts: 2 ints) in the same two launches; a block's mark is the OR of its sub-tiles' marks.  lwg_conv2d_winograd4_fine_f32 takes the SUB-TILE
@@ -178,7 +178,7 @@ int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d,
 int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* args, const LwgConvLists* lists, lwg_stream_t stream);
 int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts, int* fmarks,
                                   int* fheavy, int* flight, int* fcounts, lwg_stream_t stream);
-/* The same at 8 x 8 SUB-TILES (csrc/lwg_conv_wino.h CW4Q_*): a block is eight of them, id = 8 * tile + 4 * (sub-tile row) + sub-tile
+/* The same at 8 x 8 SUB-TILES (csrc/lwg_conv_wino.h Cw4Q = Cw4Sub<8, 8>): a block is eight of them, id = 8 * tile + 4 * (sub-tile row) + sub-tile
  * column.  lwg_spade_skip_q8_lists_f32 writes the block lists and the 16 x 8 lists exactly as lwg_spade_skip_fine_lists_f32 does AND the 8 x 8 lists
  * (qmarks, qheavy, qlight: 8 * B * tiles ints each, qcounts: 2 ints), still in two launches; a 16 x 8 mark is the OR of its two halves.
  * lwg_conv2d_winograd4_q8_f32 takes the 8 x 8 lists: groups of eight heavy sub-tiles through the unchanged K loop.  Contract, launch-size rule and

@@ -654,9 +654,9 @@ __global__ __launch_bounds__(256, (WAVES_M == 1 || NDY * NDX == 9) ? 2 : 3) void
     bool light = false;
     if constexpr (MODE == HR2_LIST) {
         static_assert(WAVES_M == 1 && NDY == 3 && NDX == 3 && (EPI == LWG_EPI_NONE || EPI == LWG_EPI_SPADE), "the list form: what the SPADE launches reach");
-        static_assert(BN == HRL_BN && TM == HRL_TM && CW4F_SX == 16 && CW4F_SY == 8, "the workgroup's pixel block is the classifier's sub-tile");
+        static_assert(BN == HRL_BN && TM == HRL_TM && Cw4F::SX == 16 && Cw4F::SY == 8, "the workgroup's pixel block is the classifier's sub-tile");
         const LwgConvLists& sk = hr2_lists(sk_...);
-        const int total = cw4f_in_image_total(a.B, a.OH, a.OW);
+        const int total = Cw4F::in_image_total(a.B, a.OH, a.OW);
         int e, nh, nl, idx;
         hrl_entry(lid, tiles_n, e, tile_n);
         hrl_counts(__builtin_amdgcn_readfirstlane(sk.counts[0]), __builtin_amdgcn_readfirstlane(sk.counts[1]), total, nh, nl);

@@ -19,6 +19,7 @@
 // Rounding: relative L2 error against fp64 ~14-20x the direct fp32 convolution's (3e-6; tools/winograd_study.py --f43): fp32-grade, NOT the direct kernel's
 // and not the F(2x2, 3x3) kernel's bits.  A frame's result does not depend on the batch it is launched in (per-image work in a fixed order).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "lwg_common.h"
 #include "lwg_conv_wino.h"
 
@@ -48,21 +49,24 @@
 #define W4_NPL 28                                // planes: rows 0..3 x 4 output columns, rows 4 / 5: 2 halves x 3 partial sums
 #define W4_MS (W4_NPL * 16 * W4_MSR)             // one pass = 16 patches
 #define W4_BIAS_OFF (W4_LOOP > W4_MS ? W4_LOOP : W4_MS)          // the block's 64 bias values, behind both uses of the LDS
-// FINE (the sub-tile form, lwg_conv_wino.h CW4F_*): the SAME rows of W4_RS = 40 floats - the 18-pixel halo rows of two slots side by side, 20 floats
-// apart, the lower two slots ten rows down: a channel plane is 20 rows + 4 (4 PLANE = 16 mod 32 as above).  The patches (pty, ptx 0-3 | 4-7) of a
-// ds_read_b128 lane group start in rows 0, 4, 10, 14 = bank quads 0, 8, 4, 12 (+ ptx % 4): sixteen distinct ones.
-#define W4F_SLOT(s) (((s) / CW4F_NSX) * CW4F_HH * W4_RS + ((s) % CW4F_NSX) * (W4_RS / CW4F_NSX))
-#define W4F_PLANE (CW4F_NS / CW4F_NSX * CW4F_HH * W4_RS + 4)
-static_assert(W4_RS / CW4F_NSX >= CW4F_HW && (W4_RS / CW4F_NSX) % 4 == 0 && W4F_PLANE >= W4_PLANE, "two sub-tile halo rows per LDS row");
-#define W4F_LOOP (2 * W4_KS * W4F_PLANE + 2 * W4_VS + W4_THREADS + 3 * W4F_PLANE)
-#define W4F_BIAS_OFF (W4F_LOOP > W4_MS ? W4F_LOOP : W4_MS)
-static_assert(CW4F_SX == 16 && CW4F_SY == 8 && CW4F_NS * CW4F_ROUNDS * 64 == W4_NQ * W4_THREADS, "sub-tile halo: four slots x six wave rounds = the staged elements");
-// Q8 (the 8 x 8 sub-tile form, lwg_conv_wino.h CW4Q_*): eight 10 x 10 sub-planes per channel plane in rows of CW4Q_RS floats (cw4q_lds_slot has the
-// layout and its bank-quad rule), FOUR halo pieces per thread and stage (a slot's 200 elements = four rounds of its wave)
-#define W4Q_NQ CW4Q_ROUNDS
-#define W4Q_LOOP (2 * W4_KS * CW4Q_PLANE + 2 * W4_VS + W4_THREADS + 3 * CW4Q_PLANE)
-#define W4Q_BIAS_OFF (W4Q_LOOP > W4_MS ? W4Q_LOOP : W4_MS)
-static_assert(CW4Q_NS == 8 && W4Q_NQ == 4 && CW4Q_RS % 4 == 0 && CW4Q_RS >= 16 + CW4Q_HW && (W4Q_BIAS_OFF + 64) * 4 <= 160 * 1024, "8 x 8 sub-tile halo: one slot per wave, inside the LDS");
+// The halo planes' placement in LDS per sub-tile geometry (lwg_conv_wino.h: Cw4Sub; void: the plain block above).
+// Cw4F (16 x 8): the SAME rows of W4_RS = 40 floats - the 18-pixel halo rows of two slots side by side, 20 floats apart, the lower two slots ten rows
+// down: a channel plane is 20 rows + 4 (4 PLANE = 16 mod 32 as above).  The patches (pty, ptx 0-3 | 4-7) of a ds_read_b128 lane group start in rows
+// 0, 4, 10, 14 = bank quads 0, 8, 4, 12 (+ ptx % 4): sixteen distinct ones.
+// Cw4Q (8 x 8): eight 10 x 10 sub-planes per channel plane in rows of Cw4QLds::RS floats (Cw4QLds has the layout and its bank-quad rule), FOUR halo
+// pieces per thread and stage (a slot's 200 elements = four rounds of its wave)
+template <typename G> struct W4Lds { static constexpr int RS = W4_RS, PLN = W4_PLANE; };
+template <> struct W4Lds<Cw4F> {
+    static constexpr int RS = W4_RS, PLN = Cw4F::NS / Cw4F::NSX * Cw4F::HH * W4_RS + 4;
+    CW_FN int slot(int s) { return (s / Cw4F::NSX) * Cw4F::HH * W4_RS + (s % Cw4F::NSX) * (W4_RS / Cw4F::NSX); }
+};
+template <> struct W4Lds<Cw4Q> : Cw4QLds {};
+// the block's 64 bias values, behind both uses of the LDS (the K loop's buffers as W4_LOOP counts them | the exchange buffer), in floats
+template <typename G> constexpr int w4_loop = (2 * W4_KS + 3) * W4Lds<G>::PLN + 2 * W4_VS + W4_THREADS;
+template <typename G> constexpr int w4_bias_off = w4_loop<G> > W4_MS ? w4_loop<G> : W4_MS;
+static_assert(w4_bias_off<void> == W4_BIAS_OFF && W4_RS / Cw4F::NSX >= Cw4F::HW && (W4_RS / Cw4F::NSX) % 4 == 0 && W4Lds<Cw4F>::PLN >= W4_PLANE, "two sub-tile halo rows per LDS row");
+static_assert(Cw4F::SX == 16 && Cw4F::SY == 8 && Cw4F::NS * Cw4F::ROUNDS * 64 == W4_NQ * W4_THREADS, "sub-tile halo: four slots x six wave rounds = the staged elements");
+static_assert(Cw4Q::NS == 8 && Cw4Q::ROUNDS == 4 && Cw4QLds::RS % 4 == 0 && Cw4QLds::RS >= 16 + Cw4Q::HW && (w4_bias_off<Cw4Q> + 64) * 4 <= 160 * 1024, "8 x 8 sub-tile halo: one slot per wave, inside the LDS");
 #ifndef LWG_W4_XCD
 #define LWG_W4_XCD 1         // XCD-aware block order (see the kernel): 0 = off (lab)
 #endif
@@ -137,32 +141,34 @@ __device__ __forceinline__ void w4_act16(int act, floatx4 (&o)[NR]) {
 // memory (lwg_conv_wino.h: cw_list_entry) - the heavy entries through the K loop and epilogue below, untouched, then the light ones from the calibration
 // frame in a streaming loop without LDS.  Heavy first: a static walk that mixed them would leave most workgroups waiting for the few
 // that drew the heavy blocks of a clustered body.
-// FINE (lwg_conv2d_winograd4_fine_f32; a LIST form): the lists hold 16 x 8 sub-tiles; a workgroup's "block" is a GROUP of four heavy sub-tiles - any
-// frames, any positions - in the four slots of its 4 x 8 patches (cw4f_slot_of_patch).  Only the halo staging (four 18 x 10 sub-planes per channel
-// plane, a wave stages the halo of one slot = one image descriptor), the transform's base addresses and the epilogue's output bases (the reader's slot is
-// wave-uniform per pass) differ; the K loop is the same code.
+// GEO (the lists' granularity; void: 32 x 16 blocks, or no lists.  SUB = not void, always a LIST form): the lists hold the sub-tiles of one geometry
+// (lwg_conv_wino.h: Cw4Sub); a workgroup's "block" is a GROUP of NS heavy sub-tiles - any frames, any positions - in the NS slots of its 4 x 8 patches
+// (slot_of_patch).  Only the halo staging (NS sub-planes per channel plane, a wave stages the halo of one slot = one image descriptor), the transform's
+// base addresses and the epilogue's output bases (the reader's slot is wave-uniform per pass) differ; the K loop is the same code.
+//   FINE = Cw4F (lwg_conv2d_winograd4_fine_f32): 16 x 8 sub-tiles, a group = four of them in four slots of 4 x 2 patches; waves 2 s, 2 s + 1 stage slot s.
+//   Q8 = Cw4Q (lwg_conv2d_winograd4_q8_f32): 8 x 8 sub-tiles, a group = EIGHT in the eight slots of 2 x 2 patches; wave w stages slot w.  Besides what
+// differs in FINE, the epilogue's reader lanes are mapped so that a wave's patches of a pass are ONE slot's (cw4_reader8: its half waves take two output
+// columns instead of two patch columns) - the same loads, sums and stores per output element.
 // SPLIT (lwg_conv2d_winograd4_f32_ws: the training step's one-sample launches; the 4-wave form, plain epilogue): ONE block per workgroup, blockIdx.z owns
 // the K stages [z a.cshift, (z + 1) a.cshift) of it (lwg_conv_wino.h: cw4_slice_begin / _end; an even number of them) and writes its raw partial outputs -
 // behind the output transform - to slab z of the workspace, a.y + z M N (the host passes YC = N, ycoff = 0, no bias, no activation): the slab goes into
 // the BASE of the block's image buffer, the stores' offsets are the whole launch's.  The K loop is the same code on absolute stage indices; the panel's
 // strides stay the layer's.  lwg_splitk_finish_kernel adds the slabs in slice order and finishes.
-// Q8 (lwg_conv2d_winograd4_q8_f32; a LIST form beside FINE, never with it): 8 x 8 sub-tiles, a group = EIGHT heavy sub-tiles in the eight slots of
-// 2 x 2 patches; wave w stages slot w.  Besides what differs in FINE, the epilogue's reader lanes are mapped so that a wave's patches of a pass are
-// ONE slot's (cw4q_reader: its half waves take two output columns instead of two patch columns) - the same loads, sums and stores per output element.
-template <int EPI, bool TWO, bool SM, bool LIST, bool FINE = false, bool SPLIT = false, bool Q8 = false>
+template <int EPI, bool TWO, bool SM, bool LIST, typename GEO = void, bool SPLIT = false>
 __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists& sk) {
-    static_assert(!FINE || (LIST && !SM && !TWO && LWG_W4_RDMAP), "the sub-tile form: a list-driven 8-wave launch");
-    static_assert(!Q8 || (LIST && !FINE && !SM && !TWO && !SPLIT && LWG_W4_RDMAP), "the 8 x 8 sub-tile form: a list-driven 8-wave launch");
+    constexpr bool SUB = !std::is_void<GEO>::value, FINE = std::is_same<GEO, Cw4F>::value, Q8 = std::is_same<GEO, Cw4Q>::value;
+    using G = std::conditional_t<SUB, GEO, Cw4F>;            // the sub-tile geometry (named under SUB only)
+    using L = W4Lds<GEO>;                                    // the halo planes' geometry in LDS
+    static_assert(!SUB || (LIST && !SM && !TWO && !SPLIT && LWG_W4_RDMAP), "the sub-tile forms: a list-driven 8-wave launch");
     static_assert(!SPLIT || (SM && !LIST && EPI == LWG_EPI_NONE), "the split form: 4-wave blocks, plain epilogue");
-    constexpr int RS = Q8 ? CW4Q_RS : W4_RS;                 // the halo planes' geometry in LDS
-    constexpr int PLANE = Q8 ? CW4Q_PLANE : FINE ? W4F_PLANE : W4_PLANE;
+    constexpr int RS = L::RS, PLANE = L::PLN;
     constexpr int RAW = W4_KS * PLANE;
     constexpr int DUMP_OFF = 2 * RAW + 2 * W4_VS;
-    constexpr int BIAS_OFF = Q8 ? W4Q_BIAS_OFF : FINE ? W4F_BIAS_OFF : W4_BIAS_OFF;
+    constexpr int BIAS_OFF = w4_bias_off<GEO>;
     constexpr bool SMS = SM && EPI == LWG_EPI_SPADE;          // (its 32 accumulator rows: gamma | beta of the SAME 16 channels, cw4_n0_spade_small)
     constexpr int NVP = SM && !SMS ? 2 : 1;                  // patches per reader thread and pass
     constexpr int NTH = SM ? 256 : W4_THREADS;               // threads per workgroup
-    constexpr int NQ = SM ? 5 : W4_NQ + (Q8 ? W4Q_NQ - W4_NQ : 0);                      // halo pieces per thread and stage
+    constexpr int NQ = SM ? 5 : W4_NQ + (Q8 ? G::ROUNDS - W4_NQ : 0); // halo pieces per thread and stage
     constexpr int NBV = SM ? 32 : W4_NB;                     // output channels per block
     constexpr int MSR = SM ? 36 : W4_MSR;                    // floats per (plane, patch) row of the exchange buffer
     constexpr int NHF = SM ? 2 : 1;                          // halves of the input transform per thread
@@ -181,14 +187,14 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     int blk = blockIdx.x;
     // LIST: the heavy entries' number (the ids below it run the K loop); a workgroup may own none
     // (counts and tile ids are clamped to the launch's grid: lists that do not belong to this launch must not become addresses)
-    // (FINE: the entries are sub-tiles, nhe counts their groups)
-    const int nall = Q8 ? cw4q_in_image_total(a.B, H, W) : FINE ? cw4f_in_image_total(a.B, H, W) : g.tiles;
+    // (SUB: the entries are sub-tiles, nhe counts their groups)
+    const int nall = SUB ? G::in_image_total(a.B, H, W) : g.tiles;
     const int nht = LIST ? min(max(__builtin_amdgcn_readfirstlane(sk.counts[0]), 0), nall) : 0;
-    const int nhe = (Q8 ? cw4q_groups(nht) : FINE ? cw4f_groups(nht) : nht) * (N / NBV);
+    const int nhe = (SUB ? G::groups(nht) : nht) * (N / NBV);
     // a launch whose tiles are ALL heavy (a frame batch without background) walks its blocks in the plain entry point's order - decided here, on the
     // device: the list order costs such a launch 0.3-3 % (profiles/spade_skip_ab_tool_list_order.txt)
-    // (FINE: the entry point's second kernel runs the plain body for such a launch - this body always walks its lists)
-    const bool lst = FINE || Q8 ? true : LIST ? nht < nall : false;
+    // (SUB: the entry point's second kernel runs the plain body for such a launch - this body always walks its lists)
+    const bool lst = SUB ? true : LIST ? nht < nall : false;
     const bool run = lst ? blk < nhe : true;
     const int nst = Cin / W4_KS;                             // even (host: Cin % 16 == 0)
     const int sbeg = SPLIT ? cw4_slice_begin((int)blockIdx.z, a.cshift) : 0;       // this workgroup's stages [sbeg, send): the layer's, or its slice
@@ -199,56 +205,43 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     floatx16 acc[9];                                         // products 0..5: (xi = q, nu); 6..8: (xi = 4 + q / 2, nu = 3 (q % 2) + 0..2)
     CwBlock<NQ, TWO> bk;                                     // the per-block state (lwg_conv_wino.h), this thread's NQ halo offsets in it
     unsigned uvoff, uvoffc;                                  // this lane's column of the fragment panel: the 16-byte parts, the ninth product
-    int fs0 = 0, fs1 = 0;                                    // FINE: the sub-tiles of this wave's reader patches, passes 0 | 1 (-1: an empty slot)
+    int fs0 = 0, fs1 = 0;                                    // SUB: the sub-tiles of this wave's reader patches, passes 0 | 1 (-1: an empty slot)
     auto setup = [&](int id) {
         int cb, t;
-        if constexpr (Q8) {
+        if constexpr (SUB) {
             int tids = tid;
             asm volatile("" : "+v"(tids));
             int slot;
             cw_list_entry(id, N / NBV, slot, cb);
             auto sub = [&](int k) {                          // the group's sub-tile in slot k (wave-uniform), -1: an empty slot
-                const int ix = cw4q_slot_index(slot, k, nht);
-                return ix < 0 ? -1 : min(max(__builtin_amdgcn_readfirstlane(sk.heavy[ix]), 0), CW4Q_NS * g.tiles - 1);
+                const int ix = G::slot_index(slot, k, nht);
+                return ix < 0 ? -1 : min(max(__builtin_amdgcn_readfirstlane(sk.heavy[ix]), 0), G::NS * g.tiles - 1);
             };
             bk.n0 = cw_n0(cb, NBV);
-            // a wave stages the halo of ONE slot (cw4q_halo_elem: slot wid): one image descriptor
-            const int u = sub(wid);
+            // a wave stages the halo of ONE slot (cw4_halo_elem: slot wid / 2 | wid) - one image descriptor.  FINE reads the whole group once: the three
+            // slots a wave needs are selected from registers
+            int fsub[FINE ? G::NS : 1], u;
+            if constexpr (FINE) {
+#pragma unroll
+                for (int k = 0; k < G::NS; ++k) fsub[k] = sub(k);
+                const int hs = wid >> 1;
+                u = hs == 0 ? fsub[0] : hs == 1 ? fsub[1] : hs == 2 ? fsub[2] : fsub[3];
+            } else {
+                u = sub(wid);
+            }
             int b, x0, y0;
-            cw4q_corner(g, max(u, 0), b, x0, y0);
+            G::corner(g, max(u, 0), b, x0, y0);
             bk.rx0 = cw_image_rsrc(a.x0, __builtin_amdgcn_readfirstlane(b), H, W, a.C0, 4u);
 #pragma unroll
             for (int k = 0; k < NQ; ++k) {
                 int s, j;
-                cw4q_halo_elem(tids + NTH * k, s, j);
-                bk.voff0[k] = cw4q_halo_voff(u >= 0, j, x0, y0, H, W, a.C0);
+                cw4_halo_elem(G{}, tids + NTH * k, s, j);
+                bk.voff0[k] = G::halo_voff(u >= 0, j, x0, y0, H, W, a.C0);
             }
-            // the epilogue's (cw4q_reader): pass ph, this wave - slot 4 ph + wid / 2
-            fs0 = sub(wid >> 1), fs1 = sub(CW4Q_NSX + (wid >> 1));
-        } else if constexpr (FINE) {
-            int tids = tid;
-            asm volatile("" : "+v"(tids));
-            int fsub[CW4F_NS], slot;                         // the group's sub-tiles
-            cw_list_entry(id, N / NBV, slot, cb);
-#pragma unroll
-            for (int k = 0; k < CW4F_NS; ++k) {
-                const int ix = cw4f_slot_index(slot, k, nht);
-                fsub[k] = ix < 0 ? -1 : min(max(__builtin_amdgcn_readfirstlane(sk.heavy[ix]), 0), CW4F_NS * g.tiles - 1);
-            }
-            bk.n0 = cw_n0(cb, NBV);
-            // a wave stages the halo of ONE slot (cw4f_halo_elem: slot wid / 2): one image descriptor
-            const int hs = wid >> 1, u = hs == 0 ? fsub[0] : hs == 1 ? fsub[1] : hs == 2 ? fsub[2] : fsub[3];
-            int b, x0, y0;
-            cw4f_corner(g, max(u, 0), b, x0, y0);
-            bk.rx0 = cw_image_rsrc(a.x0, __builtin_amdgcn_readfirstlane(b), H, W, a.C0, 4u);
-#pragma unroll
-            for (int k = 0; k < NQ; ++k) {
-                int s, j;
-                cw4f_halo_elem(tids + NTH * k, s, j);
-                bk.voff0[k] = cw4f_halo_voff(u >= 0, j, x0, y0, H, W, a.C0);
-            }
-            // the epilogue's: pass ph reads patch rows 2 ph, 2 ph + 1, this wave the columns 4 (wid / 4) .. + 3 - slot 2 ph + wid / 4
-            fs0 = (wid >> 2) ? fsub[1] : fsub[0], fs1 = (wid >> 2) ? fsub[CW4F_NSX + 1] : fsub[CW4F_NSX];
+            // the epilogue's slots of this wave, passes ph = 0 | 1.  FINE: the pass reads patch rows 2 ph, 2 ph + 1, this wave the columns 4 (wid / 4) .. + 3 -
+            // slot 2 ph + wid / 4.  Q8 (cw4_reader8): slot 4 ph + wid / 2
+            if constexpr (FINE) fs0 = (wid >> 2) ? fsub[1] : fsub[0], fs1 = (wid >> 2) ? fsub[G::NSX + 1] : fsub[G::NSX];
+            else fs0 = sub(wid >> 1), fs1 = sub(G::NSX + (wid >> 1));
         } else if constexpr (LIST) {
             if (lst) {
                 int slot;
@@ -260,7 +253,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         } else {
             cw_block(o, id, cb, t);
         }
-        if constexpr (!FINE && !Q8) {
+        if constexpr (!SUB) {
         bk.locate(a, g, t, 4 * W4_PBX, 4 * W4_PBY, SMS ? cw4_n0_spade_small(cb) : cw_n0(cb, NBV));
         int tids = tid;                                      // (through an empty asm: the halo geometry is recomputed per block - hoisted out of the block
         asm volatile("" : "+v"(tids));                       //  loop it would sit in registers through the K loop)
@@ -275,16 +268,11 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
         const int i = tid + NTH * k;
-        if constexpr (Q8) {
+        if constexpr (SUB) {
             int s, j, hy, hx, hq;
-            cw4q_halo_elem(i, s, j);
-            cw4q_halo_place(j, hy, hx, hq);
-            wst[k] = j < CW4Q_NEL ? 4 * hq * PLANE + cw4q_lds_slot(s) + hy * RS + hx : DUMP_OFF + tid;
-        } else if constexpr (FINE) {
-            int s, j, hy, hx, hq;
-            cw4f_halo_elem(i, s, j);
-            cw4f_halo_place(j, hy, hx, hq);
-            wst[k] = j < CW4F_NEL ? 4 * hq * PLANE + W4F_SLOT(s) + hy * RS + hx : DUMP_OFF + tid;
+            cw4_halo_elem(G{}, i, s, j);
+            G::halo_place(j, hy, hx, hq);
+            wst[k] = j < G::NEL ? 4 * hq * PLANE + L::slot(s) + hy * RS + hx : DUMP_OFF + tid;
         } else {
         const int pix = i >> 1, hq = i & 1, hy = pix / W4_HW, hx = pix - hy * W4_HW;
         wst[k] = i < W4_NEL ? 4 * hq * PLANE + hy * RS + hx : DUMP_OFF + tid;
@@ -330,12 +318,12 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     // the input transform's thread: patch tid % 32, channel (tid / 32) % 8, rows 3 half .. 3 half + 2
     const int patch = tid & 31, tc = (tid >> 5) & 7;
     const int pty = patch >> 3, ptx = patch & 7;
-    int pby = pty, pbx = ptx, pslot = 0;                     // FINE: the patch inside its slot's sub-plane
+    int pby = pty, pbx = ptx, pslot = 0;                     // SUB: the patch's 6 x 6 window inside its slot's sub-plane
     if constexpr (FINE) {
-        cw4f_patch_in_slot(pty, ptx, pby, pbx);
-        pslot = W4F_SLOT(cw4f_slot_of_patch(pty, ptx));
+        G::patch_in_slot(pty, ptx, pby, pbx);
+        pslot = L::slot(G::slot_of_patch(pty, ptx));
     }
-    if constexpr (Q8) pby = 0, pbx = 0, pslot = cw4q_lds_patch(pty, ptx);
+    if constexpr (Q8) pby = 0, pbx = 0, pslot = L::patch(pty, ptx);
     unsigned dbs = (unsigned)(tc * PLANE + pslot + (4 * pby) * RS + 4 * pbx) >> 2;      // its 6 x 6 input patch inside raw[0] (float index; 16-byte aligned)
     asm volatile("" : "+v"(dbs));
     dbs <<= 2;
@@ -606,7 +594,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         iteration(s + 1, IntC<1>(), IntC<0>());
     }
     W4TS(2);
-    int eb = FINE || Q8 ? 0 : bk.b, ex0 = FINE || Q8 ? 0 : bk.x0, ey0 = FINE || Q8 ? 0 : bk.y0;     // this block's coordinates (the state moves on to the next block below)
+    int eb = SUB ? 0 : bk.b, ex0 = SUB ? 0 : bk.x0, ey0 = SUB ? 0 : bk.y0;     // this block's coordinates (the state moves on to the next block below)
     const int en0 = bk.n0;
     const int es0 = fs0, es1 = fs1;
     // epilogue.  (1) M A in registers: row q -> F[b] (b = 0..3, into acc[0..3]); the half row -> three partial sums (into acc[6..8]):
@@ -646,7 +634,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     const int lanee = tide & 63;
     int rb = wid & 3;                                        // reader: output column inside a patch (wave-uniform; Q8: per half wave)
     int p16q = 0;
-    if constexpr (Q8) cw4q_reader(wid, lanee, rb, p16q);
+    if constexpr (Q8) cw4_reader8(wid, lanee, rb, p16q);
     // ... patch inside the pass and channel quad (and 32 + n4).  8-wave form: a ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27} and
     // {4-11, 16-19, 28-31} of either half wave (MI355X_MICROARCH: LDS), and a 16-byte slot of the exchange buffer lies in bank quad (patch + quad) % 16
     // (rows of 68 floats): a group reads the eight quads of patches a and a + 8 - sixteen distinct bank quads (eight lanes per patch in lane order
@@ -664,7 +652,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
     const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
     const float* const esrc = EPI == LWG_EPI_SPADE ? a.xn : EPI == LWG_EPI_RESIDUAL ? a.res : a.y;
     __amdgpu_buffer_rsrc_t ry, re;
-    auto eframe = [&]() {                                    // image eb: once per block (FINE: per pass - the slot's image)
+    auto eframe = [&]() {                                    // image eb: once per block (SUB: per pass - the slot's image)
         if (EPI == LWG_EPI_SPADE) {
             mu = *reinterpret_cast<const floatx4*>(a.mean + (size_t)eb * a.YC + cbase + n4);
             rs = *reinterpret_cast<const floatx4*>(a.rstd + (size_t)eb * a.YC + cbase + n4);
@@ -672,7 +660,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         ry = __builtin_amdgcn_make_buffer_rsrc(y + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
         re = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(esrc) + (size_t)eb * H * W * a.YC, 0, (int)img_bytes, 0x00020000);
     };
-    if constexpr (!FINE && !Q8) eframe();
+    if constexpr (!SUB) eframe();
     const int chan = EPI == LWG_EPI_SPADE ? cbase + n4 : a.ycoff + en0 + n4;
     bool more = false;
     int nblk = blk;
@@ -681,18 +669,10 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         // (pass 0 needs no barrier in front of its writes: the last LDS reads of the K loop - the fragments of its last k-pair - were issued in front of
         // the last stage's barrier; pass 1 waits for the readers of pass 0)
         if (ph == 1) __syncthreads();
-        if constexpr (Q8) {
+        if constexpr (SUB) {
             const int u = ph ? es1 : es0;
             int ub;
-            cw4q_corner(g, max(u, 0), ub, ex0, ey0);
-            eb = __builtin_amdgcn_readfirstlane(ub);
-            if (u < 0) ex0 = W, ey0 = H;                     // an empty slot: every store out of range
-            eframe();
-        }
-        if constexpr (FINE) {
-            const int u = ph ? es1 : es0;
-            int ub;
-            cw4f_corner(g, max(u, 0), ub, ex0, ey0);
+            G::corner(g, max(u, 0), ub, ex0, ey0);
             eb = __builtin_amdgcn_readfirstlane(ub);
             if (u < 0) ex0 = W, ey0 = H;                     // an empty slot: every store out of range
             eframe();
@@ -714,8 +694,8 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
         for (int hp = 0; hp < NVP; ++hp) {
             const int p = ph * 16 + (SMS ? lanee >> 2 : SM ? 8 * hp + (lanee >> 3) : p16);
-            const int ox = ex0 + 4 * (Q8 ? (p & 7) % (CW4Q_SX / 4) : FINE ? (p & 7) % (CW4F_SX / 4) : (p & 7)) + rb;
-            const int oyb = ey0 + 4 * (Q8 ? (p >> 3) % (CW4Q_SY / 4) : FINE ? (p >> 3) % (CW4F_SY / 4) : (p >> 3));
+            const int ox = ex0 + 4 * (SUB ? (p & 7) % (G::SX / 4) : (p & 7)) + rb;
+            const int oyb = ey0 + 4 * (SUB ? (p >> 3) % (G::SY / 4) : (p >> 3));
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 vo[hp][i] = cw4_out_voff(ox, oyb + i, H, W, a.YC, chan);
@@ -733,7 +713,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
             W4TS(8);
             if constexpr (!SPLIT) {                          // (a split launch's workgroup has one block)
             nblk = blk + (int)gridDim.x;
-            if constexpr (FINE || Q8) more = nblk < nhe;
+            if constexpr (SUB) more = nblk < nhe;
             else if constexpr (LIST) more = lst ? nblk < nhe : cw_has_block(o, nblk);
             else more = cw_has_block(o, nblk);
             setup(more ? nblk : blk);
@@ -819,9 +799,9 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         // four loads / stores; consecutive lanes = the quads of a pixel (a pixel's 256 / 128 bytes contiguous).  Pixels right of / below the image: the
         // out-of-range offset (dropped stores, zero loads), as in the epilogue.
         typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
-        // FINE: a light entry is a sub-tile, 128 pixels (cw4f_light_pixel): NPASS passes in all, NI at a time
+        // SUB: a light entry is a sub-tile, its SX * SY pixels (G::light_pixel): NPASS passes in all, NI at a time
         constexpr int NQD = EPI == LWG_EPI_SPADE ? 8 : 16;
-        constexpr int NPASS = (Q8 ? CW4Q_SX * CW4Q_SY : FINE ? CW4F_SX * CW4F_SY : 512) * NQD / W4_THREADS, NI = NPASS < 4 ? NPASS : 4;
+        constexpr int NPASS = (SUB ? G::SX * G::SY : 512) * NQD / W4_THREADS, NI = NPASS < 4 ? NPASS : 4;
         const int ncb = N / NBV;
         const int nend = nhe + min(max(__builtin_amdgcn_readfirstlane(sk.counts[1]), 0), nall - nht) * ncb;
         const unsigned img_bytes = (unsigned)(H * W) * (unsigned)a.YC * 4u;
@@ -831,14 +811,11 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
         for (int id = cw_list_first_light((int)blockIdx.x, (int)gridDim.x, nhe); id < nend; id += (int)gridDim.x) {
             int slot, cb;
             cw_list_entry(id - nhe, ncb, slot, cb);
-            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), (Q8 ? CW4Q_NS : FINE ? CW4F_NS : 1) * g.tiles - 1);
+            const int t = min(max(__builtin_amdgcn_readfirstlane(sk.light[slot]), 0), (SUB ? G::NS : 1) * g.tiles - 1);
             const int en0 = cw_n0(cb, NBV);
             int eb, ex0, ey0;
-            if constexpr (Q8) {
-                cw4q_corner(g, t, eb, ex0, ey0);
-                eb = __builtin_amdgcn_readfirstlane(eb);
-            } else if constexpr (FINE) {
-                cw4f_corner(g, t, eb, ex0, ey0);
+            if constexpr (SUB) {
+                G::corner(g, t, eb, ex0, ey0);
                 eb = __builtin_amdgcn_readfirstlane(eb);
             } else {
                 eb = __builtin_amdgcn_readfirstlane(cw_image(g, t));
@@ -859,8 +836,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
                     for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
-                        if constexpr (FINE) cw4f_light_pixel(px, py);
-                        if constexpr (Q8) cw4q_light_pixel(px, py);
+                        if constexpr (SUB) G::light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, cbase + 4 * q4);
                         const unsigned vc = cw4_out_voff(ex0 + px, ey0 + py, H, W, N, en0 + 4 * q4);
                         gam[i] = cw_buf_load(rc, cw4_out_group(vc, 0, true), 0u);
@@ -883,8 +859,7 @@ __device__ __forceinline__ void w4_body(const LwgConvArgs& a, const LwgConvLists
 #pragma unroll
                     for (int i = 0; i < NI; ++i) {
                         cw4_light_elem(tid, it + i, W4_THREADS, NQD, px, py, q4);
-                        if constexpr (FINE) cw4f_light_pixel(px, py);
-                        if constexpr (Q8) cw4q_light_pixel(px, py);
+                        if constexpr (SUB) G::light_pixel(px, py);
                         vo[i] = cw4_out_voff(ex0 + px, ey0 + py, H, W, a.YC, a.ycoff + en0 + 4 * q4);
                         o[i] = cw_buf_load(rc, vo[i], 0u);
                     }
@@ -902,35 +877,24 @@ __global__ __launch_bounds__(SM ? 256 : W4_THREADS, 1) void lwg_conv_winograd4_k
 }
 template <bool TWO>
 __global__ __launch_bounds__(256, 1) void lwg_conv_winograd4_split_kernel(const LwgConvArgs a) {
-    w4_body<LWG_EPI_NONE, TWO, true, false, false, true>(a, LwgConvLists{});
+    w4_body<LWG_EPI_NONE, TWO, true, false, void, true>(a, LwgConvLists{});
 }
 template <int EPI>
 __global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_list_kernel(const LwgConvArgs a, const LwgConvLists sk) {
     w4_body<EPI, false, false, true>(a, sk);
 }
-template <int EPI>
-__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_kernel(const LwgConvArgs a, const LwgConvLists sk) {
-    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) >= cw4f_in_image_total(a.B, a.H, a.W)) return;      // nothing is light: the kernel below
-    w4_body<EPI, false, false, true, true>(a, sk);
+// The sub-tile forms (G = Cw4F | Cw4Q) ...
+template <int EPI, typename G>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_sub_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) >= G::in_image_total(a.B, a.H, a.W)) return;      // nothing is light: the kernel below
+    w4_body<EPI, false, false, true, G>(a, sk);
 }
-// ... and its companion, launched behind it: a launch in which nothing is light (a frame batch without background) runs the plain kernel's body - its
+// ... and their companion, launched behind it: a launch in which nothing is light (a frame batch without background) runs the plain kernel's body - its
 // block order, staging and epilogue - decided here, on the device; every other launch ends at once.  (Two kernels, not two bodies in one: the
 // scalar-register spill lanes of both bodies together cost the SPADE form a vector register it does not have.)
-template <int EPI>
-__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_fine_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
-    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < cw4f_in_image_total(a.B, a.H, a.W)) return;
-    w4_body<EPI, false, false, false>(a, LwgConvLists{});
-}
-
-// The 8 x 8 sub-tile form and its all-heavy companion (as the pair above)
-template <int EPI>
-__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_q8_kernel(const LwgConvArgs a, const LwgConvLists sk) {
-    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) >= cw4q_in_image_total(a.B, a.H, a.W)) return;
-    w4_body<EPI, false, false, true, false, false, true>(a, sk);
-}
-template <int EPI>
-__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_q8_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
-    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < cw4q_in_image_total(a.B, a.H, a.W)) return;
+template <int EPI, typename G>
+__global__ __launch_bounds__(W4_THREADS, 1) void lwg_conv_winograd4_sub_plain_kernel(const LwgConvArgs a, const LwgConvLists sk) {
+    if (__builtin_amdgcn_readfirstlane(sk.counts[0]) < G::in_image_total(a.B, a.H, a.W)) return;
     w4_body<EPI, false, false, false>(a, LwgConvLists{});
 }
 
@@ -1123,45 +1087,28 @@ extern "C" int lwg_conv2d_winograd4_list_applies(const LwgConvArgs* pa) {
     if (!lwg_wino4_list_ok(pa)) return 0;
     return !(LWG_W4_SMALL && 2 * cw_total_blocks(pa->B, pa->H, pa->W, pa->N, 4 * W4_PBX, 4 * W4_PBY, W4_NB) <= lwg_device_cus());
 }
-extern "C" int lwg_conv2d_winograd4_list_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
+// G = void: pl = the block lists of lwg_spade_skip_lists_f32, one kernel.  G = Cw4F | Cw4Q: pl->heavy / light / counts = the SUB-TILE lists of that
+// geometry (lwg_spade_skip_fine_lists_f32 / _q8_lists_f32), the list kernel and its nothing-is-light companion; the same contract, the same
+// launch-size rule (lwg_conv2d_winograd4_list_applies) and the same result at every granularity
+template <typename G>
+static int lwg_wino4_lists_go(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
     if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
     if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const LwgConvArgs& a = *pa;
-    const size_t lds = (size_t)(W4_BIAS_OFF + 64) * 4;
+    const size_t lds = (size_t)(w4_bias_off<G> + 64) * 4, ldsp = (size_t)(W4_BIAS_OFF + 64) * 4;
     const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
-    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
-                                  : cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
+    if constexpr (std::is_void<G>::value) {
+        return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
+                                      : cw_launch_lists<lwg_conv_winograd4_list_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
+    } else {
+        const int e = a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_sub_kernel<LWG_EPI_SPADE, G>>(grid, W4_THREADS, lds, stream, a, *pl)
+                                             : cw_launch_lists<lwg_conv_winograd4_sub_kernel<LWG_EPI_NONE, G>>(grid, W4_THREADS, lds, stream, a, *pl);
+        if (e != 0) return e;
+        return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_sub_plain_kernel<LWG_EPI_SPADE, G>>(grid, W4_THREADS, ldsp, stream, a, *pl)
+                                      : cw_launch_lists<lwg_conv_winograd4_sub_plain_kernel<LWG_EPI_NONE, G>>(grid, W4_THREADS, ldsp, stream, a, *pl);
+    }
 }
-
-// The sub-tile form (include/lwg_hip.h): pl->heavy / light / counts = the SUB-TILE lists of lwg_spade_skip_fine_lists_f32; the same contract and the same
-// launch-size rule (lwg_conv2d_winograd4_list_applies) as the block lists
-extern "C" int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
-    if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
-    if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const LwgConvArgs& a = *pa;
-    const size_t lds = (size_t)(W4F_BIAS_OFF + 64) * 4, ldsp = (size_t)(W4_BIAS_OFF + 64) * 4;
-    const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
-    const int e = a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_fine_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
-                                         : cw_launch_lists<lwg_conv_winograd4_fine_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
-    if (e != 0) return e;
-    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, ldsp, stream, a, *pl)
-                                  : cw_launch_lists<lwg_conv_winograd4_fine_plain_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, ldsp, stream, a, *pl);
-}
-
-// The 8 x 8 sub-tile form (include/lwg_hip.h): pl->heavy / light / counts = the 8 x 8 lists of lwg_spade_skip_q8_lists_f32; the same contract, the same
-// launch-size rule and the same result as the two forms above
-extern "C" int lwg_conv2d_winograd4_q8_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) {
-    if (!lwg_wino4_list_ok(pa) || !pl || !pl->heavy || !pl->light || !pl->counts || !pl->cal) return (int)hipErrorInvalidValue;
-    if (!lwg_conv2d_winograd4_list_applies(pa)) return lwg_conv2d_winograd4_f32(pa, stream_);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const LwgConvArgs& a = *pa;
-    const size_t lds = (size_t)(W4Q_BIAS_OFF + 64) * 4, ldsp = (size_t)(W4_BIAS_OFF + 64) * 4;
-    const dim3 grid = cw_persistent_grid(cw_total_blocks(a.B, a.H, a.W, a.N, 4 * W4_PBX, 4 * W4_PBY, W4_NB), lwg_device_cus());
-    const int e = a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_q8_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, lds, stream, a, *pl)
-                                         : cw_launch_lists<lwg_conv_winograd4_q8_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, lds, stream, a, *pl);
-    if (e != 0) return e;
-    return a.epi == LWG_EPI_SPADE ? cw_launch_lists<lwg_conv_winograd4_q8_plain_kernel<LWG_EPI_SPADE>>(grid, W4_THREADS, ldsp, stream, a, *pl)
-                                  : cw_launch_lists<lwg_conv_winograd4_q8_plain_kernel<LWG_EPI_NONE>>(grid, W4_THREADS, ldsp, stream, a, *pl);
-}
+extern "C" int lwg_conv2d_winograd4_list_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) { return lwg_wino4_lists_go<void>(pa, pl, stream_); }
+extern "C" int lwg_conv2d_winograd4_fine_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) { return lwg_wino4_lists_go<Cw4F>(pa, pl, stream_); }
+extern "C" int lwg_conv2d_winograd4_q8_f32(const LwgConvArgs* pa, const LwgConvLists* pl, lwg_stream_t stream_) { return lwg_wino4_lists_go<Cw4Q>(pa, pl, stream_); }

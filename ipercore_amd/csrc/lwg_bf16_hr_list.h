@@ -1,5 +1,5 @@
 // The id arithmetic of the list-driven form of lwg_conv_bf16_hr2_kernel (conv_igemm_bf16.hip: lwg_conv2d_nhwc_bf16_hr_list).
-// The kernel's 8-row x 16-column pixel block IS the 16 x 8 sub-tile of lwg_conv_wino.h (CW4F_SX x CW4F_SY), so the launch reads the sub-tile lists of
+// The kernel's 8-row x 16-column pixel block IS the 16 x 8 sub-tile of lwg_conv_wino.h (Cw4F::SX x Cw4F::SY), so the launch reads the sub-tile lists of
 // lwg_spade_skip_fine_lists_f32 as they are: one workgroup per (in-image sub-tile, column tile of 128), the heavy entries first in dispatch order.
 // Plain integer arithmetic that a host compiler can include: tests/test_spade_skip_bf16_cpu.py compiles these very functions with signed-overflow
 // traps; the kernel goes through them.
@@ -11,7 +11,7 @@
 enum { HRL_EXIT = 0, HRL_HEAVY = 1, HRL_LIGHT = 2 };
 
 // the launch's workgroups: the host's number - every in-image sub-tile once per column tile, whatever the lists say (the counts stay on the device)
-CW_FN long long hrl_grid(int B, int OH, int OW, int tiles_n) { return (long long)cw4f_in_image_total(B, OH, OW) * tiles_n; }
+CW_FN long long hrl_grid(int B, int OH, int OW, int tiles_n) { return (long long)Cw4F::in_image_total(B, OH, OW) * tiles_n; }
 // workgroup lid (after lwg_xcd_remap) -> entry e and column tile
 CW_FN void hrl_entry(int lid, int tiles_n, int& e, int& tile_n) { e = lid / tiles_n, tile_n = lid - e * tiles_n; }
 // the counts as the kernel takes them: never more entries than the launch has workgroups for, whatever the memory holds
@@ -30,15 +30,15 @@ CW_FN int hrl_kind(int e, int nh, int nl, int& idx) {
 CW_FN bool hrl_locate(int u, int B, int H, int W, int& b, int& x0, int& y0) {
     const CwGrid g = cw_grid(B, H, W, CW_NB, 32, 16, CW_NB);
     b = x0 = y0 = 0;
-    if (u < 0 || u >= g.tiles * CW4F_NS) return false;
-    cw4f_corner(g, u, b, x0, y0);
-    return cw4f_in_image(x0, y0, H, W);
+    if (u < 0 || u >= g.tiles * Cw4F::NS) return false;
+    Cw4F::corner(g, u, b, x0, y0);
+    return Cw4F::in_image(x0, y0, H, W);
 }
 // every sub-tile heavy (counts[0] = the total): the plain kernel's tile order - entry e = (image, block row, block column) row-major
 CW_FN void hrl_plain_corner(int e, int H, int W, int& b, int& x0, int& y0) {
-    const int tx = (W + CW4F_SX - 1) / CW4F_SX, ty = (H + CW4F_SY - 1) / CW4F_SY;
+    const int tx = (W + Cw4F::SX - 1) / Cw4F::SX, ty = (H + Cw4F::SY - 1) / Cw4F::SY;
     const int r = e / tx;
-    x0 = (e - r * tx) * CW4F_SX, y0 = (r % ty) * CW4F_SY, b = r / ty;
+    x0 = (e - r * tx) * Cw4F::SX, y0 = (r % ty) * Cw4F::SY, b = r / ty;
 }
 // ---- a lane's place in the workgroup's accumulator tile (the row-renaming kernel's D^T layout with WAVES_M = 1): row tile i of HRL_TM is the image-row
 // pair (i, i + HRL_TM) of the sub-tile; lane -> pixel (py, px) inside the sub-tile
@@ -66,8 +66,8 @@ CW_FN bool hrl_contract_ok(const LwgConvArgs& a) {
     if ((unsigned long long)a.H * a.W * (unsigned long long)a.C0 * 2ull >= (unsigned long long)CW_OOB ||
         9ull * (unsigned long long)(a.C0 / 64) * (unsigned long long)a.N * 128ull >= (unsigned long long)CW_OOB)
         return false;
-    if (cw_total_blocks(a.B, a.H, a.W, CW_NB, 32, 16, CW_NB) * CW4F_NS >= (1ll << 30) || (long long)a.H * a.W >= (1ll << 30) ||
-        (long long)((a.W + CW4F_SX - 1) / CW4F_SX) * ((a.H + CW4F_SY - 1) / CW4F_SY) * a.B * (a.N / HRL_BN) >= 0x7fffffffll)
+    if (cw_total_blocks(a.B, a.H, a.W, CW_NB, 32, 16, CW_NB) * Cw4F::NS >= (1ll << 30) || (long long)a.H * a.W >= (1ll << 30) ||
+        (long long)((a.W + Cw4F::SX - 1) / Cw4F::SX) * ((a.H + Cw4F::SY - 1) / Cw4F::SY) * a.B * (a.N / HRL_BN) >= 0x7fffffffll)
         return false;
     if (a.epi == LWG_EPI_SPADE) return a.YC * 2 == a.N && a.ycoff == 0;
     return a.epi == LWG_EPI_NONE && a.ycoff + a.N <= a.YC;

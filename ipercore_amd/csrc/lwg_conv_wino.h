@@ -13,7 +13,7 @@
 #include "lwg_conv_args.h"
 
 #ifdef __HIPCC__
-#define CW_FN __host__ __device__ __forceinline__
+#define CW_FN static __host__ __device__ __forceinline__
 #else
 #define CW_FN static inline
 #endif
@@ -134,140 +134,97 @@ CW_FN void cw4_light_elem(int tid, int it, int nth, int nq, int& px, int& py, in
     q4 = e - p * nq, px = p & 31, py = p >> 5;
 }
 
-// ---- sub-tile lists of F(4x4) (lwg_conv2d_winograd4_fine_f32, spade_skip.hip).  A 32 x 16 block is CW4F_NS sub-tiles of CW4F_SX x
-// CW4F_SY output pixels (patch-aligned: 4 x 2 patches); sub-tile u = CW4F_NS * block + s, s = sub-tile row * 2 + sub-tile column - so the sub-tiles of
+// ---- sub-tile lists of F(4x4) (lwg_conv2d_winograd4_fine_f32 / _q8_f32, spade_skip.hip).  A 32 x 16 block is NS sub-tiles of SX x SY
+// output pixels (patch-aligned: SX / 4 x SY / 4 patches); sub-tile u = NS * block + s, s = sub-tile row * NSX + sub-tile column - so the sub-tiles of
 // a launch whose sub-tiles are all heavy are exactly the plain blocks, in their order.  A sub-tile is heavy / light by the block rule applied to ITS
 // window (cw_block_window of the sub-tile); sub-tiles wholly outside the image are in neither list.  The launch's heavy entries: entry e = (group
-// e / ncb, column block e % ncb), the group's CW4F_NS slots = heavy[CW4F_NS * group ..] (slots past the count: empty); patch (pty, ptx) of the
-// workgroup's 4 x 8 patches belongs to slot cw4f_slot_of_patch - a group that is one whole block has the plain block's patch numbering.
-#define CW4F_SX 16
-#define CW4F_SY 8
-#define CW4F_NSX (32 / CW4F_SX)
-#define CW4F_NS (CW4F_NSX * (16 / CW4F_SY))
-#define CW4F_HW (CW4F_SX + 2)                // a sub-tile's halo: 18 x 10 pixels
-#define CW4F_HH (CW4F_SY + 2)
-#define CW4F_NEL (CW4F_HW * CW4F_HH * 2)     // ... (pixel, channel quad) elements of a stage
-#define CW4F_ROUNDS ((CW4F_NEL + 63) / 64)   // ... in wave rounds of 64: six per slot = the three rounds of two waves - a wave stages ONE slot (one image descriptor)
-CW_FN int cw4f_slot_of_patch(int pty, int ptx) { return (pty / (CW4F_SY / 4)) * CW4F_NSX + ptx / (CW4F_SX / 4); }
-CW_FN void cw4f_patch_in_slot(int pty, int ptx, int& ly, int& lx) { ly = pty % (CW4F_SY / 4), lx = ptx % (CW4F_SX / 4); }
-// sub-tile u -> its image and corner
-CW_FN void cw4f_corner(const CwGrid& g, int u, int& b, int& x0, int& y0) {
-    const int t = u / CW4F_NS, s = u - t * CW4F_NS;
-    b = cw_image(g, t);
-    cw_corner(g, t - b * g.bx * g.by, 32, 16, x0, y0);
-    x0 += (s % CW4F_NSX) * CW4F_SX, y0 += (s / CW4F_NSX) * CW4F_SY;
-}
-CW_FN bool cw4f_in_image(int x0, int y0, int H, int W) { return x0 < W && y0 < H; }
-CW_FN int cw4f_in_image_total(int B, int H, int W) { return B * ((W + CW4F_SX - 1) / CW4F_SX) * ((H + CW4F_SY - 1) / CW4F_SY); }
-CW_FN int cw4f_groups(int nh) { return (nh + CW4F_NS - 1) / CW4F_NS; }
-CW_FN int cw4f_slot_index(int grp, int k, int nh) { return grp * CW4F_NS + k < nh ? grp * CW4F_NS + k : -1; }      // the heavy list's index, -1: empty
-// the classifier: which sub-tiles of the block at (x0, y0) hold the image pixel (x, y) in their window (bit s)
-CW_FN unsigned cw4f_reached(int x, int y, int x0, int y0, int d) {
-    unsigned m = 0;
-    for (int s = 0; s < CW4F_NS; ++s) {
-        const int sx = x0 + (s % CW4F_NSX) * CW4F_SX, sy = y0 + (s / CW4F_NSX) * CW4F_SY;
-        m |= (x >= sx - d && x < sx + CW4F_SX + d && y >= sy - d && y < sy + CW4F_SY + d ? 1u : 0u) << s;
+// e / ncb, column block e % ncb), the group's NS slots = heavy[NS * group ..] (slots past the count: empty); patch (pty, ptx) of the workgroup's
+// 4 x 8 patches belongs to slot slot_of_patch - a group that is one whole block has the plain block's patch numbering.
+//   Two geometries: Cw4F, 16 x 8 (four slots of 4 x 2 patches), and Cw4Q, 8 x 8 (eight slots of 2 x 2 patches: sub-tile u = 8 * block + 4 * (sub-tile
+// row) + sub-tile column).  A 16 x 8 sub-tile is the 8 x 8 sub-tiles 4 r + 2 c, 4 r + 2 c + 1 of its block: its window is the union of theirs, its
+// mark their OR.  What differs between the two beyond SX, SY - which wave stages which slot, the LDS placement, the 8 x 8 reader - follows the struct.
+template <int SX_, int SY_>
+struct Cw4Sub {
+    static constexpr int SX = SX_, SY = SY_, NSX = 32 / SX, NS = NSX * (16 / SY);
+    static constexpr int HW = SX + 2, HH = SY + 2;           // a sub-tile's halo: 18 x 10 | 10 x 10 pixels
+    static constexpr int NEL = HW * HH * 2;                  // ... (pixel, channel quad) elements of a stage
+    static constexpr int ROUNDS = (NEL + 63) / 64;           // ... in wave rounds of 64 (cw4_halo_elem: a wave stages ONE slot - one image descriptor)
+    CW_FN int slot_of_patch(int pty, int ptx) { return (pty / (SY / 4)) * NSX + ptx / (SX / 4); }
+    CW_FN void patch_in_slot(int pty, int ptx, int& ly, int& lx) { ly = pty % (SY / 4), lx = ptx % (SX / 4); }
+    // sub-tile u -> its image and corner
+    CW_FN void corner(const CwGrid& g, int u, int& b, int& x0, int& y0) {
+        const int t = u / NS, s = u - t * NS;
+        b = cw_image(g, t);
+        cw_corner(g, t - b * g.bx * g.by, 32, 16, x0, y0);
+        x0 += (s % NSX) * SX, y0 += (s / NSX) * SY;
     }
-    return m;
-}
-// halo element i = tid + 512 k of a stage (wave (i / 64) % 8, its round k) -> its slot - the wave's: waves 2 s, 2 s + 1 share slot s, three rounds each -
-// and its element j inside the slot's halo (j >= CW4F_NEL: none)
-CW_FN void cw4f_halo_elem(int i, int& slot, int& j) {
-    const int wave = (i >> 6) & 7, k = i >> 9, per = CW4F_ROUNDS / 3, wr = 3 * wave + k;
-    slot = wave / per, j = (wr - slot * CW4F_ROUNDS) * 64 + (i & 63);
-}
-// ... -> its halo pixel (hy, hx) and channel quad hq; its byte offset inside the image of the sub-tile at (x0, y0), or the marker
-CW_FN void cw4f_halo_place(int j, int& hy, int& hx, int& hq) {
-    const int pix = j >> 1;
-    hq = j & 1, hy = pix / CW4F_HW, hx = pix - hy * CW4F_HW;
-}
-// (present = false: an empty slot - nothing but markers)
-CW_FN unsigned cw4f_halo_voff(bool present, int j, int x0, int y0, int H, int W, int C) {
-    int hy, hx, hq;
-    cw4f_halo_place(j, hy, hx, hq);
-    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-    return present && j < CW4F_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W ? (unsigned)((gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
-}
-// a light sub-tile's elements from cw4_light_elem's (px, py) of the first CW4F_SX * CW4F_SY pixels
-CW_FN void cw4f_light_pixel(int& px, int& py) {
-    const int p = py * 32 + px;
-    py = p / CW4F_SX, px = p - py * CW4F_SX;
-}
-
-// ---- 8 x 8 sub-tile lists of F(4x4) (lwg_conv2d_winograd4_q8_f32, lwg_spade_skip_q8_lists_f32): the same scheme at half the sub-tile
-// width beside the 16 x 8 form - a block is CW4Q_NS = 8 sub-tiles of 2 x 2 patches, sub-tile u = 8 * block + 4 * (sub-tile row) + sub-tile column, a
-// group = eight heavy sub-tiles in the eight slots of the workgroup's 4 x 8 patches, slot of patch (pty, ptx) = 4 (pty / 2) + ptx / 2.  A 16 x 8
-// sub-tile is the sub-tiles 4 r + 2 c, 4 r + 2 c + 1 of its block: its window is the union of theirs, its mark their OR.
-#define CW4Q_SX 8
-#define CW4Q_SY 8
-#define CW4Q_NSX (32 / CW4Q_SX)
-#define CW4Q_NS (CW4Q_NSX * (16 / CW4Q_SY))
-#define CW4Q_HW (CW4Q_SX + 2)                // a sub-tile's halo: 10 x 10 pixels
-#define CW4Q_HH (CW4Q_SY + 2)
-#define CW4Q_NEL (CW4Q_HW * CW4Q_HH * 2)     // ... (pixel, channel quad) elements of a stage
-#define CW4Q_ROUNDS ((CW4Q_NEL + 63) / 64)   // ... in wave rounds of 64: four, all of ONE wave - wave w stages slot w (one image descriptor)
-CW_FN int cw4q_slot_of_patch(int pty, int ptx) { return (pty / (CW4Q_SY / 4)) * CW4Q_NSX + ptx / (CW4Q_SX / 4); }
-CW_FN void cw4q_patch_in_slot(int pty, int ptx, int& ly, int& lx) { ly = pty % (CW4Q_SY / 4), lx = ptx % (CW4Q_SX / 4); }
-CW_FN void cw4q_corner(const CwGrid& g, int u, int& b, int& x0, int& y0) {
-    const int t = u / CW4Q_NS, s = u - t * CW4Q_NS;
-    b = cw_image(g, t);
-    cw_corner(g, t - b * g.bx * g.by, 32, 16, x0, y0);
-    x0 += (s % CW4Q_NSX) * CW4Q_SX, y0 += (s / CW4Q_NSX) * CW4Q_SY;
-}
-CW_FN bool cw4q_in_image(int x0, int y0, int H, int W) { return x0 < W && y0 < H; }
-CW_FN int cw4q_in_image_total(int B, int H, int W) { return B * ((W + CW4Q_SX - 1) / CW4Q_SX) * ((H + CW4Q_SY - 1) / CW4Q_SY); }
-CW_FN int cw4q_groups(int nh) { return (nh + CW4Q_NS - 1) / CW4Q_NS; }
-CW_FN int cw4q_slot_index(int grp, int k, int nh) { return grp * CW4Q_NS + k < nh ? grp * CW4Q_NS + k : -1; }      // the heavy list's index, -1: empty
-// the classifier: which sub-tiles of the block at (x0, y0) hold the image pixel (x, y) in their window (bit s)
-CW_FN unsigned cw4q_reached(int x, int y, int x0, int y0, int d) {
-    unsigned m = 0;
-    for (int s = 0; s < CW4Q_NS; ++s) {
-        const int sx = x0 + (s % CW4Q_NSX) * CW4Q_SX, sy = y0 + (s / CW4Q_NSX) * CW4Q_SY;
-        m |= (x >= sx - d && x < sx + CW4Q_SX + d && y >= sy - d && y < sy + CW4Q_SY + d ? 1u : 0u) << s;
+    CW_FN bool in_image(int x0, int y0, int H, int W) { return x0 < W && y0 < H; }
+    CW_FN int in_image_total(int B, int H, int W) { return B * ((W + SX - 1) / SX) * ((H + SY - 1) / SY); }
+    CW_FN int groups(int nh) { return (nh + NS - 1) / NS; }
+    CW_FN int slot_index(int grp, int k, int nh) { return grp * NS + k < nh ? grp * NS + k : -1; }      // the heavy list's index, -1: empty
+    // the classifier: which sub-tiles of the block at (x0, y0) hold the image pixel (x, y) in their window (bit s)
+    CW_FN unsigned reached(int x, int y, int x0, int y0, int d) {
+        unsigned m = 0;
+        for (int s = 0; s < NS; ++s) {
+            const int sx = x0 + (s % NSX) * SX, sy = y0 + (s / NSX) * SY;
+            m |= (x >= sx - d && x < sx + SX + d && y >= sy - d && y < sy + SY + d ? 1u : 0u) << s;
+        }
+        return m;
     }
-    return m;
+    // element j of a slot's halo (cw4_halo_elem) -> its halo pixel (hy, hx) and channel quad hq; its byte offset inside the image of the sub-tile
+    // at (x0, y0), or the marker (present = false: an empty slot - nothing but markers)
+    CW_FN void halo_place(int j, int& hy, int& hx, int& hq) {
+        const int pix = j >> 1;
+        hq = j & 1, hy = pix / HW, hx = pix - hy * HW;
+    }
+    CW_FN unsigned halo_voff(bool present, int j, int x0, int y0, int H, int W, int C) {
+        int hy, hx, hq;
+        halo_place(j, hy, hx, hq);
+        const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+        return present && j < NEL && gy >= 0 && gy < H && gx >= 0 && gx < W ? (unsigned)((gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
+    }
+    // a light sub-tile's elements from cw4_light_elem's (px, py) of the first SX * SY pixels
+    CW_FN void light_pixel(int& px, int& py) {
+        const int p = py * 32 + px;
+        py = p / SX, px = p - py * SX;
+    }
+};
+using Cw4F = Cw4Sub<16, 8>;
+using Cw4Q = Cw4Sub<8, 8>;
+// halo element i = tid + 512 k of a stage (wave (i / 64) % 8, its round k) -> its slot - the wave's - and its element j inside the slot's halo
+// (j >= NEL: none).  16 x 8: waves 2 s, 2 s + 1 share slot s, three of its six rounds each.  8 x 8: wave w stages slot w in four rounds (no element:
+// the last 56 lanes of round 3)
+CW_FN void cw4_halo_elem(Cw4F, int i, int& slot, int& j) {
+    const int wave = (i >> 6) & 7, k = i >> 9, per = Cw4F::ROUNDS / 3, wr = 3 * wave + k;
+    slot = wave / per, j = (wr - slot * Cw4F::ROUNDS) * 64 + (i & 63);
 }
+CW_FN void cw4_halo_elem(Cw4Q, int i, int& slot, int& j) { slot = (i >> 6) & 7, j = (i >> 9) * 64 + (i & 63); }
 // the 16 x 8 marks from the 8 x 8 ones of a block (bit s: sub-tile s)
-CW_FN unsigned cw4q_marks16(unsigned m8) { return ((m8 | (m8 >> 1)) & 1u) | (((m8 >> 2) | (m8 >> 3)) & 1u) << 1 | (((m8 >> 4) | (m8 >> 5)) & 1u) << 2 | (((m8 >> 6) | (m8 >> 7)) & 1u) << 3; }
-// halo element i = tid + 512 k of a stage (wave (i / 64) % 8, its round k = 0..3) -> its slot - the wave - and its element j inside the slot's halo
-// (j >= CW4Q_NEL: none - the last 56 lanes of round 3)
-CW_FN void cw4q_halo_elem(int i, int& slot, int& j) { slot = (i >> 6) & 7, j = (i >> 9) * 64 + (i & 63); }
-CW_FN void cw4q_halo_place(int j, int& hy, int& hx, int& hq) {
-    const int pix = j >> 1;
-    hq = j & 1, hy = pix / CW4Q_HW, hx = pix - hy * CW4Q_HW;
-}
-CW_FN unsigned cw4q_halo_voff(bool present, int j, int x0, int y0, int H, int W, int C) {
-    int hy, hx, hq;
-    cw4q_halo_place(j, hy, hx, hq);
-    const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-    return present && j < CW4Q_NEL && gy >= 0 && gy < H && gx >= 0 && gx < W ? (unsigned)((gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
-}
-// a slot's sub-plane inside a channel plane of the LDS halo buffer (floats): rows of CW4Q_RS floats, two slots side by side 16 floats apart, four slot
+CW_FN unsigned cw4_marks16_of8(unsigned m8) { return ((m8 | (m8 >> 1)) & 1u) | (((m8 >> 2) | (m8 >> 3)) & 1u) << 1 | (((m8 >> 4) | (m8 >> 5)) & 1u) << 2 | (((m8 >> 6) | (m8 >> 7)) & 1u) << 3; }
+// 8 x 8: a slot's sub-plane inside a channel plane of the LDS halo buffer (floats): rows of RS floats, two slots side by side 16 floats apart, four slot
 // rows of ten halo rows with 0 / 8 / 16 floats between them - so that the sixteen patches of either ds_read_b128 lane group of the input transform
 // (lanes 0-3, 12-15, 20-27 | the rest of a half wave, lane = patch) start in sixteen distinct bank quads (tests/test_spade_skip_q8_cpu.py enumerates them;
-// four slots side by side in rows of 48 - 60 floats have no such padding: a patch row is a multiple of four bank quads)
-#define CW4Q_RS 28
-#define CW4Q_PLANE (4 * CW4Q_HH * CW4Q_RS + 24 + 4)        // + 4: 4 PLANE = 16 mod 32, the two channel quads of a pixel fall into different banks
-CW_FN int cw4q_lds_slot(int s) { const int r = s >> 1; return r * (CW4Q_HH * CW4Q_RS) + 4 * r * (r - 1) + (s & 1) * 16; }
-CW_FN int cw4q_lds_patch(int pty, int ptx) {               // the first float of patch (pty, ptx)'s 6 x 6 input window inside a channel plane
-    int ly, lx;
-    cw4q_patch_in_slot(pty, ptx, ly, lx);
-    return cw4q_lds_slot(cw4q_slot_of_patch(pty, ptx)) + 4 * ly * CW4Q_RS + 4 * lx;
-}
-// the epilogue's reader: wave wid, lane -> its output column rb inside a patch and its patch inside the pass (0..15: patch row p / 8 of the pass, patch
-// column p % 8).  A wave's patches of a pass are the 2 x 2 of ONE slot, 4 pass + wid / 2 - image, corner, mean / rstd and the buffer descriptors stay
+// four slots side by side in rows of 48 - 60 floats have no such padding: a patch row is a multiple of four bank quads).  (The 16 x 8 form's placement
+// shares the plain kernel's rows: conv_winograd4.hip, W4FLds.)
+struct Cw4QLds {
+    static constexpr int RS = 28;
+    static constexpr int PLN = 4 * Cw4Q::HH * RS + 24 + 4;  // + 4: 4 PLN = 16 mod 32, the two channel quads of a pixel fall into different banks
+    CW_FN int slot(int s) { const int r = s >> 1; return r * (Cw4Q::HH * RS) + 4 * r * (r - 1) + (s & 1) * 16; }
+    CW_FN int patch(int pty, int ptx) {                      // the first float of patch (pty, ptx)'s 6 x 6 input window inside a channel plane
+        int ly, lx;
+        Cw4Q::patch_in_slot(pty, ptx, ly, lx);
+        return slot(Cw4Q::slot_of_patch(pty, ptx)) + 4 * ly * RS + 4 * lx;
+    }
+};
+// 8 x 8: the epilogue's reader: wave wid, lane -> its output column rb inside a patch and its patch inside the pass (0..15: patch row p / 8 of the pass,
+// patch column p % 8).  A wave's patches of a pass are the 2 x 2 of ONE slot, 4 pass + wid / 2 - image, corner, mean / rstd and the buffer descriptors stay
 // wave-uniform -, its half waves own the output columns 2 (wid % 2) and + 1 (the 16 x 8 form: one column per wave, a slot's 4 x 2 patches per wave pair).
 // gsel / gidx: the lane's ds_read_b128 lane group and its place in it, as in the plain reader - a group reads the eight channel quads of patches a, a + 8
-CW_FN void cw4q_reader(int wid, int lane, int& rb, int& p16) {
+CW_FN void cw4_reader8(int wid, int lane, int& rb, int& p16) {
     const unsigned l5 = (unsigned)lane & 31u, gsel = (0x0FF0F00Fu >> l5) & 1u;
     const int gidx = __builtin_popcount((gsel ? 0x0FF0F00Fu : 0xF00F0FF0u) & ((1u << l5) - 1u));
     rb = 2 * (wid & 1) + (lane >> 5);
     p16 = 2 * (wid >> 1) + (gsel ? 0 : 1) + 8 * (gidx >> 3);
-}
-// a light sub-tile's elements from cw4_light_elem's (px, py) of the first CW4Q_SX * CW4Q_SY pixels
-CW_FN void cw4q_light_pixel(int& px, int& py) {
-    const int p = py * 32 + px;
-    py = p / CW4Q_SX, px = p - py * CW4Q_SX;
 }
 
 // ---- split-K launches of F(4x4) (lwg_conv2d_winograd4_f32_ws): the training step's one-sample launches.  The 4-wave form's blocks

@@ -1,11 +1,13 @@
-// The tile lists of lwg_conv2d_winograd4_list_f32 (conv_winograd4.hip) from a frame batch's resized flows.
+// The tile lists of lwg_conv2d_winograd4_list_f32 / _fine_f32 / _q8_f32 (conv_winograd4.hip) from a frame batch's resized flows.
 // The renderer marks the pixels outside the body with flow -2: no tap of any source falls into the image there, and lwg_lwb_attention_x leaves the SAME
 // vector (bv) at every such pixel of every frame.  A 3x3 convolution block whose whole input window is such pixels computes what the same block of an
 // all-background frame computes - the list-driven convolution copies that instead.  Here: (1) per (frame, 32 x 16 block) one mark - does any pixel of the
 // block's window (the block grown by d pixels, clipped to the image) have an in-image tap of any source, by the attention kernel's own predicate
-// (lwg_lwb_taps.h); (2) one workgroup turns the marks into the heavy and the light tile ids in ascending order (a fixed-order scan, every list slot
-// written by one thread) and their counts - all in device memory, read by the convolution kernel only.
+// (lwg_lwb_taps.h) - and, from the same pass, one mark per sub-tile of the block (lwg_conv_wino.h: Cw4F 16 x 8, Cw4Q 8 x 8) down to the granularity the
+// entry point asks for; (2) one workgroup per granularity turns its marks into the heavy and the light ids in ascending order (a fixed-order scan, every
+// list slot written by one thread) and their counts - all in device memory, read by the convolution kernel only.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "lwg_common.h"
 #include "lwg_conv_wino.h"
 #include "lwg_lwb_taps.h"
@@ -13,15 +15,29 @@
 #define SK_EX 32             // the F(4x4, 3x3) kernel's block: 32 x 16 output pixels
 #define SK_EY 16
 
-// one workgroup per tile (cw_grid's numbering: b * bx * by + ty * bx + tx)
-__global__ __launch_bounds__(256) void lwg_spade_skip_mark_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks) {
+// sub-tile s of the block at (x0, y0): 1 heavy (bit s of m), 0 light, 2 wholly outside the image (neither list)
+template <typename G>
+__device__ __forceinline__ void sk_write_sub(int* __restrict__ out, int t, int s, unsigned m, int x0, int y0, int h, int w) {
+    const bool in = G::in_image(x0 + (s % G::NSX) * G::SX, y0 + (s / G::NSX) * G::SY, h, w);
+    out[G::NS * t + s] = in ? (int)((m >> s) & 1u) : 2;
+}
+// The classifier, G = the finest granularity it writes (void: blocks only, Cw4F: and fmarks, Cw4Q: and fmarks, qmarks).  One workgroup per block (cw_grid's
+// numbering: b * bx * by + ty * bx + tx) evaluates every pixel of the block's window ONCE and notes which of G's sub-tile windows hold it (G::reached) - the
+// block's window is the union of its sub-tiles' windows, so the block's mark (their OR) comes out of the same pass; the 16 x 8 marks under Cw4Q are the ORs
+// of their two halves (cw4_marks16_of8): every granularity from one evaluation of each window pixel.
+template <typename G>
+__global__ __launch_bounds__(256) void lwg_spade_skip_mark_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks,
+                                                                  int* __restrict__ fmarks, int* __restrict__ qmarks) {
+    constexpr bool SUB = !std::is_void<G>::value, Q8 = std::is_same<G, Cw4Q>::value;
+    using GS = std::conditional_t<SUB, G, Cw4F>;             // (names G's members where SUB is false and nothing uses them)
+    constexpr int NS = SUB ? GS::NS : 0;
     const CwGrid g = cw_grid(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
     const int t = blockIdx.x, b = cw_image(g, t);
     int x0, y0;
     cw_corner(g, t - b * g.bx * g.by, SK_EX, SK_EY, x0, y0);
     const CwWindow win = cw_block_window(x0, y0, SK_EX, SK_EY, d, h, w);
     const int ww = win.x1 - win.x0, n = ww * (win.y1 - win.y0);
-    bool mine = false;
+    unsigned mine = 0;                                        // bit s: sub-tile s of G, bit NS: the block
     for (int s = 0; s < ns; ++s) {
         const float2* Ts = T + ((size_t)b * ns + s) * h * w;
         for (int i = threadIdx.x; i < n; i += 256) {
@@ -29,78 +45,32 @@ __global__ __launch_bounds__(256) void lwg_spade_skip_mark_kernel(const float2* 
             float wt[4];
             int tx0, ty0;
             lwb_taps_of(Ts[(size_t)y * w + x], w, h, wt, tx0, ty0);
-            mine |= lwb_tap_in_image(tx0, ty0, w, h);
-        }
-    }
-    const int any = __syncthreads_or(mine ? 1 : 0);
-    if (threadIdx.x == 0) marks[t] = any ? 1 : 0;
-}
-
-// ONE workgroup: thread i owns the marks [i per, (i + 1) per); counts per thread, an inclusive scan over the 1024 threads in LDS, then every thread writes
-// its tiles behind the heavy / light tiles of the threads before it - both lists ascending
-__global__ __launch_bounds__(1024) void lwg_spade_skip_scan_kernel(const int* __restrict__ marks, int n, int* __restrict__ heavy, int* __restrict__ light,
-                                                                   int* __restrict__ counts) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x, per = (n + 1023) / 1024;
-    const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
-    int c = 0;
-    for (int i = i0; i < i1; ++i) c += marks[i] != 0;
-    part[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int hv = part[tid] - c;                                   // heavy tiles before i0
-    for (int i = i0; i < i1; ++i) {
-        if (marks[i] != 0) heavy[hv++] = i;
-        else light[i - hv] = i;
-    }
-    if (tid == 1023) {
-        counts[0] = part[1023];
-        counts[1] = n - part[1023];
-    }
-}
-
-// The sub-tile classifier (lwg_conv_wino.h: CW4F_SX x CW4F_SY sub-tiles, CW4F_NS per block): one workgroup per block evaluates every pixel of the
-// block's window ONCE and notes which sub-tile windows hold it - the block's window is the union of its sub-tiles' windows, so the block's mark (their
-// OR) comes out of the same pass.  fmarks[CW4F_NS t + s]: 1 heavy, 0 light, 2 wholly outside the image (neither list).
-__global__ __launch_bounds__(256) void lwg_spade_skip_mark_fine_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks,
-                                                                       int* __restrict__ fmarks) {
-    const CwGrid g = cw_grid(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
-    const int t = blockIdx.x, b = cw_image(g, t);
-    int x0, y0;
-    cw_corner(g, t - b * g.bx * g.by, SK_EX, SK_EY, x0, y0);
-    const CwWindow win = cw_block_window(x0, y0, SK_EX, SK_EY, d, h, w);
-    const int ww = win.x1 - win.x0, n = ww * (win.y1 - win.y0);
-    unsigned mine = 0;                                        // bit s: sub-tile s, bit CW4F_NS: the block
-    for (int s = 0; s < ns; ++s) {
-        const float2* Ts = T + ((size_t)b * ns + s) * h * w;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int yy = i / ww, y = win.y0 + yy, x = win.x0 + (i - yy * ww);
-            float wt[4];
-            int tx0, ty0;
-            lwb_taps_of(Ts[(size_t)y * w + x], w, h, wt, tx0, ty0);
-            if (lwb_tap_in_image(tx0, ty0, w, h)) mine |= (1u << CW4F_NS) | cw4f_reached(x, y, x0, y0, d);
+            if (lwb_tap_in_image(tx0, ty0, w, h)) mine |= (1u << NS) | (SUB ? GS::reached(x, y, x0, y0, d) : 0u);
         }
     }
     unsigned all = 0;
-    for (int s = 0; s <= CW4F_NS; ++s) all |= __syncthreads_or((int)((mine >> s) & 1u)) ? 1u << s : 0u;
-    if (threadIdx.x < CW4F_NS) {
-        const int s = threadIdx.x;
-        const bool in = cw4f_in_image(x0 + (s % CW4F_NSX) * CW4F_SX, y0 + (s / CW4F_NSX) * CW4F_SY, h, w);
-        fmarks[CW4F_NS * t + s] = in ? (int)((all >> s) & 1u) : 2;
-    } else if (threadIdx.x == CW4F_NS) {
-        marks[t] = (int)((all >> CW4F_NS) & 1u);
+    for (int s = 0; s <= NS; ++s) all |= __syncthreads_or((int)((mine >> s) & 1u)) ? 1u << s : 0u;
+    // the write-out, one thread per mark: the finest sub-tiles, then each coarser level from the finer one, then the block
+    int s = threadIdx.x;
+    unsigned m = all;
+    if constexpr (Q8) {
+        if (s < Cw4Q::NS) return sk_write_sub<Cw4Q>(qmarks, t, s, m, x0, y0, h, w);
+        s -= Cw4Q::NS, m = cw4_marks16_of8(m);
     }
+    if constexpr (SUB) {
+        if (s < Cw4F::NS) return sk_write_sub<Cw4F>(fmarks, t, s, m, x0, y0, h, w);
+        s -= Cw4F::NS;
+    }
+    if (s == 0) marks[t] = (int)((all >> NS) & 1u);
 }
 
-// Two workgroups, one per mark array (blockIdx.x = 0: the blocks, 1: the sub-tiles): the scan above for marks of three classes - both counts scanned
-// over the 1024 threads, every list slot written by one thread, both lists ascending.  A thread's marks are a multiple of four and read 16 bytes at a
-// time where the array is so aligned (the sub-tiles' 150 marks per thread at 256^2 x 300 frames, one by one: 110 us of load latency per launch)
-struct SkScanJob { const int* marks; int n; int* heavy; int* light; int* counts; };
+// The scan: one workgroup per mark array (blockIdx.x = 0: the blocks, 1: the 16 x 8, 2: the 8 x 8 sub-tiles).  Thread i owns the marks [i per,
+// (i + 1) per); the heavy and the light counts per thread, an inclusive scan of both over the 1024 threads in LDS, then every thread writes its ids
+// behind those of the threads before it - every list slot written by one thread, both lists ascending.  A thread's marks are a multiple of four and
+// read 16 bytes at a time where the array is so aligned (the sub-tiles' 150 marks per thread at 256^2 x 300 frames, one by one: 110 us of load
+// latency per launch)
+struct SkScanJob { int* marks; int n; int* heavy; int* light; int* counts; };
+struct SkScanJobs { SkScanJob j[3]; };
 template <typename F>
 __device__ __forceinline__ void sk_for_marks(const int* __restrict__ marks, int i0, int i1, bool vec, F f) {
     int i = i0;
@@ -111,8 +81,9 @@ __device__ __forceinline__ void sk_for_marks(const int* __restrict__ marks, int 
         }
     for (; i < i1; ++i) f(i, marks[i]);
 }
-__device__ __forceinline__ void sk_scan_job(const SkScanJob j) {
+__global__ __launch_bounds__(1024) void lwg_spade_skip_scan_kernel(SkScanJobs js) {
     __shared__ int ph[1024], pl[1024];
+    const SkScanJob j = blockIdx.x == 0 ? js.j[0] : blockIdx.x == 1 ? js.j[1] : js.j[2];
     const int tid = threadIdx.x, n = j.n, per = ((n + 1023) / 1024 + 3) & ~3;
     const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
     const bool vec = (reinterpret_cast<size_t>(j.marks) & 15) == 0;
@@ -128,99 +99,47 @@ __device__ __forceinline__ void sk_scan_job(const SkScanJob j) {
     }
     int hv = ph[tid] - ch, lt = pl[tid] - cl;                 // heavy / light entries before i0
     sk_for_marks(j.marks, i0, i1, vec, [&](int i, int m) {
-        if (m == 1) j.heavy[hv++] = i;
-        else if (m == 0) j.light[lt++] = i;
+        if (m == 1) j.heavy[hv] = i;
+        if (m == 0) j.light[lt] = i;
+        hv += m == 1, lt += m == 0;                           // (counters as sums: as an if / else pair they become an indexed pair in scratch memory)
     });
     if (tid == 1023) {
         j.counts[0] = ph[1023];
         j.counts[1] = pl[1023];
     }
 }
-__global__ __launch_bounds__(1024) void lwg_spade_skip_scan2_kernel(SkScanJob j0, SkScanJob j1) {
-    const SkScanJob j = blockIdx.x == 0 ? j0 : j1;
-    sk_scan_job(j);
-}
-// ... three of them: the blocks, the 16 x 8 and the 8 x 8 sub-tiles
-__global__ __launch_bounds__(1024) void lwg_spade_skip_scan3_kernel(SkScanJob j0, SkScanJob j1, SkScanJob j2) {
-    const SkScanJob j = blockIdx.x == 0 ? j0 : blockIdx.x == 1 ? j1 : j2;
-    sk_scan_job(j);
-}
 
-// The classifier at 8 x 8 sub-tiles (lwg_conv_wino.h: CW4Q_*): the pass of lwg_spade_skip_mark_fine_kernel with eight window bits per pixel; the 16 x 8
-// marks are the ORs of their two halves (cw4q_marks16), the block's mark the OR of all - every granularity from ONE evaluation of each window pixel.
-// qmarks[CW4Q_NS t + s] as fmarks: 1 heavy, 0 light, 2 wholly outside the image.
-__global__ __launch_bounds__(256) void lwg_spade_skip_mark_q8_kernel(const float2* __restrict__ T, int B, int ns, int h, int w, int d, int* __restrict__ marks,
-                                                                     int* __restrict__ fmarks, int* __restrict__ qmarks) {
-    const CwGrid g = cw_grid(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
-    const int t = blockIdx.x, b = cw_image(g, t);
-    int x0, y0;
-    cw_corner(g, t - b * g.bx * g.by, SK_EX, SK_EY, x0, y0);
-    const CwWindow win = cw_block_window(x0, y0, SK_EX, SK_EY, d, h, w);
-    const int ww = win.x1 - win.x0, n = ww * (win.y1 - win.y0);
-    unsigned mine = 0;                                        // bit s: 8 x 8 sub-tile s, bit CW4Q_NS: the block
-    for (int s = 0; s < ns; ++s) {
-        const float2* Ts = T + ((size_t)b * ns + s) * h * w;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int yy = i / ww, y = win.y0 + yy, x = win.x0 + (i - yy * ww);
-            float wt[4];
-            int tx0, ty0;
-            lwb_taps_of(Ts[(size_t)y * w + x], w, h, wt, tx0, ty0);
-            if (lwb_tap_in_image(tx0, ty0, w, h)) mine |= (1u << CW4Q_NS) | cw4q_reached(x, y, x0, y0, d);
-        }
-    }
-    unsigned all = 0;
-    for (int s = 0; s <= CW4Q_NS; ++s) all |= __syncthreads_or((int)((mine >> s) & 1u)) ? 1u << s : 0u;
-    const int s = threadIdx.x;
-    if (s < CW4Q_NS) {
-        const bool in = cw4q_in_image(x0 + (s % CW4Q_NSX) * CW4Q_SX, y0 + (s / CW4Q_NSX) * CW4Q_SY, h, w);
-        qmarks[CW4Q_NS * t + s] = in ? (int)((all >> s) & 1u) : 2;
-    } else if (s < CW4Q_NS + CW4F_NS) {
-        const int f = s - CW4Q_NS;
-        const bool in = cw4f_in_image(x0 + (f % CW4F_NSX) * CW4F_SX, y0 + (f / CW4F_NSX) * CW4F_SY, h, w);
-        fmarks[CW4F_NS * t + f] = in ? (int)((cw4q_marks16(all) >> f) & 1u) : 2;
-    } else if (s == CW4Q_NS + CW4F_NS) {
-        marks[t] = (int)((all >> CW4Q_NS) & 1u);
-    }
-}
-
-extern "C" int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
-                                             int* fmarks, int* fheavy, int* flight, int* fcounts, lwg_stream_t stream_) {
-    if (!T || !marks || !heavy || !light || !counts || !fmarks || !fheavy || !flight || !fcounts || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64)
-        return (int)hipErrorInvalidValue;
+// The two launches of every entry point; js.j[0 .. levels): the blocks, the 16 x 8, the 8 x 8 sub-tiles (levels = 1 + what G adds; n is filled in here)
+template <typename G>
+static int sk_lists(const float* T, int B, int ns, int h, int w, int d, SkScanJobs js, lwg_stream_t stream_) {
+    constexpr int levels = std::is_void<G>::value ? 1 : std::is_same<G, Cw4F>::value ? 2 : 3;
+    constexpr int per[3] = {1, Cw4F::NS, Cw4Q::NS};
+    for (int i = 0; i < levels; ++i)
+        if (!js.j[i].marks || !js.j[i].heavy || !js.j[i].light || !js.j[i].counts) return (int)hipErrorInvalidValue;
+    if (!T || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64) return (int)hipErrorInvalidValue;
     const long long tiles = cw_total_blocks(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
-    if (tiles * CW4F_NS >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
+    if (tiles * per[levels - 1] >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < levels; ++i) js.j[i].n = (int)tiles * per[i];
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(lwg_spade_skip_mark_fine_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks, fmarks);
-    hipLaunchKernelGGL(lwg_spade_skip_scan2_kernel, dim3(2), dim3(1024), 0, stream, SkScanJob{marks, (int)tiles, heavy, light, counts},
-                       SkScanJob{fmarks, (int)tiles * CW4F_NS, fheavy, flight, fcounts});
+    hipLaunchKernelGGL(lwg_spade_skip_mark_kernel<G>, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d,
+                       js.j[0].marks, js.j[1].marks, js.j[2].marks);
+    hipLaunchKernelGGL(lwg_spade_skip_scan_kernel, dim3(levels), dim3(1024), 0, stream, js);
     return (int)hipGetLastError();
 }
 
 extern "C" int lwg_spade_skip_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
                                         lwg_stream_t stream_) {
-    if (!T || !marks || !heavy || !light || !counts || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64) return (int)hipErrorInvalidValue;
-    const long long tiles = cw_total_blocks(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
-    if (tiles >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(lwg_spade_skip_mark_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks);
-    hipLaunchKernelGGL(lwg_spade_skip_scan_kernel, dim3(1), dim3(1024), 0, stream, marks, (int)tiles, heavy, light, counts);
-    return (int)hipGetLastError();
+    return sk_lists<void>(T, B, ns, h, w, d, SkScanJobs{{{marks, 0, heavy, light, counts}, {}, {}}}, stream_);
 }
-
+extern "C" int lwg_spade_skip_fine_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
+                                             int* fmarks, int* fheavy, int* flight, int* fcounts, lwg_stream_t stream_) {
+    return sk_lists<Cw4F>(T, B, ns, h, w, d, SkScanJobs{{{marks, 0, heavy, light, counts}, {fmarks, 0, fheavy, flight, fcounts}, {}}}, stream_);
+}
 // The block lists, the 16 x 8 lists (both as lwg_spade_skip_fine_lists_f32 leaves them) AND the 8 x 8 lists (qmarks, qheavy, qlight: 8 * B * tiles ints
 // each, qcounts: 2 ints) in the same two launches
 extern "C" int lwg_spade_skip_q8_lists_f32(const float* T, int B, int ns, int h, int w, int d, int* marks, int* heavy, int* light, int* counts,
                                            int* fmarks, int* fheavy, int* flight, int* fcounts, int* qmarks, int* qheavy, int* qlight, int* qcounts,
                                            lwg_stream_t stream_) {
-    if (!T || !marks || !heavy || !light || !counts || !fmarks || !fheavy || !flight || !fcounts || !qmarks || !qheavy || !qlight || !qcounts || B <= 0 ||
-        ns <= 0 || h <= 0 || w <= 0 || d < 0 || d > 64)
-        return (int)hipErrorInvalidValue;
-    const long long tiles = cw_total_blocks(B, h, w, CW_NB, SK_EX, SK_EY, CW_NB);
-    if (tiles * CW4Q_NS >= (1ll << 30) || (long long)h * w >= (1ll << 30)) return (int)hipErrorInvalidValue;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(lwg_spade_skip_mark_q8_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, reinterpret_cast<const float2*>(T), B, ns, h, w, d, marks, fmarks,
-                       qmarks);
-    hipLaunchKernelGGL(lwg_spade_skip_scan3_kernel, dim3(3), dim3(1024), 0, stream, SkScanJob{marks, (int)tiles, heavy, light, counts},
-                       SkScanJob{fmarks, (int)tiles * CW4F_NS, fheavy, flight, fcounts}, SkScanJob{qmarks, (int)tiles * CW4Q_NS, qheavy, qlight, qcounts});
-    return (int)hipGetLastError();
+    return sk_lists<Cw4Q>(T, B, ns, h, w, d,
+                          SkScanJobs{{{marks, 0, heavy, light, counts}, {fmarks, 0, fheavy, flight, fcounts}, {qmarks, 0, qheavy, qlight, qcounts}}}, stream_);
 }

@@ -477,28 +477,22 @@ def spade_skip_lists(flow, d):
     assert two == 2 and flow.dtype == torch.float32
     tiles = B * ((h + 15) // 16) * ((w + 31) // 32)
     q8 = spade_skip_q8_lists_apply(tiles, h, w)
-    buf = torch.empty((39 if q8 else 15) * tiles + 8, device=flow.device, dtype=torch.int32)
-    if q8:
-        qb, buf = buf[:24 * tiles], buf[24 * tiles:]         # (marks first: 16-byte aligned)
-        qmarks, qheavy, qlight = qb[:8 * tiles], qb[8 * tiles:16 * tiles], qb[16 * tiles:]
-    fmarks, fheavy, flight = buf[:4 * tiles], buf[4 * tiles:8 * tiles], buf[8 * tiles:12 * tiles]      # (the sub-tiles' marks first: 16-byte aligned)
-    bb = buf[12 * tiles:]
-    marks, heavy, light, counts, fcounts = bb[:tiles], bb[tiles:2 * tiles], bb[2 * tiles:3 * tiles], bb[3 * tiles:3 * tiles + 2], bb[3 * tiles + 2:3 * tiles + 4]
-    i32 = torch.int32
-    if q8:
-        qcounts = bb[3 * tiles + 4:3 * tiles + 6]
-        _lib.check(_lib.lib().lwg_spade_skip_q8_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
-                                                          _ptr(counts, i32), _ptr(fmarks, i32), _ptr(fheavy, i32), _ptr(flight, i32), _ptr(fcounts, i32),
-                                                          _ptr(qmarks, i32), _ptr(qheavy, i32), _ptr(qlight, i32), _ptr(qcounts, i32), _stream()),
-                   "lwg_spade_skip_q8_lists_f32")
-        out = SkipLists((heavy, light, counts))
-        out.fine, out.fine8 = (fheavy, flight, fcounts), (qheavy, qlight, qcounts)
-        return out
-    _lib.check(_lib.lib().lwg_spade_skip_fine_lists_f32(_ptr(flow), B, ns, h, w, int(d), _ptr(marks, i32), _ptr(heavy, i32), _ptr(light, i32),
-                                                        _ptr(counts, i32), _ptr(fmarks, i32), _ptr(fheavy, i32), _ptr(flight, i32), _ptr(fcounts, i32),
-                                                        _stream()), "lwg_spade_skip_fine_lists_f32")
-    out = SkipLists((heavy, light, counts))
-    out.fine = (fheavy, flight, fcounts)
+    # one buffer: per level (marks, heavy, light) of `per` entries per block, the finest level first (every marks array 16-byte aligned), then the
+    # levels' counts - blocks, 16 x 8, 8 x 8
+    per = ([8] if q8 else []) + [4, 1]
+    n = 3 * sum(per) * tiles
+    buf = torch.empty(n + 8, device=flow.device, dtype=torch.int32)
+    levels, off = [], 0
+    for p in per:
+        levels.insert(0, [buf[off + i * p * tiles:off + (i + 1) * p * tiles] for i in range(3)])
+        off += 3 * p * tiles
+    for i, lv in enumerate(levels):
+        lv.append(buf[n + 2 * i:n + 2 * i + 2])
+    name = "lwg_spade_skip_q8_lists_f32" if q8 else "lwg_spade_skip_fine_lists_f32"
+    _lib.check(getattr(_lib.lib(), name)(_ptr(flow), B, ns, h, w, int(d), *[_ptr(t, torch.int32) for lv in levels for t in lv], _stream()), name)
+    out = SkipLists(levels[0][1:])
+    out.fine = tuple(levels[1][1:])
+    out.fine8 = tuple(levels[2][1:]) if q8 else None
     return out
 
 
@@ -659,22 +653,18 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
             a.w = _ptr(_wwino4(spec))
             kind = "winograd4"
             if lists is not None:
-                i32 = torch.int32
-                fine = len(lists) == 2 and isinstance(lists[0], SkipLists)
-                if fine:
+                # the granularity -> its (heavy, light, counts) and entry point: a plain 4-tuple is block lists with their calibration frame
+                name = "lwg_conv2d_winograd4_list_f32"
+                if len(lists) == 2 and isinstance(lists[0], SkipLists):
                     sl, cal = lists
-                    fine = sl.fine is not None and spade_skip_fine_apply(x0)
-                    q8 = fine and sl.fine8 is not None and spade_skip_q8_apply(x0, spec.N // 64)
-                    lists = tuple(sl.fine8 if q8 else sl.fine if fine else sl) + (cal,)
-                else:
-                    q8 = False
-                ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32), _ptr(lists[3]))
-                if q8:
-                    _lib.check(_lib.lib().lwg_conv2d_winograd4_q8_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_q8_f32")
-                elif fine:
-                    _lib.check(_lib.lib().lwg_conv2d_winograd4_fine_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_fine_f32")
-                else:
-                    _lib.check(_lib.lib().lwg_conv2d_winograd4_list_f32(a, ctypes.byref(ld), _stream()), "lwg_conv2d_winograd4_list_f32")
+                    trip = sl
+                    if sl.fine is not None and spade_skip_fine_apply(x0):
+                        trip, name = sl.fine, "lwg_conv2d_winograd4_fine_f32"
+                        if sl.fine8 is not None and spade_skip_q8_apply(x0, spec.N // 64):
+                            trip, name = sl.fine8, "lwg_conv2d_winograd4_q8_f32"
+                    lists = tuple(trip) + (cal,)
+                ld = _lib.LwgConvLists(*[_ptr(t, torch.int32) for t in lists[:3]], _ptr(lists[3]))
+                _lib.check(getattr(_lib.lib(), name)(a, ctypes.byref(ld), _stream()), name)
             elif nws:                               # a training launch (train_conv_tiles("4x4")) split over K
                 ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
                 _lib.check(_lib.lib().lwg_conv2d_winograd4_f32_ws(a, _ptr(ws), _stream()), "lwg_conv2d_winograd4_f32_ws")

@@ -224,3 +224,39 @@ def test_calibration_frames_follow_the_packed_weights():
         finally:
             with torch.no_grad():
                 w.div_(1.5)
+
+
+# ---- the classifier's three entry points ----
+
+@pytest.mark.parametrize("B,h,w", [(2, 40, 72), (1, 1, 8)])
+@pytest.mark.parametrize("d", [1, 5])
+def test_three_classifier_entry_points_agree(B, h, w, d):
+    """lwg_spade_skip_lists_f32 (blocks), _fine_lists_f32 (and 16 x 8) and _q8_lists_f32 (and 8 x 8) run one classifier and one scan: what they share
+    is bitwise the same - the block marks, lists and counts of all three, the 16 x 8 ones of the latter two.  Frame 0: a body in the middle of a
+    background frame, the last frame all background; 40 x 72 has ragged blocks and sub-tiles wholly outside the image (class-2 marks)."""
+    ns, i32 = 2, torch.int32
+    T = torch.full((B, ns, h, w, 2), -2.0)
+    ys, xs = slice(h // 4, max(3 * h // 4, 1)), slice(w // 4, 3 * w // 4)
+    T[0, 0, ys, xs] = _rand((B, ns, h, w, 2), 31, 0.5).clamp(-0.9, 0.9)[0, 0, ys, xs]
+    T = T.to(DEV)
+    tiles = B * ((h + 15) // 16) * ((w + 31) // 32)
+
+    def level(per):                                           # marks, heavy, light (poisoned: the lists' tails are compared too), counts
+        return [torch.full((per * tiles,), -7, device=DEV, dtype=i32) for _ in range(3)] + [torch.full((2,), -7, device=DEV, dtype=i32)]
+
+    def run(name, pers):
+        out = [level(p) for p in pers]
+        ops._lib.check(getattr(ops._lib.lib(), name)(ops._ptr(T), B, ns, h, w, d, *[ops._ptr(t, i32) for lv in out for t in lv], ops._stream()), name)
+        return out
+
+    blk, fine, q8 = run("lwg_spade_skip_lists_f32", (1,)), run("lwg_spade_skip_fine_lists_f32", (1, 4)), run("lwg_spade_skip_q8_lists_f32", (1, 4, 8))
+    torch.cuda.synchronize()
+    for other in (fine, q8):
+        for a, b in zip(blk[0], other[0]):
+            assert torch.equal(a, b)
+    for a, b in zip(fine[1], q8[1]):
+        assert torch.equal(a, b)
+    marks, _, _, counts = blk[0]
+    fmarks, fcounts = fine[1][0], fine[1][3]
+    assert int(counts.sum()) == tiles and set(marks.tolist()) <= {0, 1} and int(counts[0]) == int(marks.sum()) and 0 < int(counts[0]) <= tiles // B
+    assert int(fcounts.sum()) == B * ((h + 7) // 8) * ((w + 15) // 16) and ((fmarks == 2).any().item() == (h % 16 in range(1, 9) or w % 32 in range(1, 17)))

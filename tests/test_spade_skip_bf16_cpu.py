@@ -32,10 +32,10 @@ static u64 bad = 0, walked = 0, exited = 0, elems = 0;
 static std::vector<int> in_image(int B, int H, int W) {
     const CwGrid g = cw_grid(B, H, W, CW_NB, 32, 16, CW_NB);
     std::vector<int> ids;
-    for (int u = 0; u < g.tiles * CW4F_NS; ++u) {
+    for (int u = 0; u < g.tiles * Cw4F::NS; ++u) {
         int b, x0, y0;
-        cw4f_corner(g, u, b, x0, y0);
-        if (cw4f_in_image(x0, y0, H, W)) ids.push_back(u);
+        Cw4F::corner(g, u, b, x0, y0);
+        if (Cw4F::in_image(x0, y0, H, W)) ids.push_back(u);
     }
     return ids;
 }
@@ -44,7 +44,7 @@ static std::vector<int> in_image(int B, int H, int W) {
 static void walk_case(int B, int H, int W, int tiles_n, int heavy_mode, int c0, int c1) {
     const std::vector<int> ids = in_image(B, H, W);
     const int total = (int)ids.size();
-    if (total != cw4f_in_image_total(B, H, W)) FAIL("total %d != %d", total, cw4f_in_image_total(B, H, W));
+    if (total != Cw4F::in_image_total(B, H, W)) FAIL("total %d != %d", total, Cw4F::in_image_total(B, H, W));
     std::vector<int> heavy, light;
     for (int k = 0; k < total; ++k) {
         const bool h = heavy_mode == 2 || (heavy_mode == 1 && k == total / 2) || (heavy_mode == 3 && (k % 3 == 0 || k == total - 1));
@@ -80,7 +80,7 @@ static void walk_case(int B, int H, int W, int tiles_n, int heavy_mode, int c0, 
         }
         if (b < 0 || b >= B || x0 < 0 || x0 >= W || y0 < 0 || y0 >= H || x0 % 16 || y0 % 8) { FAIL("corner %d %d %d", b, x0, y0); continue; }
         // the sub-tile's class by the lists = the kind of the entry that visits it
-        const int u_here = CW4F_NS * ((b * ((H + 15) / 16) + y0 / 16) * ((W + 31) / 32) + x0 / 32) + 2 * ((y0 % 16) / 8) + (x0 % 32) / 16;
+        const int u_here = Cw4F::NS * ((b * ((H + 15) / 16) + y0 / 16) * ((W + 31) / 32) + x0 / 32) + 2 * ((y0 % 16) / 8) + (x0 % 32) / 16;
         bool is_heavy = false;
         for (int v : heavy) is_heavy |= v == u_here;
         if (is_heavy != (kind == HRL_HEAVY)) FAIL("kind of sub-tile %d", u_here);
@@ -94,8 +94,8 @@ static void walk_case(int B, int H, int W, int tiles_n, int heavy_mode, int c0, 
     // ids that are no sub-tile of the launch
     int b, x0, y0;
     const CwGrid g = cw_grid(B, H, W, CW_NB, 32, 16, CW_NB);
-    if (hrl_locate(-1, B, H, W, b, x0, y0) || hrl_locate(g.tiles * CW4F_NS, B, H, W, b, x0, y0) || hrl_locate(0x7fffffff, B, H, W, b, x0, y0)) FAIL("locate took a foreign id");
-    for (int u = 0; u < g.tiles * CW4F_NS; ++u) {
+    if (hrl_locate(-1, B, H, W, b, x0, y0) || hrl_locate(g.tiles * Cw4F::NS, B, H, W, b, x0, y0) || hrl_locate(0x7fffffff, B, H, W, b, x0, y0)) FAIL("locate took a foreign id");
+    for (int u = 0; u < g.tiles * Cw4F::NS; ++u) {
         bool in = false;
         for (int v : ids) in |= v == u;
         if (hrl_locate(u, B, H, W, b, x0, y0) != in) FAIL("locate(%d)", u);
@@ -108,13 +108,13 @@ static void light_case(int H, int W, int N, int YC, int ycoff) {
     for (int y0 = 0; y0 < H; y0 += 8)
         for (int x0 = 0; x0 < W; x0 += 16)
             for (int tile_n = 0; tile_n < N / HRL_BN; ++tile_n) {
-                std::vector<int> sub((size_t)CW4F_SX * CW4F_SY * HRL_BN, 0);
+                std::vector<int> sub((size_t)Cw4F::SX * Cw4F::SY * HRL_BN, 0);
                 for (int wn = 0; wn < 4; ++wn)
                     for (int lane = 0; lane < 64; ++lane)
                         for (int i = 0; i < HRL_TM; ++i) {
                             int py, px;
                             hrl_lane_pixel(lane, i, py, px);
-                            if (py < 0 || py >= CW4F_SY || px < 0 || px >= CW4F_SX) { FAIL("lane pixel"); continue; }
+                            if (py < 0 || py >= Cw4F::SY || px < 0 || px >= Cw4F::SX) { FAIL("lane pixel"); continue; }
                             const int oy = y0 + py, ox = x0 + px, khalf = lane >> 5, ncol = tile_n * HRL_BN + wn * 32;
                             if (oy >= H || ox >= W) continue;                    // a dead lane: nothing read beyond offset 0, nothing stored
                             const size_t o = hrl_acc_offset(oy, ox, W, N, ncol, khalf);
@@ -123,7 +123,7 @@ static void light_case(int H, int W, int N, int YC, int ycoff) {
                                 const int col = ncol + hrl_acc_column(khalf, r);
                                 if (o + r >= facc.size()) { FAIL("accumulator offset outside the frame"); continue; }
                                 ++facc[o + r];
-                                ++sub[(size_t)(py * CW4F_SX + px) * HRL_BN + col - tile_n * HRL_BN];
+                                ++sub[(size_t)(py * Cw4F::SX + px) * HRL_BN + col - tile_n * HRL_BN];
                                 // the frame is the panel's columns per pixel: a 32-column tile is stored [khalf][r]
                                 if (o + r != ((size_t)oy * W + ox) * N + (size_t)(ncol + 16 * khalf + r)) FAIL("accumulator layout");
                                 ++elems;
@@ -136,10 +136,10 @@ static void light_case(int H, int W, int N, int YC, int ycoff) {
                                 ++fcpy[c + j];
                             }
                         }
-                for (int py = 0; py < CW4F_SY; ++py)
-                    for (int px = 0; px < CW4F_SX; ++px)
+                for (int py = 0; py < Cw4F::SY; ++py)
+                    for (int px = 0; px < Cw4F::SX; ++px)
                         for (int c = 0; c < HRL_BN; ++c)
-                            if (sub[(size_t)(py * CW4F_SX + px) * HRL_BN + c] != (y0 + py < H && x0 + px < W ? 1 : 0)) FAIL("(pixel, column) of a sub-tile");
+                            if (sub[(size_t)(py * Cw4F::SX + px) * HRL_BN + c] != (y0 + py < H && x0 + px < W ? 1 : 0)) FAIL("(pixel, column) of a sub-tile");
             }
     for (int v : facc) if (v != 1) FAIL("accumulator float touched %d times (H=%d W=%d N=%d)", v, H, W, N);
     for (size_t k = 0; k < fcpy.size(); ++k) {
@@ -180,7 +180,7 @@ static void contract_case() {
 }
 
 int main() {
-    if (HRL_BN != 128 || HRL_TM != 4 || CW4F_SX != 16 || CW4F_SY != 8) FAIL("constants");
+    if (HRL_BN != 128 || HRL_TM != 4 || Cw4F::SX != 16 || Cw4F::SY != 8) FAIL("constants");
 @MAIN@
     contract_case();
     printf("walked %llu exited %llu elems %llu bad %llu\n", walked, exited, elems, bad);
@@ -234,7 +234,9 @@ def test_kernel_goes_through_the_shared_functions():
                  "hrl_grid(a.B, a.OH, a.OW, a.N / HRL_BN)"):
         assert call in k, call
     h = open(os.path.join(CSRC, "lwg_bf16_hr_list.h")).read()
-    assert "#define CW4F_SX" not in h and "#define CW4F_SX" not in k and '#include "lwg_conv_wino.h"' in h
+    for own in ("Cw4Sub<", "struct Cw4", "#define SX", "int SX ="):
+        assert own not in h and own not in k, own
+    assert '#include "lwg_conv_wino.h"' in h and "Cw4F::SX" in h
 
 
 # ---- the window reach d: a numpy model of the two SPADE convolutions as the direct kernel computes them ----

@@ -1,10 +1,10 @@
-"""CPU checks of the integer arithmetic behind the sub-tile form of the list-driven F(4x4, 3x3) convolution (csrc/lwg_conv_wino.h part 1: CW4F_*,
-cw4f_corner, cw4f_reached, cw4f_slot_of_patch, cw4f_slot_index, cw4f_halo_elem, cw4f_halo_voff, cw4f_light_pixel) - the very functions the kernels
+"""CPU checks of the integer arithmetic behind the sub-tile form of the list-driven F(4x4, 3x3) convolution (csrc/lwg_conv_wino.h part 1: Cw4F =
+Cw4Sub<16, 8> - corner, reached, slot_of_patch, slot_index, halo_voff, light_pixel - and cw4_halo_elem) - the very functions the kernels
 compile, built into a host program with signed-overflow traps as tests/test_spade_skip_cpu.py does.
 
   * sub-tile numbering and windows: sub-tile 4 t + s of block t, its corner, its window against the definition pixel by pixel, which sub-tiles lie in
     the image - on ragged images (40 x 72: the lower sub-tiles of the last block row and the right ones of the last block column are outside);
-  * the classifier's one-pass rule: bit s of cw4f_reached = "the pixel lies in sub-tile s's window", and on random foreground masks the block's mark is
+  * the classifier's one-pass rule: bit s of Cw4F::reached = "the pixel lies in sub-tile s's window", and on random foreground masks the block's mark is
     the OR of its in-image sub-tiles' marks;
   * the group walk of every workgroup for heavy counts 0, 1, 3, 4, 5 and 4 k + 2 and 2, 4, 8 column blocks: every (sub-tile, column block) exactly
     once, empty slots only in the last group; the light entries behind them exactly once;
@@ -39,36 +39,36 @@ static void numbering_case(int B, int H, int W, int d) {
         int bx0, by0;
         cw_corner(g, t - b * g.bx * g.by, 32, 16, bx0, by0);
         const CwWindow bw = cw_block_window(bx0, by0, 32, 16, d, H, W);
-        for (int s = 0; s < CW4F_NS; ++s) {
+        for (int s = 0; s < Cw4F::NS; ++s) {
             int ub, x0, y0;
-            cw4f_corner(g, CW4F_NS * t + s, ub, x0, y0);
+            Cw4F::corner(g, Cw4F::NS * t + s, ub, x0, y0);
             if (ub != b || x0 != bx0 + (s & 1) * 16 || y0 != by0 + (s >> 1) * 8) FAIL("corner t=%d s=%d: %d %d %d", t, s, ub, x0, y0);
-            const bool in = cw4f_in_image(x0, y0, H, W);
+            const bool in = Cw4F::in_image(x0, y0, H, W);
             if (in != (x0 < W && y0 < H)) FAIL("in_image");
             inside += in;
             ++subs;
         }
-        // every image pixel: bit s of cw4f_reached <=> inside sub-tile s's window; the block's window = the union of the in-image sub-tiles' windows
+        // every image pixel: bit s of Cw4F::reached <=> inside sub-tile s's window; the block's window = the union of the in-image sub-tiles' windows
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) {
-                const unsigned m = cw4f_reached(x, y, bx0, by0, d);
+                const unsigned m = Cw4F::reached(x, y, bx0, by0, d);
                 bool any_in = false;
-                for (int s = 0; s < CW4F_NS; ++s) {
+                for (int s = 0; s < Cw4F::NS; ++s) {
                     const int x0 = bx0 + (s & 1) * 16, y0 = by0 + (s >> 1) * 8;
-                    const CwWindow w = cw_block_window(x0, y0, CW4F_SX, CW4F_SY, d, H, W);
+                    const CwWindow w = cw_block_window(x0, y0, Cw4F::SX, Cw4F::SY, d, H, W);
                     const bool want = x >= w.x0 && x < w.x1 && y >= w.y0 && y < w.y1;
                     const bool def = x >= x0 - d && x < x0 + 16 + d && y >= y0 - d && y < y0 + 8 + d;
                     if (want != def || want != (((m >> s) & 1u) != 0)) FAIL("reached H=%d W=%d d=%d t=%d s=%d (%d, %d)", H, W, d, t, s, x, y);
-                    any_in |= want && cw4f_in_image(x0, y0, H, W);
+                    any_in |= want && Cw4F::in_image(x0, y0, H, W);
                 }
                 const bool inb = x >= bw.x0 && x < bw.x1 && y >= bw.y0 && y < bw.y1;
                 if (inb != any_in) FAIL("union H=%d W=%d d=%d t=%d (%d, %d)", H, W, d, t, x, y);
             }
     }
-    if (inside != cw4f_in_image_total(B, H, W)) FAIL("in-image total H=%d W=%d: %d != %d", H, W, inside, cw4f_in_image_total(B, H, W));
+    if (inside != Cw4F::in_image_total(B, H, W)) FAIL("in-image total H=%d W=%d: %d != %d", H, W, inside, Cw4F::in_image_total(B, H, W));
 }
 
-// random foreground masks: marks as the classifier forms them (one pass over the block's window, cw4f_reached) against the definition; block = OR
+// random foreground masks: marks as the classifier forms them (one pass over the block's window, Cw4F::reached) against the definition; block = OR
 static void mask_case(int H, int W, int d, int permille) {
     const CwGrid g = cw_grid(1, H, W, 64, 32, 16, 64);
     std::vector<char> fg((size_t)H * W);
@@ -81,15 +81,15 @@ static void mask_case(int H, int W, int d, int permille) {
         bool blk = false;
         for (int y = bw.y0; y < bw.y1; ++y)
             for (int x = bw.x0; x < bw.x1; ++x)
-                if (fg[(size_t)y * W + x]) blk = true, all |= cw4f_reached(x, y, bx0, by0, d);
+                if (fg[(size_t)y * W + x]) blk = true, all |= Cw4F::reached(x, y, bx0, by0, d);
         bool orr = false;
-        for (int s = 0; s < CW4F_NS; ++s) {
+        for (int s = 0; s < Cw4F::NS; ++s) {
             const int x0 = bx0 + (s & 1) * 16, y0 = by0 + (s >> 1) * 8;
-            const CwWindow w = cw_block_window(x0, y0, CW4F_SX, CW4F_SY, d, H, W);
+            const CwWindow w = cw_block_window(x0, y0, Cw4F::SX, Cw4F::SY, d, H, W);
             bool want = false;
             for (int y = w.y0; y < w.y1; ++y)
                 for (int x = w.x0; x < w.x1; ++x) want |= fg[(size_t)y * W + x] != 0;
-            if (!cw4f_in_image(x0, y0, H, W)) continue;
+            if (!Cw4F::in_image(x0, y0, H, W)) continue;
             if (want != (((all >> s) & 1u) != 0)) FAIL("mark H=%d W=%d d=%d t=%d s=%d", H, W, d, t, s);
             orr |= want;
         }
@@ -100,7 +100,7 @@ static void mask_case(int H, int W, int d, int permille) {
 
 // nh heavy and nl light sub-tiles (ids: heavy 3 i + 1, light 3 i + 2), ncb column blocks, nwg workgroups
 static void walk_case(int nh, int nl, int ncb, int nwg) {
-    const int ngrp = cw4f_groups(nh), nhe = ngrp * ncb, nle = nl * ncb;
+    const int ngrp = Cw4F::groups(nh), nhe = ngrp * ncb, nle = nl * ncb;
     std::vector<int> hseen((size_t)nh * ncb, 0), lseen((size_t)nl * ncb, 0);
     for (int wg = 0; wg < nwg; ++wg) {
         int id = wg;
@@ -109,14 +109,14 @@ static void walk_case(int nh, int nl, int ncb, int nwg) {
             cw_list_entry(id, ncb, grp, cb);
             if (grp < 0 || grp >= ngrp || cb < 0 || cb >= ncb) { FAIL("entry"); continue; }
             int empty = 0;
-            for (int k = 0; k < CW4F_NS; ++k) {
-                const int ix = cw4f_slot_index(grp, k, nh);
+            for (int k = 0; k < Cw4F::NS; ++k) {
+                const int ix = Cw4F::slot_index(grp, k, nh);
                 if (ix < 0) { ++empty; continue; }
-                if (ix != grp * CW4F_NS + k || ix >= nh || empty) { FAIL("slot index nh=%d grp=%d k=%d", nh, grp, k); continue; }      // (empty slots: trailing only)
+                if (ix != grp * Cw4F::NS + k || ix >= nh || empty) { FAIL("slot index nh=%d grp=%d k=%d", nh, grp, k); continue; }      // (empty slots: trailing only)
                 ++hseen[(size_t)ix * ncb + cb];
             }
             if (empty && grp != ngrp - 1) FAIL("empty slot in group %d of %d (nh=%d)", grp, ngrp, nh);
-            if (empty != (grp == ngrp - 1 ? ngrp * CW4F_NS - nh : 0)) FAIL("empty count nh=%d grp=%d", nh, grp);
+            if (empty != (grp == ngrp - 1 ? ngrp * Cw4F::NS - nh : 0)) FAIL("empty count nh=%d grp=%d", nh, grp);
             ++walked;
         }
         if (cw_list_first_light(wg, nwg, nhe) != id) FAIL("first light");
@@ -140,10 +140,10 @@ static void patch_case(int B, int H, int W) {
         cw_corner(g, t - b * g.bx * g.by, 32, 16, bx0, by0);
         for (int pty = 0; pty < 4; ++pty)
             for (int ptx = 0; ptx < 8; ++ptx) {
-                const int s = cw4f_slot_of_patch(pty, ptx);
+                const int s = Cw4F::slot_of_patch(pty, ptx);
                 int ly, lx, ub, x0, y0;
-                cw4f_patch_in_slot(pty, ptx, ly, lx);
-                cw4f_corner(g, CW4F_NS * t + s, ub, x0, y0);
+                Cw4F::patch_in_slot(pty, ptx, ly, lx);
+                Cw4F::corner(g, Cw4F::NS * t + s, ub, x0, y0);
                 if (s != (pty >> 1) * 2 + (ptx >> 2) || ub != b || x0 + 4 * lx != bx0 + 4 * ptx || y0 + 4 * ly != by0 + 4 * pty) FAIL("patch t=%d (%d, %d)", t, pty, ptx);
                 // the epilogue's reader: pass ph of the wave pair wid / 4 reads patches of ONE slot
                 ++elems;
@@ -152,43 +152,43 @@ static void patch_case(int B, int H, int W) {
 }
 
 static void halo_case(int H, int W, int C, int x0, int y0) {
-    std::vector<int> seen((size_t)CW4F_NS * CW4F_NEL, 0);
+    std::vector<int> seen((size_t)Cw4F::NS * Cw4F::NEL, 0);
     for (int i = 0; i < 3 * 512; ++i) {
         int s, j, s0, j0;
-        cw4f_halo_elem(i, s, j);
-        cw4f_halo_elem(i & ~63, s0, j0);
-        if (s != s0 || s < 0 || s >= CW4F_NS || j < 0) { FAIL("halo elem %d", i); continue; }       // a wave round: one slot
-        if (j >= CW4F_NEL) {
-            if (cw4f_halo_voff(true, j, x0, y0, H, W, C) != CW_OOB) FAIL("halo: no element but an offset");
+        cw4_halo_elem(Cw4F{}, i, s, j);
+        cw4_halo_elem(Cw4F{}, i & ~63, s0, j0);
+        if (s != s0 || s < 0 || s >= Cw4F::NS || j < 0) { FAIL("halo elem %d", i); continue; }       // a wave round: one slot
+        if (j >= Cw4F::NEL) {
+            if (Cw4F::halo_voff(true, j, x0, y0, H, W, C) != CW_OOB) FAIL("halo: no element but an offset");
             continue;
         }
-        ++seen[(size_t)s * CW4F_NEL + j];
+        ++seen[(size_t)s * Cw4F::NEL + j];
         int hy, hx, hq;
-        cw4f_halo_place(j, hy, hx, hq);
-        if (hy < 0 || hy >= CW4F_HH || hx < 0 || hx >= CW4F_HW || hq < 0 || hq > 1 || (hy * CW4F_HW + hx) * 2 + hq != j) FAIL("halo place %d", j);
+        Cw4F::halo_place(j, hy, hx, hq);
+        if (hy < 0 || hy >= Cw4F::HH || hx < 0 || hx >= Cw4F::HW || hq < 0 || hq > 1 || (hy * Cw4F::HW + hx) * 2 + hq != j) FAIL("halo place %d", j);
         const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
         const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
         const unsigned want = in ? (unsigned)(((long long)gy * W + gx) * C + 4 * hq) * 4u : CW_OOB;
-        if (cw4f_halo_voff(true, j, x0, y0, H, W, C) != want) FAIL("halo voff (%d, %d) j=%d", x0, y0, j);
-        if (cw4f_halo_voff(false, j, x0, y0, H, W, C) != CW_OOB) FAIL("halo voff of an empty slot");
+        if (Cw4F::halo_voff(true, j, x0, y0, H, W, C) != want) FAIL("halo voff (%d, %d) j=%d", x0, y0, j);
+        if (Cw4F::halo_voff(false, j, x0, y0, H, W, C) != CW_OOB) FAIL("halo voff of an empty slot");
         ++elems;
     }
     for (int v : seen) if (v != 1) FAIL("halo element staged %d times", v);
 }
 
 static void light_case(int nq) {
-    const int npass = CW4F_SX * CW4F_SY * nq / 512;
-    std::vector<int> seen((size_t)CW4F_SX * CW4F_SY * nq, 0);
+    const int npass = Cw4F::SX * Cw4F::SY * nq / 512;
+    std::vector<int> seen((size_t)Cw4F::SX * Cw4F::SY * nq, 0);
     for (int tid = 0; tid < 512; ++tid) {
         int q0 = -1;
         for (int it = 0; it < npass; ++it) {
             int px, py, q4;
             cw4_light_elem(tid, it, 512, nq, px, py, q4);
-            cw4f_light_pixel(px, py);
-            if (px < 0 || px >= CW4F_SX || py < 0 || py >= CW4F_SY || q4 < 0 || q4 >= nq) { FAIL("light elem"); continue; }
+            Cw4F::light_pixel(px, py);
+            if (px < 0 || px >= Cw4F::SX || py < 0 || py >= Cw4F::SY || q4 < 0 || q4 >= nq) { FAIL("light elem"); continue; }
             if (it == 0) q0 = q4;
             if (q4 != q0) FAIL("light quad");
-            ++seen[(size_t)(py * CW4F_SX + px) * nq + q4];
+            ++seen[(size_t)(py * Cw4F::SX + px) * nq + q4];
             ++elems;
         }
     }
@@ -196,7 +196,7 @@ static void light_case(int nq) {
 }
 
 int main() {
-    if (CW4F_NS != 4 || CW4F_SX * CW4F_NSX != 32 || CW4F_SY * (CW4F_NS / CW4F_NSX) != 16 || CW4F_NS * CW4F_ROUNDS * 64 != 3 * 512 || CW4F_NEL != 360) FAIL("constants");
+    if (Cw4F::NS != 4 || Cw4F::SX * Cw4F::NSX != 32 || Cw4F::SY * (Cw4F::NS / Cw4F::NSX) != 16 || Cw4F::NS * Cw4F::ROUNDS * 64 != 3 * 512 || Cw4F::NEL != 360) FAIL("constants");
 @MAIN@
     printf("subs %llu masks %llu walked %llu elems %llu bad %llu\n", subs, masks, walked, elems, bad);
     return bad != 0;
@@ -246,12 +246,17 @@ def test_subtiles_groups_slots_and_halo():
 
 
 def test_kernels_use_the_shared_functions():
-    """The sub-tile kernel and the classifier go through the functions audited above and share ONE pair of sub-tile constants."""
+    """The sub-tile kernel and the classifier go through the functions audited above - by the geometry parameter G, which the 16 x 8 entry points
+    instantiate with Cw4F - and there is ONE definition of the sub-tile geometry."""
     rd = lambda n: open(os.path.join(CSRC, n)).read()      # noqa: E731
     k = rd("conv_winograd4.hip")
-    for call in ("cw4f_slot_index(slot, k, nht)", "cw4f_halo_elem(tids + NTH * k, s, j)", "cw4f_halo_voff(u >= 0, j, x0, y0, H, W, a.C0)", "cw4f_slot_of_patch(pty, ptx)",
-                 "cw4f_patch_in_slot(pty, ptx, pby, pbx)", "cw4f_light_pixel(px, py)", "cw4f_in_image_total(a.B, H, W)", "cw4f_groups(nht)"):
+    for call in ("G::slot_index(slot, k, nht)", "cw4_halo_elem(G{}, tids + NTH * k, s, j)", "G::halo_voff(u >= 0, j, x0, y0, H, W, a.C0)", "G::slot_of_patch(pty, ptx)",
+                 "G::patch_in_slot(pty, ptx, pby, pbx)", "G::light_pixel(px, py)", "G::in_image_total(a.B, H, W)", "G::groups(nht)",
+                 "lwg_wino4_lists_go<Cw4F>(pa, pl, stream_)"):
         assert call in k, call
     c = rd("spade_skip.hip")
-    assert "cw4f_reached(x, y, x0, y0, d)" in c and "cw4f_in_image(" in c
-    assert "#define CW4F_SX" not in k and "#define CW4F_SX" not in c and rd("lwg_conv_wino.h").count("#define CW4F_SX") == 1
+    assert "GS::reached(x, y, x0, y0, d)" in c and "G::in_image(" in c and "sk_lists<Cw4F>(" in c
+    for own in ("struct Cw4Sub", "Cw4Sub<", "#define SX", "int SX ="):
+        assert own not in k and own not in c, own
+    h = rd("lwg_conv_wino.h")
+    assert h.count("struct Cw4Sub") == 1 and h.count("using Cw4F = Cw4Sub<16, 8>;") == 1 and h.count("Cw4Sub<") == 2

@@ -2,7 +2,7 @@
 """A/B of the list-driven SPADE convolutions (ops.SPADE_SKIP) on the benchmark's clip, one process.
 
   1. the heavy share - 32 x 16 blocks, 16 x 8 and 8 x 8 sub-tiles whose window holds a pixel with an in-image tap - per feature size and window reach d, from
-     the classifier's counts;
+     the classifier's counts, and the time of one classifier call (its two launches, all three granularities; median of --reps);
   2. per-launch times (HIP events around the conv entry points, ops.CONV_HOOK) of the eighteen SPADE launches of a frame batch with the switch off,
      with the block lists (ops.SPADE_SKIP_FINE = False), with the 16 x 8 lists (ops.SPADE_SKIP_Q8 = False) and with the 8 x 8 lists on the launches
      of at least --q8-min entries on feature maps of at most --q8-max-hw pixels, alternated --reps times; median per launch and the sum;
@@ -75,13 +75,20 @@ def main():
                 try:
                     with ops.conv_precision("winograd"):
                         lists = ops.spade_skip_lists(flow, d)
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.reps + 1)]      # the classifier's two launches, timed
+                        ev[0].record()
+                        for e in ev[1:]:
+                            ops.spade_skip_lists(flow, d)
+                            e.record()
+                        torch.cuda.synchronize()
+                        tcls = statistics.median(a.elapsed_time(b) for a, b in zip(ev, ev[1:]))
                 finally:
                     ops.SPADE_SKIP_Q8_MIN, ops.SPADE_SKIP_Q8_MAX_HW = prev
                 nh, nl = (int(v) for v in lists[2].cpu())
                 fh, fl = (int(v) for v in lists.fine[2].cpu())
                 qh, ql = (int(v) for v in lists.fine8[2].cpu()) if lists.fine8 is not None else (0, 1)
-                print("  %-6s %4d^2  d=%d  heavy %6d of %6d = %.3f | %7d of %7d = %.3f | %7d of %7d = %.3f" %
-                      (tag, h, d, nh, nh + nl, nh / (nh + nl), fh, fh + fl, fh / (fh + fl), qh, qh + ql, qh / (qh + ql)))
+                print("  %-6s %4d^2  d=%d  heavy %6d of %6d = %.3f | %7d of %7d = %.3f | %7d of %7d = %.3f   classifier %.3f ms" %
+                      (tag, h, d, nh, nh + nl, nh / (nh + nl), fh, fh + fl, fh / (fh + fl), qh, qh + ql, qh / (qh + ql), tcls))
 
     MODES = (("off", False, False, False), ("block", True, False, False), ("sub", True, True, False), ("q8", True, True, True)) + \
         ((("off2", False, False, False),) if args.control else ())
