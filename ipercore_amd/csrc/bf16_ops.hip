@@ -5,26 +5,9 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
+#include "lwg_lwb_taps.h"
 
-typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float lwg_b2f_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float lwg_b2f_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ void lwg_unpack8(const uintx4 v, float (&f)[8]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = lwg_b2f_lo(v[k]);
-        f[2 * k + 1] = lwg_b2f_hi(v[k]);
-    }
-}
-__device__ __forceinline__ unsigned lwg_pack2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (__bf16)lo;
-    v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // ---------------------------------------------------------------------------------------------- Liquid Warping Block (attention)
 // csrc/lwb_attn.hip lwg_lwb_attn_kernel on bf16 q / Ks / Vs / out: one pixel per LPP = C/8 lanes, 16-byte gathers of 8 channels,
@@ -49,7 +32,7 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
     const long gp = ((long)b * h + y) * w + x;
 
     float q8[8];
-    lwg_unpack8(*reinterpret_cast<const uintx4*>(q + gp * C + 8 * cl), q8);
+    lwg_bf16_widen8(*reinterpret_cast<const uintx4*>(q + gp * C + 8 * cl), q8);
     // the biases leave the loop (registers = resident waves = pixel chains in flight, which is what this kernel runs on):
     // sum_k (K_k + bk_k) q_k = sum_k K_k q_k + qbk, and sum_s a_s (V_s + bv) = sum_s a_s V_s + bv because the a_s sum to one
     float qbk = 0.f;
@@ -72,7 +55,8 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
 #pragma unroll
     for (int k = 0; k < 8; ++k) o[k] = 0.f;
 
-    // one source: the flow of this pixel -> sampling position (grid_sample, align_corners=False) -> corner tap + bilinear weights
+    // one source: the flow of this pixel -> sampling position (grid_sample, align_corners=False) -> corner tap + bilinear weights (lwb_taps_of's
+    // expressions as this kernel's own copy, as in lwb_attn.hip: the recorded bits of the in-kernel resize depend on it)
     auto position = [&](int s, int& tx0, int& ty0, float& wx0, float& wx1, float& wy0, float& wy1) {
         const float2* Tp = reinterpret_cast<const float2*>(T) + ((size_t)b * ns + s) * S * S;
         float gx, gy;
@@ -121,6 +105,7 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
             const unsigned sbase = (sidx * (unsigned)hw * (unsigned)C + 8u * (unsigned)cl) * 2u;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
+                // lwb_tap's text (lwg_lwb_taps.h), inline: through the call the C = 256 instantiation goes from 16 to 28 bytes of scratch
                 const int ty = ty0 + (t >> 1), tx = tx0 + (t & 1);
                 const bool ok = ty >= 0 && ty < h && tx >= 0 && tx < w;
                 const unsigned voff = ok ? sbase + (unsigned)(ty * w + tx) * (unsigned)C * 2u : 0xC0000000u;
@@ -136,8 +121,8 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
             for (int t = 0; t < 4; ++t) {
                 const float wt = ((t >> 1) ? tp.wy1 : tp.wy0) * ((t & 1) ? tp.wx1 : tp.wx0);
                 float k8[8], v8[8];
-                lwg_unpack8(tp.kr[t], k8);
-                lwg_unpack8(tp.vr[t], v8);
+                lwg_bf16_widen8(tp.kr[t], k8);
+                lwg_bf16_widen8(tp.vr[t], v8);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) { ka[k] += k8[k] * wt; va[k] += v8[k] * wt; }
             }
@@ -164,13 +149,13 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
             for (int k = 0; k < 8; ++k) ka[k] = va[k] = 0.f;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int ty = ty0 + (t >> 1), tx = tx0 + (t & 1);
+                int ty, tx;
                 const float wt = ((t >> 1) ? wy1 : wy0) * ((t & 1) ? wx1 : wx0);
-                if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
+                if (lwb_tap(t, tx0, ty0, w, h, tx, ty)) {
                     const size_t off = ((size_t)ty * w + tx) * C;
                     float k8[8], v8[8];
-                    lwg_unpack8(*reinterpret_cast<const uintx4*>(Kb + off), k8);
-                    lwg_unpack8(*reinterpret_cast<const uintx4*>(Vb + off), v8);
+                    lwg_bf16_widen8(*reinterpret_cast<const uintx4*>(Kb + off), k8);
+                    lwg_bf16_widen8(*reinterpret_cast<const uintx4*>(Vb + off), v8);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) { ka[k] += k8[k] * wt; va[k] += v8[k] * wt; }
                 }
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_bf16_kernel(const __bf1
         const float invl = 1.f / lrun;
         uintx4 r;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = lwg_pack2(o[2 * k] * invl + bv[8 * cl + 2 * k], o[2 * k + 1] * invl + bv[8 * cl + 2 * k + 1]);
+        for (int k = 0; k < 4; ++k) r[k] = lwg_bf16_pack2(o[2 * k] * invl + bv[8 * cl + 2 * k], o[2 * k + 1] * invl + bv[8 * cl + 2 * k + 1]);
         *reinterpret_cast<uintx4*>(out + gp * C + 8 * cl) = r;
     }
 }
@@ -198,23 +183,16 @@ extern "C" int lwg_lwb_attention_bf16(const void* q, const void* Ks, const void*
     const __bf16* Kb = reinterpret_cast<const __bf16*>(Ks);
     const __bf16* Vb = reinterpret_cast<const __bf16*>(Vs);
     __bf16* ob = reinterpret_cast<__bf16*>(out);
-#define LWG_ATTN16_GO(LPP, BUF, PAIR, OCC)                                                                                              \
-    hipLaunchKernelGGL((lwg_lwb_attn_bf16_kernel<LPP, BUF, PAIR, OCC>), dim3((unsigned)((total + 4 * (64 / LPP) - 1) / (4 * (64 / LPP)))), \
-                       dim3(256), 0, stream, qb, Kb, Vb, bk, bv, T, ob, B, ns, h, w, S, src_batched)
-#define LWG_ATTN16_LAUNCH(LPP)                                                          \
-    {                                                                                   \
-        if (!buf_ok) LWG_ATTN16_GO(LPP, false, false, 4);                               \
-        else LWG_ATTN16_GO(LPP, true, (LWG_ATTN16_PAIR != 0), (LWG_ATTN16_PAIR ? 3 : LWG_ATTN16_OCC)); \
-    }
-    switch (C) {
-        case 64: LWG_ATTN16_LAUNCH(8) break;
-        case 128: LWG_ATTN16_LAUNCH(16) break;
-        case 256: LWG_ATTN16_LAUNCH(32) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_ATTN16_LAUNCH
-#undef LWG_ATTN16_GO
-    return (int)hipGetLastError();
+    const bool known = lwg_lpp_dispatch<8, 32>(C, 8, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if (!buf_ok)
+            hipLaunchKernelGGL((lwg_lwb_attn_bf16_kernel<LPP, false, false, 4>), lwg_lpp_grid<LPP>(total), dim3(256), 0, stream, qb, Kb, Vb, bk, bv, T, ob, B, ns,
+                               h, w, S, src_batched);
+        else
+            hipLaunchKernelGGL((lwg_lwb_attn_bf16_kernel<LPP, true, (LWG_ATTN16_PAIR != 0), (LWG_ATTN16_PAIR ? 3 : LWG_ATTN16_OCC)>), lwg_lpp_grid<LPP>(total),
+                               dim3(256), 0, stream, qb, Kb, Vb, bk, bv, T, ob, B, ns, h, w, S, src_batched);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------- output head + compositing

@@ -11,6 +11,7 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
+#include "lwg_lwb_taps.h"
 
 // BUF: the K / V taps through raw buffer loads - an out-of-image tap gets an out-of-range offset and the hardware returns zeros, so the
 // eight gathers of a source are unconditional and in flight together (with per-tap branches each load waited for its own exec mask
@@ -66,7 +67,9 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_kernel(const float* __r
             gx = ly0 * (lx0 * t00.x + lx1 * t01.x) + ly1 * (lx0 * t10.x + lx1 * t11.x);
             gy = ly0 * (lx0 * t00.y + lx1 * t01.y) + ly1 * (lx0 * t10.y + lx1 * t11.y);
         }
-        // grid_sample, align_corners=False: pixel = ((g + 1) * size - 1) / 2
+        // grid_sample, align_corners=False: pixel = ((g + 1) * size - 1) / 2.  lwb_taps_of's expressions (lwg_lwb_taps.h) as this kernel's own copy: with
+        // the weights in its wt[4] form the compiler contracts the four-texel blend above differently and the in-kernel resize leaves the recorded
+        // bits; tests/test_lwb_taps_cpu.py holds every copy to the header's text
         const float ix = ((gx + 1.f) * (float)w - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)h - 1.f) * 0.5f;
         const float fx0 = floorf(ix), fy0 = floorf(iy);
         const float wx1 = ix - fx0, wy1 = iy - fy0, wx0 = (fx0 + 1.f) - ix, wy0 = (fy0 + 1.f) - iy;
@@ -85,6 +88,7 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_kernel(const float* __r
             floatx4 k4[4], v4[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
+                // lwb_tap's text, inline: through the call this loop is allocated differently (bf16_ops.hip: more scratch at C = 256)
                 const int ty = ty0 + (t >> 1), tx = tx0 + (t & 1);
                 const bool ok = ty >= 0 && ty < h && tx >= 0 && tx < w;
                 const unsigned voff = ok ? sbase + (unsigned)(ty * w + tx) * (unsigned)PS * 4u : 0xC0000000u;
@@ -100,9 +104,9 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_kernel(const float* __r
         } else {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int ty = ty0 + (t >> 1), tx = tx0 + (t & 1);
+                int ty, tx;
                 const float wt = ((t >> 1) ? wy1 : wy0) * ((t & 1) ? wx1 : wx0);
-                if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
+                if (lwb_tap(t, tx0, ty0, w, h, tx, ty)) {
                     const size_t off = ((size_t)ty * w + tx) * PS;
                     const floatx4 k4 = *reinterpret_cast<const floatx4*>(Kb + off);
                     const floatx4 v4 = *reinterpret_cast<const floatx4*>(Vb + off);
@@ -134,8 +138,6 @@ __global__ __launch_bounds__(256, OCC) void lwg_lwb_attn_kernel(const float* __r
     }
 }
 
-// src_batched = 0: Ks/Vs (ns,h,w,C) shared by all B frames; 1: (B*ns,h,w,C), frame b uses rows b*ns+s.
-// q (B,h,w,C) = fq(tsf_x) incl. bias; Ks/Vs (ns,h,w,C) = Wk x_src / Wv x_src WITHOUT bias; bk/bv (C);
 // The flow resize of LWB.resize_trans (attlwb_spade_resunet.py:175-181: F.interpolate(T, size=(h, w), mode="bilinear", align_corners=True))
 // as its own pass: n = B * ns flow fields (S,S,2) -> (h,w,2).  The attention / fusion kernels do this resize per pixel when handed the
 // full-resolution flows - four 8-byte loads per pixel and source at a stride of S / h pixels, each a trip to HBM at the head of the
@@ -174,33 +176,32 @@ extern "C" int lwg_flow_resize_f32(const float* T, int n, int S, int h, int w, f
     return (int)hipGetLastError();
 }
 
+// The launch of both forward entry points: Ks / Vs dense (KVS false) or the two halves of one K | V tensor with rows of kvs floats.
+template <bool KVS>
+static int lwg_attn_launch(const float* q, const float* Ks, const float* Vs, const float* bk, const float* bv, const float* T, float* out, int B,
+                           int ns, int h, int w, int C, int S, int src_batched, int kvs, hipStream_t stream) {
+    const long total = lwg_tile_frame_positions(B, h, w);
+    // the buffer form's 32-bit offsets: the K (and V) tensor - the one K | V tensor of 2C-float rows in the KVS form - below 3 GB
+    const bool buf_ok = (unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * (KVS ? 8ull : 4ull) < 0xC0000000ull;
+    const bool known = lwg_lpp_dispatch<8, 64>(C, 4, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if (!buf_ok)
+            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, false, 5, KVS>), lwg_lpp_grid<LPP>(total), dim3(256), 0, stream, q, Ks, Vs, bk, bv, T, out, B, ns, h, w, S, src_batched, kvs);
+        else
+            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, true, LWG_ATTN_OCC, KVS>), lwg_lpp_grid<LPP>(total), dim3(256), 0, stream, q, Ks, Vs, bk, bv, T, out, B, ns, h, w, S, src_batched, kvs);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
+}
+
+// src_batched = 0: Ks/Vs (ns,h,w,C) shared by all B frames; 1: (B*ns,h,w,C), frame b uses rows b*ns+s.
+// q (B,h,w,C) = fq(tsf_x) incl. bias; Ks/Vs (ns,h,w,C) = Wk x_src / Wv x_src WITHOUT bias; bk/bv (C);
 // T (B,ns,S,S,2) flows in grid_sample coordinates (-2 = background); out (B,h,w,C).
 extern "C" int lwg_lwb_attention_f32(const float* q, const float* Ks, const float* Vs, const float* bk, const float* bv,
                                      const float* T, float* out, int B, int ns, int h, int w, int C, int S,
                                      int src_batched, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!q || !Ks || !Vs || !bk || !bv || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0)
         return (int)hipErrorInvalidValue;
-    const long total = lwg_tile_frame_positions(B, h, w);
-    const bool buf_ok = (unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * 4ull < 0xC0000000ull;
-#define LWG_ATTN_LAUNCH(LPP)                                                                                      \
-    {                                                                                                             \
-        const long per_block = 4 * (64 / LPP);                                                                    \
-        const dim3 grid((unsigned)((total + per_block - 1) / per_block));                                         \
-        if (!buf_ok)                                                                                              \
-            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, false, 5>), grid, dim3(256), 0, stream, q, Ks, Vs, bk, bv, T, out, B, ns, h, w, S, src_batched, 0); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, true, LWG_ATTN_OCC>), grid, dim3(256), 0, stream, q, Ks, Vs, bk, bv, T, out, B, ns, h, w, S, src_batched, 0);  \
-    }
-    switch (C) {
-        case 32: LWG_ATTN_LAUNCH(8) break;
-        case 64: LWG_ATTN_LAUNCH(16) break;
-        case 128: LWG_ATTN_LAUNCH(32) break;
-        case 256: LWG_ATTN_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_ATTN_LAUNCH
-    return (int)hipGetLastError();
+    return lwg_attn_launch<false>(q, Ks, Vs, bk, bv, T, out, B, ns, h, w, C, S, src_batched, 0, reinterpret_cast<hipStream_t>(stream_));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -208,28 +209,8 @@ extern "C" int lwg_lwb_attention_f32(const float* q, const float* Ks, const floa
 // projection, networks/training.py attlwb): no slicing copies in front of the kernel.
 extern "C" int lwg_lwb_attention_kv_f32(const float* q, const float* kv, const float* bk, const float* bv, const float* T, float* out,
                                         int B, int ns, int h, int w, int C, int S, int src_batched, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!q || !kv || !bk || !bv || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0) return (int)hipErrorInvalidValue;
-    const long total = lwg_tile_frame_positions(B, h, w);
-    const bool buf_ok = (unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * 8ull < 0xC0000000ull;
-#define LWG_ATTN_KV_LAUNCH(LPP)                                                                                   \
-    {                                                                                                             \
-        const long per_block = 4 * (64 / LPP);                                                                    \
-        const dim3 grid((unsigned)((total + per_block - 1) / per_block));                                         \
-        if (!buf_ok)                                                                                              \
-            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, false, 5, true>), grid, dim3(256), 0, stream, q, kv, kv + C, bk, bv, T, out, B, ns, h, w, S, src_batched, 2 * C); \
-        else                                                                                                      \
-            hipLaunchKernelGGL((lwg_lwb_attn_kernel<LPP, true, LWG_ATTN_OCC, true>), grid, dim3(256), 0, stream, q, kv, kv + C, bk, bv, T, out, B, ns, h, w, S, src_batched, 2 * C);  \
-    }
-    switch (C) {
-        case 32: LWG_ATTN_KV_LAUNCH(8) break;
-        case 64: LWG_ATTN_KV_LAUNCH(16) break;
-        case 128: LWG_ATTN_KV_LAUNCH(32) break;
-        case 256: LWG_ATTN_KV_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_ATTN_KV_LAUNCH
-    return (int)hipGetLastError();
+    return lwg_attn_launch<true>(q, kv, kv + C, bk, bv, T, out, B, ns, h, w, C, S, src_batched, 2 * C, reinterpret_cast<hipStream_t>(stream_));
 }
 
 // Backward of the attention-form Liquid Warping Block (personalization step).  Per pixel, with K_s = warp_s(Ks) + bk,
@@ -258,8 +239,8 @@ __global__ __launch_bounds__(256) void lwg_lwb_attn_bwd_kernel(const float* __re
     const bool live = gp < total;
     if (!live) gp = total - 1;
     const int hw = h * w;
-    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
-    const int y = rem / w, x = rem - y * w;
+    int b, y, x;
+    lwb_pixel_of(gp, h, w, b, y, x);
 
     const floatx4 q4 = *reinterpret_cast<const floatx4*>(q + gp * C + 4 * cl);
     const floatx4 g4 = *reinterpret_cast<const floatx4*>(dout + gp * C + 4 * cl);
@@ -304,9 +285,9 @@ __global__ __launch_bounds__(256) void lwg_lwb_attn_bwd_kernel(const float* __re
         floatx4 ka = {0.f, 0.f, 0.f, 0.f}, va = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int ty = ty0s[s] + (t >> 1), tx = tx0s[s] + (t & 1);
+            int ty, tx;
             const float wt = ((t >> 1) ? wy1s[s] : wy0s[s]) * ((t & 1) ? wx1s[s] : wx0s[s]);
-            if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
+            if (lwb_tap(t, tx0s[s], ty0s[s], w, h, tx, ty)) {
                 const size_t off = ((size_t)ty * w + tx) * PS;
                 const floatx4 k4 = *reinterpret_cast<const floatx4*>(Kb + off);
                 const floatx4 v4 = *reinterpret_cast<const floatx4*>(Vb + off);
@@ -346,9 +327,9 @@ __global__ __launch_bounds__(256) void lwg_lwb_attn_bwd_kernel(const float* __re
         float* dVb = dVs + sidx * hw * PS + 4 * cl;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int ty = ty0s[s] + (t >> 1), tx = tx0s[s] + (t & 1);
+            int ty, tx;
             const float wt = ((t >> 1) ? wy1s[s] : wy0s[s]) * ((t & 1) ? wx1s[s] : wx0s[s]);
-            if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
+            if (lwb_tap(t, tx0s[s], ty0s[s], w, h, tx, ty)) {
                 const size_t off = ((size_t)ty * w + tx) * PS;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -361,54 +342,34 @@ __global__ __launch_bounds__(256) void lwg_lwb_attn_bwd_kernel(const float* __re
     if (live) *reinterpret_cast<floatx4*>(dq + gp * C + 4 * cl) = dq4;
 }
 
+template <bool KVS>
+static int lwg_attn_bwd_launch(const float* q, const float* Ks, const float* Vs, const float* bk, const float* bv, const float* T, const float* dout,
+                               float* dq, float* dKs, float* dVs, int B, int ns, int h, int w, int C, int S, int src_batched, int kvs, hipStream_t stream) {
+    const bool known = lwg_lpp_dispatch<8, 64>(C, 4, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        hipLaunchKernelGGL((lwg_lwb_attn_bwd_kernel<LPP, KVS>), lwg_lpp_grid<LPP>((long)B * h * w), dim3(256), 0, stream, q, Ks, Vs, bk, bv, T, dout, dq,
+                           dKs, dVs, B, ns, h, w, S, src_batched, kvs);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
+}
+
 // dq (B,h,w,C) is written; dKs / dVs (shaped like Ks / Vs) are ACCUMULATED into (zero them first); ns <= 8.
 extern "C" int lwg_lwb_attention_bwd_f32(const float* q, const float* Ks, const float* Vs, const float* bk, const float* bv,
                                          const float* T, const float* dout, float* dq, float* dKs, float* dVs, int B, int ns, int h,
                                          int w, int C, int S, int src_batched, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!q || !Ks || !Vs || !bk || !bv || !T || !dout || !dq || !dKs || !dVs || B <= 0 || ns <= 0 || ns > 8 || h <= 0 || w <= 0 || S <= 0)
         return (int)hipErrorInvalidValue;
-    const long total = (long)B * h * w;
-#define LWG_ATTN_BWD_LAUNCH(LPP)                                                                                      \
-    {                                                                                                                 \
-        const long per_block = 4 * (64 / LPP);                                                                        \
-        hipLaunchKernelGGL(lwg_lwb_attn_bwd_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, \
-                           stream, q, Ks, Vs, bk, bv, T, dout, dq, dKs, dVs, B, ns, h, w, S, src_batched, 0);                    \
-    }
-    switch (C) {
-        case 32: LWG_ATTN_BWD_LAUNCH(8) break;
-        case 64: LWG_ATTN_BWD_LAUNCH(16) break;
-        case 128: LWG_ATTN_BWD_LAUNCH(32) break;
-        case 256: LWG_ATTN_BWD_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_ATTN_BWD_LAUNCH
-    return (int)hipGetLastError();
+    return lwg_attn_bwd_launch<false>(q, Ks, Vs, bk, bv, T, dout, dq, dKs, dVs, B, ns, h, w, C, S, src_batched, 0, reinterpret_cast<hipStream_t>(stream_));
 }
 
 // Backward with K | V as one tensor kv (nsrc,h,w,2C): d(kv) is ACCUMULATED into dkv of the same shape (zero it first).
 extern "C" int lwg_lwb_attention_kv_bwd_f32(const float* q, const float* kv, const float* bk, const float* bv, const float* T,
                                             const float* dout, float* dq, float* dkv, int B, int ns, int h, int w, int C, int S,
                                             int src_batched, lwg_stream_t stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!q || !kv || !bk || !bv || !T || !dout || !dq || !dkv || B <= 0 || ns <= 0 || ns > 8 || h <= 0 || w <= 0 || S <= 0)
         return (int)hipErrorInvalidValue;
-    const long total = (long)B * h * w;
-#define LWG_ATTN_KV_BWD_LAUNCH(LPP)                                                                                   \
-    {                                                                                                                 \
-        const long per_block = 4 * (64 / LPP);                                                                        \
-        hipLaunchKernelGGL((lwg_lwb_attn_bwd_kernel<LPP, true>), dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, \
-                           stream, q, kv, kv + C, bk, bv, T, dout, dq, dkv, dkv + C, B, ns, h, w, S, src_batched, 2 * C);             \
-    }
-    switch (C) {
-        case 32: LWG_ATTN_KV_BWD_LAUNCH(8) break;
-        case 64: LWG_ATTN_KV_BWD_LAUNCH(16) break;
-        case 128: LWG_ATTN_KV_BWD_LAUNCH(32) break;
-        case 256: LWG_ATTN_KV_BWD_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_ATTN_KV_BWD_LAUNCH
-    return (int)hipGetLastError();
+    return lwg_attn_bwd_launch<true>(q, kv, kv + C, bk, bv, T, dout, dq, dkv, dkv + C, B, ns, h, w, C, S, src_batched, 2 * C,
+                                     reinterpret_cast<hipStream_t>(stream_));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -418,32 +379,15 @@ extern "C" int lwg_lwb_attention_kv_bwd_f32(const float* q, const float* kv, con
 // as one gather kernel:   out = (tsf_x + gate * scale_w * sum_s warp_s(src_x)) * scale_o      (gate == nullptr: 1)
 // Same flow resize / grid_sample conventions, lane mapping and 16-byte gathers as lwg_lwb_attn_kernel.
 // The flow resize / grid_sample / tap-clamping expressions of the fusion block, shared by its forward and its backward kernel (one
-// copy: the backward scatters to exactly the taps, with exactly the weights, the forward gathered from).
-struct LwgFuseResize {      // per pixel: flow resize S x S -> h x w, bilinear, align_corners=True (ATen area_pixel_compute_source_index)
-    int y0, x0, y1, x1;
-    float ly0, ly1, lx0, lx1;
-    bool same;
-};
+// copy: the backward scatters to exactly the taps, with exactly the weights, the forward gathered from).  The resize indices and weights are
+// lwb_resize_of's (lwg_lwb_taps.h); the blend and the tap expressions are that header's text, kept here (see lwg_lwb_attn_kernel).
 struct LwgFuseTaps {        // per pixel and source: top-left tap (clamped to [-2, size + 1]) and the bilinear weights of grid_sample
     int tx0, ty0;
     float wx0, wx1, wy0, wy1;
 };
 
-__device__ __forceinline__ LwgFuseResize lwg_fuse_resize(int y, int x, int h, int w, int S) {
-    LwgFuseResize r;
-    const float sc_y = h > 1 ? (float)(S - 1) / (float)(h - 1) : 0.f;
-    const float sc_x = w > 1 ? (float)(S - 1) / (float)(w - 1) : 0.f;
-    const float sy = sc_y * (float)y, sx = sc_x * (float)x;
-    r.y0 = (int)sy; r.x0 = (int)sx;
-    r.y1 = r.y0 + (r.y0 < S - 1 ? 1 : 0); r.x1 = r.x0 + (r.x0 < S - 1 ? 1 : 0);
-    r.ly1 = sy - (float)r.y0; r.lx1 = sx - (float)r.x0;
-    r.ly0 = 1.f - r.ly1; r.lx0 = 1.f - r.lx1;
-    r.same = (h == S) && (w == S);
-    return r;
-}
-
 // Tp: the (S,S,2) flow of this frame and source
-__device__ __forceinline__ LwgFuseTaps lwg_fuse_taps(const float2* __restrict__ Tp, const LwgFuseResize& r, int y, int x, int h, int w, int S) {
+__device__ __forceinline__ LwgFuseTaps lwg_fuse_taps(const float2* __restrict__ Tp, const LwbResize& r, int y, int x, int h, int w, int S) {
     float gx, gy;
     if (r.same) {
         const float2 t = Tp[(size_t)y * S + x];
@@ -466,9 +410,8 @@ __device__ __forceinline__ LwgFuseTaps lwg_fuse_taps(const float2* __restrict__ 
 
 // tap t in 0..3 (row-major 2 x 2): its pixel, its weight, and whether it lies inside the h x w source map (zero padding otherwise)
 __device__ __forceinline__ bool lwg_fuse_tap(const LwgFuseTaps& p, int t, int h, int w, int& ty, int& tx, float& wt) {
-    ty = p.ty0 + (t >> 1); tx = p.tx0 + (t & 1);
     wt = ((t >> 1) ? p.wy1 : p.wy0) * ((t & 1) ? p.wx1 : p.wx0);
-    return ty >= 0 && ty < h && tx >= 0 && tx < w;
+    return lwb_tap(t, p.tx0, p.ty0, w, h, tx, ty);
 }
 
 template <int LPP>
@@ -484,9 +427,9 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_kernel(const float* __restri
     const long gp = ((long)blockIdx.x * 4 + wid) * PPW + lane / LPP;
     if (gp >= total) return;
     const int hw = h * w;
-    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
-    const int y = rem / w, x = rem - y * w;
-    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
+    int b, y, x;
+    lwb_pixel_of(gp, h, w, b, y, x);
+    const LwbResize rz = lwb_resize_of(y, x, h, w, S);
 
     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < ns; ++s) {
@@ -521,22 +464,12 @@ extern "C" int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const fl
                                 int h, int w, int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!tsf_x || !src_x || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0) return (int)hipErrorInvalidValue;
-    const long total = (long)B * h * w;
-#define LWG_FUSE_LAUNCH(LPP)                                                                                          \
-    {                                                                                                                 \
-        const long per_block = 4 * (64 / LPP);                                                                        \
-        hipLaunchKernelGGL(lwg_lwb_fuse_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, stream, \
-                           tsf_x, src_x, gate, T, out, B, ns, h, w, S, src_batched, scale_w, scale_o);                            \
-    }
-    switch (C) {
-        case 32: LWG_FUSE_LAUNCH(8) break;
-        case 64: LWG_FUSE_LAUNCH(16) break;
-        case 128: LWG_FUSE_LAUNCH(32) break;
-        case 256: LWG_FUSE_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_FUSE_LAUNCH
-    return (int)hipGetLastError();
+    const bool known = lwg_lpp_dispatch<8, 64>(C, 4, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        hipLaunchKernelGGL(lwg_lwb_fuse_kernel<LPP>, lwg_lpp_grid<LPP>((long)B * h * w), dim3(256), 0, stream, tsf_x, src_x, gate, T, out, B, ns, h, w, S,
+                           src_batched, scale_w, scale_o);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // The same block on bf16 tsf_x / src_x / gate / out (the "bf16" / "bf16_winograd" engines: bf16 activation storage end to end); the flows stay
@@ -545,23 +478,6 @@ extern "C" int lwg_lwb_fuse_f32(const float* tsf_x, const float* src_x, const fl
 // arithmetic is lwg_lwb_fuse_kernel's, in fp32 and in its order: bf16 widened by shift (exact), four taps into wv, acc += wv source after
 // source, (t + g * (acc * scale_w)) * scale_o, then ONE round-to-nearest-even to bf16 at the store (v_cvt_pk_bf16_f32).  No LDS, no
 // cross-lane traffic: a lane past the last pixel simply leaves.
-typedef unsigned int lwg_fuse_uintx4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned lwg_pack_bf16x2(float lo, float hi) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 v;
-    v[0] = (__bf16)lo;
-    v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void lwg_fuse_widen8(const lwg_fuse_uintx4 v, float (&f)[8]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __builtin_bit_cast(float, v[k] << 16);
-        f[2 * k + 1] = __builtin_bit_cast(float, v[k] & 0xffff0000u);
-    }
-}
-
 template <int LPP>
 __global__ __launch_bounds__(256) void lwg_lwb_fuse_bf16_kernel(const __bf16* __restrict__ tsf, const __bf16* __restrict__ src,
                                                                const __bf16* __restrict__ gate, const float* __restrict__ T,
@@ -575,15 +491,15 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_bf16_kernel(const __bf16* __
     const long gp = ((long)blockIdx.x * 4 + wid) * PPW + lane / LPP;
     if (gp >= total) return;
     const int hw = h * w;
-    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
-    const int y = rem / w, x = rem - y * w;
-    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
+    int b, y, x;
+    lwb_pixel_of(gp, h, w, b, y, x);
+    const LwbResize rz = lwb_resize_of(y, x, h, w, S);
 
     // the pixel's own rows are requested before the flow -> taps -> gather chain, not after it: they ride under it (seven pixels in eight of a
     // rendered frame are background - every tap outside - and would otherwise wait for the flow and then again for tsf_x)
-    const lwg_fuse_uintx4 tq = *reinterpret_cast<const lwg_fuse_uintx4*>(tsf + gp * C + 8 * cl);
-    lwg_fuse_uintx4 gq = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};        // bf16 1.0 pairs
-    if (gate) gq = *reinterpret_cast<const lwg_fuse_uintx4*>(gate + gp * C + 8 * cl);
+    const uintx4 tq = *reinterpret_cast<const uintx4*>(tsf + gp * C + 8 * cl);
+    uintx4 gq = {0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};        // bf16 1.0 pairs
+    if (gate) gq = *reinterpret_cast<const uintx4*>(gate + gp * C + 8 * cl);
 
     float acc[8];
 #pragma unroll
@@ -601,7 +517,7 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_bf16_kernel(const __bf16* __
             float wt;
             if (lwg_fuse_tap(tp, t, h, w, ty, tx, wt)) {
                 float v8[8];
-                lwg_fuse_widen8(*reinterpret_cast<const lwg_fuse_uintx4*>(Sb + ((size_t)ty * w + tx) * C), v8);
+                lwg_bf16_widen8(*reinterpret_cast<const uintx4*>(Sb + ((size_t)ty * w + tx) * C), v8);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) wv[k] += v8[k] * wt;
             }
@@ -610,15 +526,15 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_bf16_kernel(const __bf16* __
         for (int k = 0; k < 8; ++k) acc[k] += wv[k];       // the reference sums the warped sources one after the other
     }
     float t8[8], g8[8];
-    lwg_fuse_widen8(tq, t8);
-    lwg_fuse_widen8(gq, g8);
+    lwg_bf16_widen8(tq, t8);
+    lwg_bf16_widen8(gq, g8);
     float r[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) r[k] = (t8[k] + g8[k] * (acc[k] * scale_w)) * scale_o;
-    lwg_fuse_uintx4 o;
+    uintx4 o;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = lwg_pack_bf16x2(r[2 * k], r[2 * k + 1]);
-    *reinterpret_cast<lwg_fuse_uintx4*>(out + gp * C + 8 * cl) = o;
+    for (int k = 0; k < 4; ++k) o[k] = lwg_bf16_pack2(r[2 * k], r[2 * k + 1]);
+    *reinterpret_cast<uintx4*>(out + gp * C + 8 * cl) = o;
 }
 
 // tsf_x / gate / out (B,h,w,C) bf16; src_x (ns,h,w,C) or (B*ns,h,w,C) bf16; T (B,ns,S,S,2) fp32; gate may be NULL; C in {32,64,128,256}.
@@ -626,23 +542,13 @@ extern "C" int lwg_lwb_fuse_bf16(const void* tsf_x, const void* src_x, const voi
                                  int w, int C, int S, int src_batched, float scale_w, float scale_o, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!tsf_x || !src_x || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0) return (int)hipErrorInvalidValue;
-    const long total = (long)B * h * w;
-#define LWG_FUSE16_LAUNCH(LPP)                                                                                        \
-    {                                                                                                                 \
-        const long per_block = 4 * (64 / LPP);                                                                        \
-        hipLaunchKernelGGL(lwg_lwb_fuse_bf16_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, stream, \
-                           static_cast<const __bf16*>(tsf_x), static_cast<const __bf16*>(src_x), static_cast<const __bf16*>(gate), T,     \
-                           static_cast<__bf16*>(out), B, ns, h, w, S, src_batched, scale_w, scale_o);                                     \
-    }
-    switch (C) {
-        case 32: LWG_FUSE16_LAUNCH(4) break;
-        case 64: LWG_FUSE16_LAUNCH(8) break;
-        case 128: LWG_FUSE16_LAUNCH(16) break;
-        case 256: LWG_FUSE16_LAUNCH(32) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_FUSE16_LAUNCH
-    return (int)hipGetLastError();
+    const bool known = lwg_lpp_dispatch<4, 32>(C, 8, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        hipLaunchKernelGGL(lwg_lwb_fuse_bf16_kernel<LPP>, lwg_lpp_grid<LPP>((long)B * h * w), dim3(256), 0, stream, static_cast<const __bf16*>(tsf_x),
+                           static_cast<const __bf16*>(src_x), static_cast<const __bf16*>(gate), T, static_cast<__bf16*>(out), B, ns, h, w, S, src_batched,
+                           scale_w, scale_o);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -672,9 +578,9 @@ __global__ __launch_bounds__(256) void lwg_lwb_fuse_bwd_kernel(const float* __re
     const bool live = gp < total;
     if (!live) gp = total - 1;                    // every lane reaches the barrier; a dead lane stores and adds nothing
     const int hw = h * w;
-    const int b = (int)(gp / hw), rem = (int)(gp - (long)b * hw);
-    const int y = rem / w, x = rem - y * w;
-    const LwgFuseResize rz = lwg_fuse_resize(y, x, h, w, S);
+    int b, y, x;
+    lwb_pixel_of(gp, h, w, b, y, x);
+    const LwbResize rz = lwb_resize_of(y, x, h, w, S);
 
     const floatx4 do4 = *reinterpret_cast<const floatx4*>(dout + gp * C + 4 * cl);
     floatx4 g4 = {1.f, 1.f, 1.f, 1.f};
@@ -731,20 +637,10 @@ extern "C" int lwg_lwb_fuse_bwd_f32(const float* src_x, const float* gate, const
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!T || !dout || !d_tsf || !d_src || (gate && (!d_gate || !src_x)) || B <= 0 || ns <= 0 || ns > 64 || h <= 0 || w <= 0 || S <= 0)
         return (int)hipErrorInvalidValue;
-    const long total = (long)B * h * w;
-#define LWG_FUSE_BWD_LAUNCH(LPP)                                                                                      \
-    {                                                                                                                 \
-        const long per_block = 4 * (64 / LPP);                                                                        \
-        hipLaunchKernelGGL(lwg_lwb_fuse_bwd_kernel<LPP>, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0, stream, \
-                           src_x, gate, T, dout, d_tsf, d_src, d_gate, B, ns, h, w, S, src_batched, scale_w, scale_o);            \
-    }
-    switch (C) {
-        case 32: LWG_FUSE_BWD_LAUNCH(8) break;
-        case 64: LWG_FUSE_BWD_LAUNCH(16) break;
-        case 128: LWG_FUSE_BWD_LAUNCH(32) break;
-        case 256: LWG_FUSE_BWD_LAUNCH(64) break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LWG_FUSE_BWD_LAUNCH
-    return (int)hipGetLastError();
+    const bool known = lwg_lpp_dispatch<8, 64>(C, 4, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        hipLaunchKernelGGL(lwg_lwb_fuse_bwd_kernel<LPP>, lwg_lpp_grid<LPP>((long)B * h * w), dim3(256), 0, stream, src_x, gate, T, dout, d_tsf, d_src, d_gate,
+                           B, ns, h, w, S, src_batched, scale_w, scale_o);
+    });
+    return known ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }

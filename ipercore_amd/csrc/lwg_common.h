@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 #define LWG_WAVE 64
@@ -118,6 +120,41 @@ __device__ __forceinline__ int lwg_xcd_remap(int bid, int nwg) {
     const int xcd = bid & 7, idx = bid >> 3;
     const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return start + idx;
+}
+
+// bf16 pairs in a dword (the 16-byte accesses of the bf16 engines carry four): two floats rounded to nearest even and packed (v_cvt_pk_bf16_f32), and
+// a 16-byte row widened to its eight floats by shift / mask (exact)
+__device__ __forceinline__ unsigned lwg_bf16_pack2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    bf16x2 v;
+    v[0] = (__bf16)lo;
+    v[1] = (__bf16)hi;
+    return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ void lwg_bf16_widen8(const uintx4 v, float (&f)[8]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f[2 * k] = __builtin_bit_cast(float, v[k] << 16);
+        f[2 * k + 1] = __builtin_bit_cast(float, v[k] & 0xffff0000u);
+    }
+}
+
+// The per-pixel gather kernels (lwb_attn.hip, bf16_ops.hip) give a pixel LPP = C / cpl lanes, LPP a template argument: calls
+// launch(std::integral_constant<int, LPP>()) for LPP in {LO, 2 LO, 4 LO, 8 LO} up to HI with C == LPP * cpl; false: no kernel for this C.
+// Four waves per workgroup, 64 / LPP pixels per wave (lwg_lpp_grid).
+template <int LO, int HI, typename F> static inline bool lwg_lpp_dispatch(int C, int cpl, F&& launch) {
+    constexpr int TOP = 8 * LO <= HI ? 8 * LO : 4 * LO;
+    static_assert(4 * LO <= HI, "three or four lane counts");
+    if (C == LO * cpl) launch(std::integral_constant<int, LO>());
+    else if (C == 2 * LO * cpl) launch(std::integral_constant<int, 2 * LO>());
+    else if (C == 4 * LO * cpl) launch(std::integral_constant<int, 4 * LO>());
+    else if (C == TOP * cpl) launch(std::integral_constant<int, TOP>());
+    else return false;
+    return true;
+}
+template <int LPP> static inline dim3 lwg_lpp_grid(long total) {
+    constexpr long per_block = 4 * (64 / LPP);
+    return dim3((unsigned)((total + per_block - 1) / per_block));
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
