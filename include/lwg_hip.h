@@ -584,6 +584,29 @@ int lwg_up4_head_compose_bf16(const LwgConvArgs* args, const void* whead, const 
  * cv_utils.save_cv2_img(normalize=True), tools/utils/filesio/cv_utils.py:100-116): pred (B,3,S,S) fp32 ->
  * (B,S,S,3) uint8 = uint8((x+1)/2.0*255) in numpy fp32 arithmetic (truncation); bgr = 1: cv2's channel order. */
 int lwg_frames_to_u8(const float* pred, int B, int S, int bgr, uint8_t* out, lwg_stream_t stream);
+/* lwg_png_deflate_u8: the zlib stream of a PNG's single IDAT chunk, encoded on the device (csrc/png_deflate.hip; opt-in through
+ * output.FrameWriter(encoder="device")).  u8 (B,H,W,3) uint8 as lwg_frames_to_u8 writes it (H != W allowed) -> streams (B, capacity) uint8,
+ * nbytes (B,) int32: frame b's stream is streams[b * capacity .. + nbytes[b]), capacity = lwg_png_stream_capacity(H, W, rows_per_segment);
+ * bytes behind nbytes[b] are not written.  ws: lwg_png_deflate_ws_bytes(...) bytes of device memory, 16-byte aligned.  Two launches on
+ * `stream` (one workgroup per segment: filter, code, bits; then packing, Adler-32 and nbytes).  Integers only.
+ * Stream format (tests/pngdev_emu.py is the definition and states every tie rule; the kernels equal it byte for byte):
+ *   78 01, the segments, 01 00 00 FF FF, the big-endian Adler-32 of all raw bytes.
+ *   Raw bytes: PNG scanlines with filter type 4 (Paeth, 3 bytes per pixel) on every row - the byte 04, then 3W residuals; left / up /
+ *   upper-left are 0 outside the image.  A segment is rows_per_segment scanlines (the last one what is left), n = rows (1 + 3W) raw bytes.
+ *   A segment is ONE dynamic-Huffman block over literals only: BFINAL 0, BTYPE 2, HLIT 257, HDIST 1, HCLEN 19; the code-length code gives
+ *   the symbols 0..15 four bits each and 16..18 none, so the header is the 257 literal / length code lengths and one distance length 0
+ *   as 4-bit numbers (1 106 bits in all); the n literals; end of block; then an empty stored block (000, zero bits to the byte boundary,
+ *   00 00 FF FF) so that every segment ends on a byte.  Code lengths: Huffman over the segment's histogram + the end-of-block symbol once
+ *   (two queues, leaf before internal node on equal weight), limited to 15 bits by miniz's rule, handed out in ascending order to the symbols
+ *   sorted by (count descending, symbol ascending); canonical codes (RFC 1951 3.2.2).
+ *   If that takes more than n + 5 bytes the segment is one STORED block instead: 00, LEN, NLEN, the n raw bytes.  Hence
+ *   capacity = H (1 + 3W) + 5 nseg + 11.
+ * hipErrorInvalidValue before any launch: NULL pointers, sizes <= 0, a segment of more than 65 535 raw bytes (LEN is 16 bits: min(rows_per_segment,
+ * H) (1 + 3W) <= 65 535), a capacity beyond int32, ws not 16-byte aligned.  The two helpers are host-only and return 0 for such arguments. */
+int lwg_png_deflate_u8(const uint8_t* u8, int B, int H, int W, int rows_per_segment, void* ws, uint8_t* streams, int32_t* nbytes,
+                       lwg_stream_t stream);
+size_t lwg_png_stream_capacity(int H, int W, int rows_per_segment);
+size_t lwg_png_deflate_ws_bytes(int B, int H, int W, int rows_per_segment);
 int lwg_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int Cp, int P, lwg_stream_t stream);
 int lwg_nhwc_to_nchw_f32(const float* src, float* dst, int B, int C, int Cs, int P, lwg_stream_t stream);
 

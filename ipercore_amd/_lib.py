@@ -152,6 +152,9 @@ _SIGS = {
     "lwg_nchw_to_nhwc_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "lwg_nhwc_to_nchw_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "lwg_frames_to_u8": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f]),
+    "lwg_png_deflate_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
+    "lwg_png_stream_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "lwg_png_deflate_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "lwg_morph_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_canny_f32": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                             ctypes.c_float, ctypes.c_float, c_f, c_f, c_f]),

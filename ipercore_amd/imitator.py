@@ -84,6 +84,7 @@ class Imitator(object):
         self.generator = None
         self.temporal = bool(_opt_get(opt, "temporal", False))
         self.time_step = int(_opt_get(opt, "time_step", 1))
+        self.png_encoder = str(_opt_get(opt, "png_encoder", "host"))      # output.FrameWriter's encoder: "host" (zlib threads) or "device"
         self.temporal_fifo = None
         self.primary_ids = 0                      # which source's camera / shape drives the target (Swapper sets it)
         self._create_networks()
@@ -301,7 +302,7 @@ class Imitator(object):
             preds = self.synthesize_temporal(tgt, cam_strategy, use_selected_f2pts=use_selected_f2pts)
             if output_dir:
                 from .output import FrameWriter
-                writer = FrameWriter(output_dir, prefix=prefix)
+                writer = FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
                 writer.submit(preds, 0)
                 return writer.close()
             preds = preds.cpu().numpy()
@@ -309,7 +310,7 @@ class Imitator(object):
         if output_dir:
             # device-side uint8 conversion + pinned async D2H + threaded PNG encoding: the frame loop never waits for disk
             from .output import FrameWriter
-            writer = FrameWriter(output_dir, prefix=prefix)
+            writer = FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
             for s in range(0, tgt.shape[0], self.frame_batch):
                 writer.submit(self.synthesize(tgt[s:s + self.frame_batch], cam_strategy, t0=s, use_selected_f2pts=use_selected_f2pts), s)
             return writer.close()

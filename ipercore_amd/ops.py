@@ -1301,6 +1301,30 @@ def frames_to_u8(pred, bgr=False):
     return out
 
 
+def png_deflate(u8, rows_per_segment=16):
+    """(B,H,W,3) uint8 device frames -> (streams (B, capacity) uint8, nbytes (B,) int32): streams[b, :nbytes[b]] is the zlib stream of frame
+    b's PNG IDAT chunk (include/lwg_hip.h lwg_png_deflate_u8; ``output.png_from_stream`` wraps it into a file).  Bytes behind nbytes[b] are
+    not written."""
+    if not u8.is_cuda:
+        raise RuntimeError("png_deflate needs a device tensor: there is no CPU fallback")
+    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
+        raise ValueError("png_deflate takes a (B,H,W,3) uint8 tensor")
+    B, H, W, _ = u8.shape
+    lib = _lib.lib()
+    cap = lib.lwg_png_stream_capacity(H, W, int(rows_per_segment))
+    nws = lib.lwg_png_deflate_ws_bytes(max(B, 1), H, W, int(rows_per_segment))
+    if cap == 0 or nws == 0:
+        raise ValueError(f"png_deflate: no encoding for {H} x {W} frames in segments of {rows_per_segment} rows (a segment holds at most 65535 bytes)")
+    streams = torch.empty(B, cap, device=u8.device, dtype=torch.uint8)
+    nbytes = torch.empty(B, device=u8.device, dtype=torch.int32)
+    if B == 0:
+        return streams, nbytes
+    ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
+    _lib.check(lib.lwg_png_deflate_u8(_ptr(u8.contiguous(), torch.uint8), B, H, W, int(rows_per_segment), _ptr(ws, torch.uint8), _ptr(streams, torch.uint8),
+                                      _ptr(nbytes, torch.int32), _stream()), "lwg_png_deflate_u8")
+    return streams, nbytes
+
+
 # ---------------------------------------------------------------------------------------------- backward of the convs
 def conv2d_wgrad(x0, spec, dy, x1=None, out_hw=None, ycoff=0):
     """dW of the conv described by ``spec`` for inputs x0 (x1) and output gradient dy (laid out like the forward y) ->
