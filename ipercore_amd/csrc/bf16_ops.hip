@@ -4,7 +4,7 @@
 // tensors in HBM are bf16: half the bytes per launch, 16-byte accesses carry 8 channels.
 
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 #include "lwg_lwb_taps.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -178,7 +178,7 @@ extern "C" int lwg_lwb_attention_bf16(const void* q, const void* Ks, const void*
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!q || !Ks || !Vs || !bk || !bv || !T || !out || B <= 0 || ns <= 0 || h <= 0 || w <= 0 || S <= 0) return (int)hipErrorInvalidValue;
     const long total = lwg_tile_frame_positions(B, h, w);
-    const bool buf_ok = (unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * 2ull < 0xC0000000ull;
+    const bool buf_ok = lwg_buf_fits((unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * 2ull);
     const __bf16* qb = reinterpret_cast<const __bf16*>(q);
     const __bf16* Kb = reinterpret_cast<const __bf16*>(Ks);
     const __bf16* Vb = reinterpret_cast<const __bf16*>(Vs);
@@ -319,9 +319,9 @@ extern "C" int lwg_head_compose_bf16(const void* x, const void* wb, const float*
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!x || !wb || (pred && !bg) || (!pred && !mask && !img) || B <= 0 || S <= 0 || C != 64 || B > 65535) return (int)hipErrorInvalidValue;
     const unsigned long long per = (unsigned long long)S * S * 128ull;
-    if (per >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)B * per >= 0xC0000000ull) {     // the halo goes through 32-bit buffer offsets: larger batches run in slices of frames
-        const int nbs = (int)((0xC0000000ull - 1ull) / per);
+    const int nbs = lwg_slice_frames(B, per);
+    if (nbs < 0) return (int)hipErrorInvalidValue;
+    if (nbs > 0) {     // the halo goes through 32-bit buffer offsets: larger batches run in slices of frames
         const size_t plane = (size_t)S * S;
         for (int b0 = 0; b0 < B; b0 += nbs) {
             const int nb = B - b0 < nbs ? B - b0 : nbs;

@@ -33,7 +33,7 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
-#include "lwg_conv_slices.h"
+#include "lwg_conv_direct.h"
 #include "lwg_conv_epilogue.h"
 
 typedef int intx4 __attribute__((ext_vector_type(4)));
@@ -481,32 +481,25 @@ template <int WAVES_M, int WAVES_N, int TM, int TN, int EPI, bool SMALLC, bool D
 static hipError_t launch_cfg(const LwgConvArgs& a, hipStream_t stream, float* ws = nullptr) {
     constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
     constexpr size_t lds = (size_t)2 * 8 * ((BM + 1) * 4 + BN * 4) * sizeof(float) + 3 * LWG_MAX_TAPS * sizeof(int);
-    auto kern = lwg_conv_igemm_kernel<WAVES_M, WAVES_N, TM, TN, EPI, SMALLC, DEEP>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done); e != hipSuccess) return e;
+    constexpr auto kern = lwg_conv_igemm_kernel<WAVES_M, WAVES_N, TM, TN, EPI, SMALLC, DEEP>;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / BN;
     if constexpr (EPI == LWG_EPI_NONE && !SMALLC && BM == 64 && BN == 64) {
         int cps = 0;
         const int slices = ws ? lwg_conv_split_plan(a, &cps) : 0;
         if (slices > 1) {
-            hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, slices), dim3(256), lds, stream, a, cps, ws, 0u);
+            if (hipError_t e = lwg_launch_lds<kern>(dim3(tiles_m * tiles_n, slices), dim3(256), lds, stream, a, cps, ws, 0u); e != hipSuccess) return e;
             return lwg_splitk_finish_launch(a, ws, slices, stream);
         }
     }
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), lds, stream, a, 0, (float*)nullptr, 0u);
-    return hipGetLastError();
+    return lwg_launch_lds<kern>(dim3(tiles_m * tiles_n), dim3(256), lds, stream, a, 0, (float*)nullptr, 0u);
 }
 
 // The four parity launches of a transposed convolution as ONE grid (blockIdx.z = parity) on the small-launch tile configuration.
 template <int EPI>
 static hipError_t launch_parity4(const LwgConvArgs& a, hipStream_t stream, unsigned panel_floats) {
     constexpr size_t lds = (size_t)2 * 8 * ((64 + 1) * 4 + 64 * 4) * sizeof(float) + 3 * LWG_MAX_TAPS * sizeof(int);
-    auto kern = lwg_conv_igemm_kernel<2, 2, 1, 1, EPI, false, LWG_CONV_DEEP != 0>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done); e != hipSuccess) return e;
     const int tiles_m = (a.M + 63) / 64, tiles_n = a.N / 64;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, 1, 4), dim3(256), lds, stream, a, 0, (float*)nullptr, panel_floats);
-    return hipGetLastError();
+    return lwg_launch_lds<lwg_conv_igemm_kernel<2, 2, 1, 1, EPI, false, LWG_CONV_DEEP != 0>>(dim3(tiles_m * tiles_n, 1, 4), dim3(256), lds, stream, a, 0, (float*)nullptr, panel_floats);
 }
 
 template <int EPI, bool SMALLC>
@@ -536,39 +529,25 @@ extern "C" int lwg_conv2d_nhwc_f32_ws(const LwgConvArgs* pa, float* ws, lwg_stre
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return ws ? 1 : lwg_conv2d_nhwc_f32_ws(&s, nullptr, stream_); }, &sliced_err)) return sliced_err;
-    }
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (a workspace is sized for the whole launch: refused)
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return ws ? 1 : lwg_conv2d_nhwc_f32_ws(&s, nullptr, stream_); }); e >= 0) return e;
     const int Cin = a.C0 + a.C1;
-    if (!a.x0 || !a.w || !a.y || a.ntaps < 1 || a.ntaps > LWG_MAX_TAPS || a.M <= 0) return (int)hipErrorInvalidValue;
-    if (a.N % 64 != 0 || (Cin & 3) != 0 || (a.YC & 3) != 0 || (a.ycoff & 3) != 0) return (int)hipErrorInvalidValue;
-    if (a.xdt != LWG_DT_F32 || (a.ydt != LWG_DT_F32 && ((a.ydt != LWG_DT_BF16 && a.ydt != LWG_DT_F32_Q4) || a.epi != LWG_EPI_NONE || ws))) return (int)hipErrorInvalidValue;
-    if (a.ydt == LWG_DT_F32_Q4 && a.act == LWG_ACT_RELU_MASK) return (int)hipErrorInvalidValue;
-    // buffer-load addressing: every tensor the kernel gathers from must be smaller than LWG_OOB_OFFSET bytes
-    const unsigned long long pix = (unsigned long long)a.B * a.H * a.W;
-    if (pix * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 4ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    // fp32 in; out fp32, or - plain epilogue, no workspace - bf16 / channel-quad planes (those without the ReLU mask)
+    if (a.ydt != LWG_DT_F32 && ((a.ydt != LWG_DT_BF16 && a.ydt != LWG_DT_F32_Q4) || a.epi != LWG_EPI_NONE || ws)) return (int)hipErrorInvalidValue;
+    if (!cd_contract_ok(a, CdEngine{LWG_DT_F32, a.ydt, 4, 32, 4, 0ull}) || (a.ydt == LWG_DT_F32_Q4 && a.act == LWG_ACT_RELU_MASK)) return (int)hipErrorInvalidValue;
+    // Cin % 32 != 0: the first layers' form - one input of 4, 8 or 16 channels, plain epilogue
     const bool smallc = (Cin % 32) != 0;
-    if (smallc) {
-        if (a.C1 != 0 || Cin > 16 || (Cin & (Cin - 1)) != 0 || (1 << a.cshift) != (Cin >> 2)) return (int)hipErrorInvalidValue;
-    } else if (a.C1 != 0 && (a.C0 % 32 != 0 || !a.x1)) {
-        return (int)hipErrorInvalidValue;
-    }
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.N % 128 != 0 || smallc || a.YC * 2 != a.N) return (int)hipErrorInvalidValue;
-        return (int)launch_epi<LWG_EPI_SPADE, false>(a, stream);
-    }
-    if (a.epi == LWG_EPI_RESIDUAL) {
-        if (!a.res || smallc) return (int)hipErrorInvalidValue;
-        if (a.act == LWG_ACT_RELU_MASK && ws) {
+    if (smallc && (a.C1 != 0 || Cin > 16 || (Cin & (Cin - 1)) != 0 || (1 << a.cshift) != (Cin >> 2) || a.epi != LWG_EPI_NONE)) return (int)hipErrorInvalidValue;
+    if (a.act == LWG_ACT_RELU_MASK && a.epi == LWG_EPI_NONE) return (int)hipErrorInvalidValue;
+    return cd_epi_dispatch(a, 128, false, [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        if constexpr (EPI == LWG_EPI_RESIDUAL) {
             int cps = 0;
-            if (lwg_conv_split_plan(a, &cps) > 1) return (int)launch_epi<LWG_EPI_NONE, false>(a, stream, ws);   // slabs + the masking finish kernel
+            if (a.act == LWG_ACT_RELU_MASK && ws && lwg_conv_split_plan(a, &cps) > 1) return launch_epi<LWG_EPI_NONE, false>(a, stream, ws);   // slabs + the masking finish kernel
         }
-        return (int)launch_epi<LWG_EPI_RESIDUAL, false>(a, stream);
-    }
-    if (a.act == LWG_ACT_RELU_MASK) return (int)hipErrorInvalidValue;
-    if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    return smallc ? (int)launch_epi<LWG_EPI_NONE, true>(a, stream) : (int)launch_epi<LWG_EPI_NONE, false>(a, stream, ws);
+        if constexpr (EPI == LWG_EPI_NONE) return smallc ? launch_epi<LWG_EPI_NONE, true>(a, stream) : launch_epi<LWG_EPI_NONE, false>(a, stream, ws);
+        else return launch_epi<EPI, false>(a, stream);
+    });
 }
 
 // nn.ConvTranspose2d(kernel 4, stride 2, padding 1) on fp32 NHWC as ONE call (decoder up-sampling, attlwb_spade_resunet.py:331-340;
@@ -590,17 +569,14 @@ extern "C" int lwg_conv_transpose4_nhwc_f32(const LwgConvArgs* pa, lwg_stream_t 
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv_transpose4_nhwc_f32(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 4 || a.stride != 1 || a.omul != 2 || a.ooy != 0 || a.oox != 0 || a.C1 != 0 ||
-        a.epi != LWG_EPI_NONE || a.xdt != LWG_DT_F32 || (a.ydt != LWG_DT_F32 && a.ydt != LWG_DT_F32_Q4) || a.C0 % 32 != 0 || a.N % 64 != 0 || (a.YC & 3) != 0 ||
-        (a.ycoff & 3) != 0 || a.OH != a.H || a.OW != a.W || a.YH != 2 * a.H || a.YW != 2 * a.W)
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv_transpose4_nhwc_f32(&s, stream_); }); e >= 0) return e;
+    if (!cd_basics_ok(a, 4) || a.ntaps != 4 || a.stride != 1 || a.omul != 2 || a.ooy != 0 || a.oox != 0 || a.C1 != 0 || a.epi != LWG_EPI_NONE ||
+        a.xdt != LWG_DT_F32 || (a.ydt != LWG_DT_F32 && a.ydt != LWG_DT_F32_Q4) || a.C0 % 32 != 0 || a.OH != a.H || a.OW != a.W || a.YH != 2 * a.H || a.YW != 2 * a.W)
         return (int)hipErrorInvalidValue;
     for (int t = 0; t < 4; ++t)
         if (a.dy[t] < -1 || a.dy[t] > 0 || a.dx[t] < -1 || a.dx[t] > 0) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.B * a.H * a.W * (unsigned long long)a.C0 * 4ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    if (!lwg_buf_fits((unsigned long long)a.B * a.H * a.W * (unsigned long long)a.C0 * 4ull)) return (int)hipErrorInvalidValue;
     const unsigned panel_floats = 4u * (unsigned)a.C0 * (unsigned)a.N;
     if (lwg_conv_transpose4_is_one_grid(pa)) return (int)launch_parity4<LWG_EPI_NONE>(a, stream, panel_floats);
     for (int p = 0; p < 4; ++p) {

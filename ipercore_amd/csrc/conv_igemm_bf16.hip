@@ -26,7 +26,7 @@
 #ifndef LWG_BF16_NT_ST
 #define LWG_BF16_NT_ST 0     // lab: the epilogue's 16-byte output stores non-temporal (worth 0.5 % in conv_winograd4.hip)
 #endif
-#include "lwg_conv_slices.h"
+#include "lwg_conv_direct.h"
 #include "lwg_bf16_hr_list.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1003,14 +1003,10 @@ extern "C" int lwg_conv_transpose4_nhwc_bf16(const LwgConvArgs* pa, lwg_stream_t
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv_transpose4_nhwc_bf16(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps != 4 || a.C1 != 0 || (a.C0 != 64 && a.C0 != 128)) return (int)hipErrorInvalidValue;
-    if (a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16 || a.stride != 1 || a.H != a.OH || a.W != a.OW || a.omul != 2) return (int)hipErrorInvalidValue;
-    if (a.YH != 2 * a.OH || a.YW != 2 * a.OW || a.N % 64 != 0 || (a.YC & 7) != 0 || (a.ycoff & 7) != 0 || a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.B * a.H * a.W * (unsigned long long)a.C0 * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv_transpose4_nhwc_bf16(&s, stream_); }); e >= 0) return e;
+    if (!cd_basics_ok(a, 8) || a.ntaps != 4 || a.C1 != 0 || (a.C0 != 64 && a.C0 != 128) || a.epi != LWG_EPI_NONE || !cd_inputs_fit(a, 2ull)) return (int)hipErrorInvalidValue;
+    if (a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16 || a.stride != 1 || a.H != a.OH || a.W != a.OW || a.omul != 2 || a.YH != 2 * a.OH || a.YW != 2 * a.OW) return (int)hipErrorInvalidValue;
     if (a.N % 128 == 0) return (int)(a.C0 == 64 ? launch_cfg_bf16_up4<1, 1>(a, stream) : launch_cfg_bf16_up4<2, 1>(a, stream));
     return (int)(a.C0 == 64 ? launch_cfg_bf16_up4<1, 2>(a, stream) : launch_cfg_bf16_up4<2, 2>(a, stream));
 }
@@ -1108,18 +1104,9 @@ template <int NCH, int WAVES_N, int TM>
 static hipError_t launch_cfg_bf16_pw_tm(const LwgConvArgs& a, hipStream_t stream) {
     constexpr int BM = (8 / WAVES_N) * TM * 32;
     constexpr size_t lds = (size_t)2 * NCH * BM * 128;
-    auto kern = lwg_conv_bf16_pw_kernel<NCH, WAVES_N, TM>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done); e != hipSuccess) return e;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    }
     const int ntiles = (a.M + BM - 1) / BM;
-    const int slots = cus * (TM == 4 ? 1 : 2);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < slots ? ntiles : slots)), dim3(512), lds, stream, a);
-    return hipGetLastError();
+    const int slots = lwg_device_cus() * (TM == 4 ? 1 : 2);
+    return lwg_launch_lds<lwg_conv_bf16_pw_kernel<NCH, WAVES_N, TM>>(dim3((unsigned)(ntiles < slots ? ntiles : slots)), dim3(512), lds, stream, a);
 }
 
 template <int NCH, int WAVES_N>
@@ -1212,18 +1199,17 @@ extern "C" int lwg_conv2d_nhwc_c8_bf16(const LwgConvArgs* pa, lwg_stream_t strea
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_c8_bf16(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    if (!a.x0 || !a.w || !a.y || a.M <= 0 || a.ntaps < 1 || a.ntaps > 10) return (int)hipErrorInvalidValue;
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_c8_bf16(&s, stream_); }); e >= 0) return e;
+    if (!cd_basics_ok(a, 8) || a.ntaps < 1 || a.ntaps > 10 || a.stride < 1 || !cd_inputs_fit(a, 4ull)) return (int)hipErrorInvalidValue;
     if (a.xdt != LWG_DT_F32 || a.ydt != LWG_DT_BF16 || a.C0 != 8 || a.C1 != 0 || a.N != 64 || a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    if ((a.YC & 7) != 0 || (a.ycoff & 7) != 0 || a.stride < 1) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.B * a.H * a.W * 32ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
     const int ngroups4 = (a.M + 255) / 256;
     hipLaunchKernelGGL(lwg_conv_c8_bf16_kernel, dim3((unsigned)(ngroups4 < 2048 ? ngroups4 : 2048)), dim3(256), 0, stream, a, (a.ntaps + 1) / 2);
     return hipGetLastError();
 }
+
+// the generic bf16 engines' contract (lwg_conv_direct.h): bf16 in and out, 64-channel K chunks, 8-channel output slices, a 2-byte panel entry per (k, n)
+static constexpr CdEngine LWG_BF16_ENGINE = {LWG_DT_BF16, LWG_DT_BF16, 64, 64, 8, 2ull};
 
 template <int EPI>
 static hipError_t launch_epi_bf16_hr(const LwgConvArgs& a, hipStream_t stream) {
@@ -1238,38 +1224,22 @@ extern "C" int lwg_conv2d_nhwc_bf16_hr(const LwgConvArgs* pa, lwg_stream_t strea
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_bf16_hr(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    const int Cin = a.C0 + a.C1;
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_bf16_hr(&s, stream_); }); e >= 0) return e;
     if (!a.x0 || !a.w || !a.y || a.M <= 0 || (a.ntaps != 9 && a.ntaps != 4 && a.ntaps != 1)) return (int)hipErrorInvalidValue;
     if (a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16 || a.stride != 1 || a.H != a.OH || a.W != a.OW) return (int)hipErrorInvalidValue;
     if (a.ntaps == 1) {
-        // pointwise C -> C launches: weights resident in registers, persistent workgroups (lwg_conv_bf16_pw_kernel)
+        // pointwise C -> C launches: weights resident in registers, persistent workgroups (lwg_conv_bf16_pw_kernel); its input is M rows of C0
         if (!lwg_bf16_pw_ok(a) || (a.YC & 7) != 0 || (a.ycoff & 7) != 0) return (int)hipErrorInvalidValue;
-        if ((unsigned long long)a.M * (unsigned long long)a.C0 * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+        if (!lwg_buf_fits((unsigned long long)a.M * (unsigned long long)a.C0 * 2ull)) return (int)hipErrorInvalidValue;
         if (a.N == 64) return (int)launch_cfg_bf16_pw<1, 2>(a, stream);
         if (a.N == 128) return (int)launch_cfg_bf16_pw<2, 4>(a, stream);
         return (int)launch_cfg_bf16_pw<4, 8>(a, stream);
     }
-    if (a.N % 64 != 0 || Cin % 64 != 0 || (a.YC & 7) != 0 || (a.ycoff & 7) != 0) return (int)hipErrorInvalidValue;
-    if (a.C1 != 0 && (a.C0 % 64 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
+    if (!cd_contract_ok(a, LWG_BF16_ENGINE)) return (int)hipErrorInvalidValue;
     for (int t = 0; t < a.ntaps; ++t)
         if (a.dy[t] < -1 || a.dy[t] > 1 || a.dx[t] < -1 || a.dx[t] > 1) return (int)hipErrorInvalidValue;
-    const unsigned long long pix = (unsigned long long)a.B * a.H * a.W;
-    if (pix * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.ntaps * (Cin / 64) * (unsigned long long)a.N * 128ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.YC * 2 != a.N || a.ycoff != 0) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_bf16_hr<LWG_EPI_SPADE>(a, stream);
-    }
-    if (a.epi == LWG_EPI_RESIDUAL) {
-        if (!a.res) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_bf16_hr<LWG_EPI_RESIDUAL>(a, stream);
-    }
-    if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    return (int)launch_epi_bf16_hr<LWG_EPI_NONE>(a, stream);
+    return cd_epi_dispatch(a, 64, true, [&](auto epi) { return launch_epi_bf16_hr<decltype(epi)::value>(a, stream); });       // (SPADE: any N = 2 YC)
 }
 
 // The list-driven 3 x 3 launch (include/lwg_hip.h): hrl_contract_ok on the shapes; the grid is the host's number - every in-image
@@ -1296,7 +1266,7 @@ extern "C" int lwg_conv2d_nhwc_bf16_hr_acc(const LwgConvArgs* pa, lwg_stream_t s
     LwgConvArgs a = *pa;
     if (a.ydt != LWG_DT_F32 || a.epi != LWG_EPI_NONE || a.act != LWG_ACTIVATION_NONE || a.YC != a.N || a.ycoff != 0) return (int)hipErrorInvalidValue;
     a.ydt = LWG_DT_BF16;                             // (the shape rules of the list form; the kernel stores floats)
-    if (!hrl_contract_ok(a) || (unsigned long long)a.B * a.H * a.W * (unsigned long long)a.C0 * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    if (!hrl_contract_ok(a) || !cd_inputs_fit(a, 2ull)) return (int)hipErrorInvalidValue;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     constexpr size_t lds = (size_t)2 * LWG_HALO_BYTES + 2 * 128 * sizeof(float);
     hipLaunchKernelGGL((lwg_conv_bf16_hr2_kernel<3, 3, LWG_EPI_NONE, 1, HR2_ACC>), dim3((unsigned)hrl_grid(a.B, a.OH, a.OW, a.N / HRL_BN)), dim3(256), lds, stream, a);
@@ -1307,12 +1277,8 @@ template <int WAVES_M, int WAVES_N, int TM, int TN, int EPI, bool DMA_A>
 static hipError_t launch_cfg_bf16(const LwgConvArgs& a, hipStream_t stream) {
     constexpr int BM = WAVES_M * TM * 32, BN = WAVES_N * TN * 32;
     constexpr size_t lds = (size_t)2 * (BM + BN) * 128 + 3 * LWG_MAX_TAPS * sizeof(int);
-    auto kern = lwg_conv_bf16_kernel<WAVES_M, WAVES_N, TM, TN, EPI, DMA_A>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done); e != hipSuccess) return e;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / BN;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WAVES_M * WAVES_N * 64), lds, stream, a);
-    return hipGetLastError();
+    return lwg_launch_lds<lwg_conv_bf16_kernel<WAVES_M, WAVES_N, TM, TN, EPI, DMA_A>>(dim3(tiles_m * tiles_n), dim3(WAVES_M * WAVES_N * 64), lds, stream, a);
 }
 
 template <int EPI>
@@ -1321,11 +1287,7 @@ static hipError_t launch_epi_bf16(const LwgConvArgs& a, hipStream_t stream) {
     // ds_write); LWG_BF16_TILE64 0 = heuristic below, 1 = 128 x 64 tiles wherever the epilogue allows, -1 = never; LWG_BF16_BIG 1 =
     // the 8-wave 256 x 256 tile where it applies
     constexpr bool dma_a = LWG_BF16_DMA_A != 0;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    }
+    const int cus = lwg_device_cus();
     // N % 256 == 0 and at least one 256 x 256 tile per CU: eight waves, wave tile 128 x 64 - six fragment reads per eight MFMAs
     // instead of four per four (the 4-wave kernel's LDS port is as busy as its matrix pipe)
     if (LWG_BF16_BIG && dma_a && a.N % 256 == 0 && (long)((a.M + 255) / 256) * (a.N / 256) >= (long)cus) return launch_cfg_bf16<2, 4, 4, 2, EPI, true>(a, stream);
@@ -1343,26 +1305,8 @@ extern "C" int lwg_conv2d_nhwc_bf16(const LwgConvArgs* pa, lwg_stream_t stream_)
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_bf16(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    const int Cin = a.C0 + a.C1;
-    if (!a.x0 || !a.w || !a.y || a.ntaps < 1 || a.ntaps > LWG_MAX_TAPS || a.M <= 0) return (int)hipErrorInvalidValue;
-    if (a.xdt != LWG_DT_BF16 || a.ydt != LWG_DT_BF16) return (int)hipErrorInvalidValue;
-    if (a.N % 64 != 0 || Cin % 64 != 0 || (a.YC & 7) != 0 || (a.ycoff & 7) != 0) return (int)hipErrorInvalidValue;
-    if (a.C1 != 0 && (a.C0 % 64 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
-    const unsigned long long pix = (unsigned long long)a.B * a.H * a.W;
-    if (pix * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 2ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.ntaps * (Cin / 64) * (unsigned long long)a.N * 128ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.N % 128 != 0 || a.YC * 2 != a.N || a.ycoff != 0) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_bf16<LWG_EPI_SPADE>(a, stream);
-    }
-    if (a.epi == LWG_EPI_RESIDUAL) {
-        if (!a.res) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_bf16<LWG_EPI_RESIDUAL>(a, stream);
-    }
-    if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    return (int)launch_epi_bf16<LWG_EPI_NONE>(a, stream);
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_bf16(&s, stream_); }); e >= 0) return e;
+    if (!cd_contract_ok(a, LWG_BF16_ENGINE)) return (int)hipErrorInvalidValue;
+    return cd_epi_dispatch(a, 128, true, [&](auto epi) { return launch_epi_bf16<decltype(epi)::value>(a, stream); });
 }

@@ -26,7 +26,7 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
-#include "lwg_conv_slices.h"
+#include "lwg_conv_direct.h"
 #include "lwg_conv_epilogue.h"
 
 typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
@@ -620,12 +620,8 @@ __global__ __launch_bounds__(512, 1) void lwg_conv_igemm_split_pp_kernel(const L
 template <int EPI>
 static hipError_t launch_split_pp(const LwgConvArgs& a, hipStream_t stream) {
     constexpr size_t lds = (size_t)2 * (2 * 3 * 2 * (128 + 4) * 16 + 3 * 2 * 128 * 16) + 3 * LWG_MAX_TAPS * sizeof(int);
-    auto kern = lwg_conv_igemm_split_pp_kernel<EPI>;
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done); e != hipSuccess) return e;
     const int tiles_m = (a.M + 255) / 256, tiles_n = a.N / 128;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, stream, a);
-    return hipGetLastError();
+    return lwg_launch_lds<lwg_conv_igemm_split_pp_kernel<EPI>>(dim3(tiles_m * tiles_n), dim3(512), lds, stream, a);
 }
 
 // the 256x128 ping-pong kernel needs N % 128 == 0 and enough tiles that one workgroup per CU keeps the chip busy
@@ -651,26 +647,8 @@ extern "C" int lwg_conv2d_nhwc_f32_split(const LwgConvArgs* pa, lwg_stream_t str
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pa) return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    {   // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices (lwg_conv_slices.h)
-        int sliced_err = 0;
-        if (lwg_conv_run_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_f32_split(&s, stream_); }, &sliced_err)) return sliced_err;
-    }
-    const int Cin = a.C0 + a.C1;
-    if (!a.x0 || !a.w || !a.y || a.ntaps < 1 || a.ntaps > LWG_MAX_TAPS || a.M <= 0) return (int)hipErrorInvalidValue;
-    if (a.N % 64 != 0 || Cin % 32 != 0 || (a.YC & 3) != 0 || (a.ycoff & 3) != 0) return (int)hipErrorInvalidValue;
-    if (a.C1 != 0 && (a.C0 % 32 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
-    const unsigned long long pix = (unsigned long long)a.B * a.H * a.W;
-    if (pix * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 4ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.ntaps * Cin * a.N * 6ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if (a.xdt != LWG_DT_F32 || a.ydt != LWG_DT_F32) return (int)hipErrorInvalidValue;
-    if (a.epi == LWG_EPI_SPADE) {
-        if (!a.xn || !a.mean || !a.rstd || !a.bias || a.N % 128 != 0 || a.YC * 2 != a.N) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_split<LWG_EPI_SPADE>(a, stream);
-    }
-    if (a.epi == LWG_EPI_RESIDUAL) {
-        if (!a.res) return (int)hipErrorInvalidValue;
-        return (int)launch_epi_split<LWG_EPI_RESIDUAL>(a, stream);
-    }
-    if (a.epi != LWG_EPI_NONE) return (int)hipErrorInvalidValue;
-    return (int)launch_epi_split<LWG_EPI_NONE>(a, stream);
+    // inputs beyond the 32-bit buffer-offset range: the same launch in batch slices
+    if (const int e = cd_sliced(a, [&](const LwgConvArgs& s) { return lwg_conv2d_nhwc_f32_split(&s, stream_); }); e >= 0) return e;
+    if (!cd_contract_ok(a, CdEngine{LWG_DT_F32, LWG_DT_F32, 32, 32, 4, 6ull})) return (int)hipErrorInvalidValue;        // (the three bf16 planes: 6 bytes per (k, n))
+    return cd_epi_dispatch(a, 128, false, [&](auto epi) { return launch_epi_split<decltype(epi)::value>(a, stream); });
 }

@@ -19,7 +19,7 @@
 #include <type_traits>
 
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 
 #define LWG_OOB_OFFSET 0xC0000000u
 
@@ -557,9 +557,7 @@ static int lwg_wgrad_launch(const LwgConvArgs* pa, const float* dy, float* ws, h
     const int Cin = a.C0 + a.C1;
     if (!a.x0 || a.ntaps < 1 || a.ntaps > LWG_MAX_TAPS || a.M <= 0 || a.N <= 0 || (a.N & 3) || (Cin & 3) || (a.YC & 3) || (a.ycoff & 3))
         return (int)hipErrorInvalidValue;
-    const unsigned long long pix = (unsigned long long)a.B * a.H * a.W;
-    if (pix * (unsigned long long)(a.C0 > a.C1 ? a.C0 : a.C1) * 4ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    if ((unsigned long long)a.B * a.YH * a.YW * a.YC * 4ull >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    if (!cd_inputs_fit(a, 4ull) || !lwg_buf_fits((unsigned long long)a.B * a.YH * a.YW * a.YC * 4ull)) return (int)hipErrorInvalidValue;
     const bool smallc = (Cin % 32) != 0;
     if (smallc && (a.C1 != 0 || Cin > 16 || (Cin & (Cin - 1)) != 0 || (1 << a.cshift) != (Cin >> 2))) return (int)hipErrorInvalidValue;
     if (!smallc && a.C1 != 0 && (a.C0 % 32 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
@@ -570,13 +568,13 @@ static int lwg_wgrad_launch(const LwgConvArgs* pa, const float* dy, float* ws, h
     const int splits = lwg_wgrad_splits(Ktot, a.N, a.M);
     const int cps = (nchunks + splits - 1) / splits;
     const size_t lds = (size_t)4 * 32 * 128 * sizeof(float) + LWG_MAX_TAPS * sizeof(int);
-    auto kern = bn == 64 ? (smallc ? lwg_conv_wgrad_kernel<true, 64> : lwg_conv_wgrad_kernel<false, 64>)
-                         : (smallc ? lwg_conv_wgrad_kernel<true, 128> : lwg_conv_wgrad_kernel<false, 128>);
-    static unsigned long long attr_done[4] = {0ull, 0ull, 0ull, 0ull};
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, attr_done[(bn == 64 ? 2 : 0) + (smallc ? 1 : 0)]); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(tiles, splits), dim3(256), lds, stream, a, dy, Ktot, cps, ws, want_bias);
+    auto launch = [&](auto sc, auto bnc) {
+        return lwg_launch_lds<lwg_conv_wgrad_kernel<decltype(sc)::value != 0, decltype(bnc)::value>>(dim3(tiles, splits), dim3(256), lds, stream, a, dy, Ktot, cps, ws, want_bias);
+    };
+    const hipError_t e = bn == 64 ? (smallc ? launch(IntC<1>(), IntC<64>()) : launch(IntC<0>(), IntC<64>()))
+                                  : (smallc ? launch(IntC<1>(), IntC<128>()) : launch(IntC<0>(), IntC<128>()));
     *splits_out = splits;
-    return 0;
+    return (int)e;
 }
 
 // args: forward geometry; dy: gradient of the forward output (same layout as y); dw: (ntaps*Cin, N) row-major in the

@@ -20,7 +20,7 @@
 #include <type_traits>
 
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 
 #define WGW_OOB 0xC0000000u
 #define WGW_CT 8                                         // tiles per chunk
@@ -287,9 +287,7 @@ extern "C" int lwg_conv2d_wgrad_winograd_f32(const LwgConvArgs* pa, const float*
     const int splits = wgw_splits(a, lwg_device_cus());
     const int cps = (nchunks + splits - 1) / splits;
     const size_t lds = (size_t)2 * WGW_STAGE * sizeof(float);
-    static unsigned long long attr_done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_conv_wgrad_winograd_kernel), lds, attr_done); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(lwg_conv_wgrad_winograd_kernel, dim3((Ctot / 64) * (a.N / 64), splits), dim3(512), lds, stream, a, dy, TH, TW, T, cps, ws);
+    if (hipError_t e = lwg_launch_lds<lwg_conv_wgrad_winograd_kernel>(dim3((Ctot / 64) * (a.N / 64), splits), dim3(512), lds, stream, a, dy, TH, TW, T, cps, ws); e != hipSuccess) return (int)e;
     const size_t slab = (size_t)16 * Ctot * a.N, total = (size_t)cin * nout;
     if (total < 65536 && splits >= 32)
         hipLaunchKernelGGL(lwg_wgw_reduce_kernel<16>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, ws, splits, slab, Ctot, a.N, cin, nout, dw);

@@ -10,7 +10,7 @@
 // gather with 16-byte loads, one pixel per LPP = C/4 lanes, online softmax over the ns sources.
 
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 #include "lwg_lwb_taps.h"
 
 // BUF: the K / V taps through raw buffer loads - an out-of-image tap gets an out-of-range offset and the hardware returns zeros, so the
@@ -182,7 +182,7 @@ static int lwg_attn_launch(const float* q, const float* Ks, const float* Vs, con
                            int ns, int h, int w, int C, int S, int src_batched, int kvs, hipStream_t stream) {
     const long total = lwg_tile_frame_positions(B, h, w);
     // the buffer form's 32-bit offsets: the K (and V) tensor - the one K | V tensor of 2C-float rows in the KVS form - below 3 GB
-    const bool buf_ok = (unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * (KVS ? 8ull : 4ull) < 0xC0000000ull;
+    const bool buf_ok = lwg_buf_fits((unsigned long long)(src_batched ? B * ns : ns) * (unsigned long long)h * w * (unsigned long long)C * (KVS ? 8ull : 4ull));
     const bool known = lwg_lpp_dispatch<8, 64>(C, 4, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if (!buf_ok)

@@ -18,7 +18,7 @@
 // parameter-free norm, attlwb_spade_resunet.py:62,83) - one (count, mean, M2) record per (frame, tile, channel), merged by
 // lwg_in_stats_final (norm.hip) - and the separate statistics pass over x (9 launches, 9 full reads per frame) disappears.
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 #include "lwg_lwb_taps.h"
 
 typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
@@ -473,7 +473,7 @@ static int lwg_attnx_launch(const ST* x, const ST* Kq, const float* kappa, const
     if (!x || !Kq || !kappa || !Vs || !bv || !T || !out || B <= 0 || ns <= 0 || ns > 64 || h <= 0 || w <= 0) return (int)hipErrorInvalidValue;
     const unsigned long long nsrc = (unsigned long long)(src_batched ? B * ns : ns);
     // the taps go through 32-bit buffer offsets with 0xC0000000 as the out-of-range marker (zero fill): K / V below 3 GiB each
-    if (nsrc * (unsigned long long)h * w * (unsigned long long)C * sizeof(ST) >= 0xC0000000ull) return (int)hipErrorInvalidValue;
+    if (!lwg_buf_fits(nsrc * (unsigned long long)h * w * (unsigned long long)C * sizeof(ST))) return (int)hipErrorInvalidValue;
     const long tiles = (long)((w + 7) >> 3) * ((h + 7) >> 3);
     constexpr int CPL = AttnXTraits<ST>::CPL;
     const int npass = (C / CPL) / 4;

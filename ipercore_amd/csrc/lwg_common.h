@@ -104,6 +104,7 @@ __device__ __forceinline__ float lwg_act(float v, int act) {
 // taking LwgActC<A>; A >= 0: compile-time activation, -1: a.act at run time (tanh / sigmoid / the ReLU mask of a data gradient).  Same expressions per
 // value in every copy: same bits.
 template <int A> struct LwgActC { static constexpr int value = A; };
+template <int V> struct IntC { static constexpr int value = V; };      // any other compile-time integer handed to a generic lambda
 template <int A> __device__ __forceinline__ float lwg_act_c(float v, int act_runtime) { return lwg_act(v, A >= 0 ? A : act_runtime); }
 template <int A> __device__ __forceinline__ bool lwg_act_is_mask(int act_runtime) { return A == LWG_ACT_RELU_MASK || (A < 0 && act_runtime == LWG_ACT_RELU_MASK); }
 template <typename F> __device__ __forceinline__ void lwg_act_dispatch(int act, F&& body) {

@@ -317,9 +317,8 @@ CW_FN bool cw_panel_args_ok(const float* wpanel, const float* upk, int Cin, int 
 
 // ---- part 2: device code and the launch ----
 #ifdef __HIPCC__
-#include "lwg_common.h"
+#include "lwg_conv_direct.h"
 
-template <int V> struct IntC { static constexpr int value = V; };
 // POLICY: the cache policy of the load (0 = default; F(4x4)'s halo loads pass W4_NT_LD)
 template <int POLICY = 0>
 __device__ __forceinline__ floatx4 cw_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
@@ -377,21 +376,15 @@ __device__ __forceinline__ void cw_rst1(float* dst, int plane, floatx4 v) {
     for (int k = 0; k < 4; ++k) dst[k * plane] = v[k];
 }
 
-// The dynamic-LDS opt-in of one kernel instantiation (once per device) and its launch
+// The dynamic-LDS opt-in of one kernel instantiation (once per device) and its launch: lwg_launch_lds (lwg_conv_direct.h)
 template <void (*KERNEL)(const LwgConvArgs)>
 static inline int cw_launch(dim3 grid, unsigned threads, size_t lds, hipStream_t stream, const LwgConvArgs& a) {
-    static unsigned long long done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a);
-    return (int)hipGetLastError();
+    return (int)lwg_launch_lds<KERNEL>(grid, dim3(threads), lds, stream, a);
 }
 // ... of a list-driven kernel (LwgConvArgs and the lists)
 template <void (*KERNEL)(const LwgConvArgs, const LwgConvLists)>
 static inline int cw_launch_lists(dim3 grid, unsigned threads, size_t lds, hipStream_t stream, const LwgConvArgs& a, const LwgConvLists& l) {
-    static unsigned long long done = 0ull;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done); e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, a, l);
-    return (int)hipGetLastError();
+    return (int)lwg_launch_lds<KERNEL>(grid, dim3(threads), lds, stream, a, l);
 }
 // persistent workgroups: one per CU (LDS) at most, each walking block ids blockIdx.x + k gridDim.x (LWG_WINO_PERSIST = 0: one block per workgroup)
 static inline dim3 cw_persistent_grid(long long total, int cus) { return dim3((unsigned)(LWG_WINO_PERSIST && total > cus ? cus : total)); }

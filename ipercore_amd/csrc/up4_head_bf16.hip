@@ -15,7 +15,7 @@
 //            block) units per wave, the per-tap partial sums shifted through LDS (the input halo's space), tanh / sigmoid / compositing, fp32 NCHW planes.
 // Same arithmetic in the same order as the two kernels it replaces (bf16 rounding of the intermediate included): check_bf16_up4_head compares them.
 #include "lwg_common.h"
-#include "lwg_conv_args.h"
+#include "lwg_conv_direct.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int uintx4 __attribute__((ext_vector_type(4)));
@@ -316,21 +316,21 @@ extern "C" int lwg_up4_head_compose_bf16(const LwgConvArgs* pa, const void* whea
         a.act != LWG_ACT_RELU)
         return (int)hipErrorInvalidValue;
     const unsigned long long per = (unsigned long long)a.H * a.W * 256ull;
-    if (per >= 0xC0000000ull) return (int)hipErrorInvalidValue;
-    const int nbs = (int)((0xC0000000ull - 1ull) / per);                        // frames per launch (32-bit buffer offsets)
+    int nbs = lwg_slice_frames(a.B, per);                                       // frames per launch (32-bit buffer offsets)
+    if (nbs < 0) return (int)hipErrorInvalidValue;
+    if (nbs == 0) nbs = a.B;
     const size_t plane = (size_t)4 * a.H * a.W;
     const int tiles = ((2 * a.W + UH_TW - 1) / UH_TW) * ((2 * a.H + UH_TH - 1) / UH_TH);
     const int cus = lwg_device_cus();                                          // persistent workgroups: one per CU (156 KB of LDS each)
-    static unsigned long long done = 0;
-    if (hipError_t e = lwg_allow_dynamic_lds(reinterpret_cast<const void*>(lwg_up4_head_bf16_kernel), (size_t)UH_LDS, done); e != hipSuccess) return (int)e;
     for (int b0 = 0; b0 < a.B; b0 += nbs) {
         const int nb = a.B - b0 < nbs ? a.B - b0 : nbs;
         const __bf16* xs = reinterpret_cast<const __bf16*>(a.x0) + (size_t)b0 * a.H * a.W * 128;
         const long total = (long)tiles * nb;
-        hipLaunchKernelGGL(lwg_up4_head_bf16_kernel, dim3((unsigned)(total < cus ? total : cus)), dim3(512), (size_t)UH_LDS, stream, xs,
-                           reinterpret_cast<const __bf16*>(a.w), a.bias, reinterpret_cast<const __bf16*>(whead), bg ? bg + (size_t)b0 * bg_bstride : bg, bg_bstride,
-                           a.H, a.W, nb, (unsigned)((unsigned long long)nb * per), pred ? pred + (size_t)b0 * 3 * plane : pred, mask ? mask + (size_t)b0 * plane : mask,
-                           img ? img + (size_t)b0 * 3 * plane : img);
+        const hipError_t e = lwg_launch_lds<lwg_up4_head_bf16_kernel>(
+            dim3((unsigned)(total < cus ? total : cus)), dim3(512), (size_t)UH_LDS, stream, xs, reinterpret_cast<const __bf16*>(a.w), a.bias,
+            reinterpret_cast<const __bf16*>(whead), bg ? bg + (size_t)b0 * bg_bstride : bg, bg_bstride, a.H, a.W, nb, (unsigned)((unsigned long long)nb * per),
+            pred ? pred + (size_t)b0 * 3 * plane : pred, mask ? mask + (size_t)b0 * plane : mask, img ? img + (size_t)b0 * 3 * plane : img);
+        if (e != hipSuccess) return (int)e;
     }
-    return (int)hipGetLastError();
+    return 0;
 }

@@ -92,7 +92,7 @@ class Imitator(object):
     # ------------------------------------------------------------------ frame batch actually launched
     def max_frame_batch(self):
         """No per-tensor cap reaches the caller any more: a launch whose gathered input would exceed the conv kernels' 32-bit buffer
-        offsets (3 GiB) is cut into batch slices INSIDE the C entry points (csrc/lwg_conv_slices.h; a frame is independent of its
+        offsets (3 GiB) is cut into batch slices INSIDE the C entry points (csrc/lwg_conv_direct.h; a frame is independent of its
         batch, so the values do not change).  What bounds a frame batch now is device memory (~0.2 GB of fp32 activations per
         512 x 512 frame): returns None."""
         return None

@@ -1320,7 +1320,7 @@ def check_bf16_up4_head():
 
 def check_batch_slicing_1024():
     """Frame batches whose gathered tensors exceed the conv kernels' 32-bit buffer offsets (3 GiB): the C entry points cut the launch
-    into batch slices (csrc/lwg_conv_slices.h), the caller sees no limit.  1024 x 1024 novel-view poses: fp32 at frame batch 26 (the
+    into batch slices (csrc/lwg_conv_direct.h), the caller sees no limit.  1024 x 1024 novel-view poses: fp32 at frame batch 26 (the
     (26,512,512,128) skip / up-sampling inputs are 3.4 GiB) and bf16 at frame batch 50 (the same tensors in bf16, and the (50,1024,1024,64)
     head input = 6.7 GB) - every frame bitwise equal to its batches-of-2 rendering."""
     m = {}

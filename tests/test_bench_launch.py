@@ -196,7 +196,7 @@ def test_bench_personalize_eight_ranks_gloo(tmp_path):
 def test_default_frame_batch_and_kernel_launch_count():
     """N = 1: the clip of every benched configuration is ONE launch batch; N > 1: batches of 32 (fp32 at 512) so that the exchange of one batch
     overlaps the next.  The launch accounting counts the kernel launches behind a call the library slices over the batch: the library itself says
-    how many (lwg_conv_slice_count = the rule of csrc/lwg_conv_slices.h; no Python copy of it)."""
+    how many (lwg_conv_slice_count = the rule of csrc/lwg_conv_direct.h; no Python copy of it)."""
     import bench
     from ipercore_amd import _lib, ops
     assert bench.default_frame_batch("fp32", 512) >= 300 and bench.default_frame_batch("fp32", 1024) >= 96

@@ -125,7 +125,7 @@ def test_configs0_motion_imitate_256_cpu_plumbing(monkeypatch):
 
 def test_frame_batch_is_not_clamped(monkeypatch):
     """The 3 GiB per-tensor range of the conv kernels' buffer offsets no longer reaches the caller (launches are cut into batch slices
-    inside the C entry points, csrc/lwg_conv_slices.h): ``frame_batch`` is what was asked for at any size / precision mode."""
+    inside the C entry points, csrc/lwg_conv_direct.h): ``frame_batch`` is what was asked for at any size / precision mode."""
     emu_ops.install(monkeypatch)
     case = pu.build_case(image_size=64, num_filters=[64, 64, 128], n_res=2, bg_filters=[64, 64, 128], n_frames=1, ns=1)
     im = pu.make_imitator(case, frame_batch=12, device="cpu")
