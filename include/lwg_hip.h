@@ -356,7 +356,8 @@ int lwg_norm_bwd_nhwc_f32(const float* dy, const float* y, const float* x, const
 int lwg_adam_step_f32(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int t,
                       lwg_stream_t stream);
 /* The same update with the step count kept on the device (*t_dev is incremented, then read): what a captured (hipGraph) training step
- * must use, because a host-side step count would be frozen into the graph. */
+ * must use, because a host-side step count would be frozen into the graph.  Both forms run the same kernel, which forms the bias
+ * corrections 1 - beta^t itself: at the same t they give the same bits. */
 int lwg_adam_step_dev_f32(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                           int* t_dev, lwg_stream_t stream);
 /* Weight panels straight from the parameter tensors, one launch each (the personalization step re-packs every weight and
@@ -393,7 +394,7 @@ int lwg_crop_resize_bilinear_f32(const float* x, const long long* box, float* y,
                                  lwg_stream_t stream);
 int lwg_crop_resize_bilinear_bwd_f32(const float* dy, const long long* box, float* dx, int N, int C, int H, int W, int OH, int OW, lwg_stream_t stream);
 /* nn.PReLU(C) of the frozen Sphere20a (criterions/faceloss.py:209-283, relu{b}_{i}) on NHWC rows, with the block's residual add (:262-281, x + relu(conv(..)))
- * folded in: y = (res ? res : 0) + (x >= 0 ? x : slope[c] x); x, res, y (rows, C), slope (C), C % 4 == 0.  _bwd: dx = dy * (x >= 0 ? 1 : slope[c]) - the slopes
+ * folded in: y = (res ? res : 0) + (x > 0 ? x : slope[c] x); x, res, y (rows, C), slope (C), C % 4 == 0.  _bwd: dx = dy * (x > 0 ? 1 : slope[c]) - the slopes
  * are frozen (no gradient for them) and the residual's gradient is dy itself. */
 int lwg_prelu_f32(const float* x, const float* slope, const float* res, size_t rows, int C, float* y, lwg_stream_t stream);
 int lwg_prelu_bwd_f32(const float* x, const float* slope, const float* dy, size_t rows, int C, float* dx, lwg_stream_t stream);

@@ -45,8 +45,9 @@ extern "C" int lwg_act_bwd_f32(const float* dy, const float* y, size_t n, int ac
 }
 
 // ---------------------------------------------------------------------------------------------- per-channel PReLU (+ residual)
-// The frozen Sphere20a of the face loss (criterions/faceloss.py:203-285): y = res + (x >= 0 ? x : slope[c] x) on NHWC rows, res optional;
-// backward dx = dy * (x >= 0 ? 1 : slope[c]) (the slopes are frozen: no gradient for them; the residual's gradient is dy itself).
+// The frozen Sphere20a of the face loss (criterions/faceloss.py:203-285): y = res + (x > 0 ? x : slope[c] x) on NHWC rows, res optional;
+// backward dx = dy * (x > 0 ? 1 : slope[c]) - ATen's PReLU rule: at x = +-0 the gradient is slope[c] dy (the slopes are frozen: no gradient for
+// them; the residual's gradient is dy itself).
 template <bool BWD>
 __global__ void lwg_prelu_kernel(const floatx4* __restrict__ x, const floatx4* __restrict__ slope, const floatx4* __restrict__ other,
                                  int C4, size_t n4, floatx4* __restrict__ out) {
@@ -56,10 +57,10 @@ __global__ void lwg_prelu_kernel(const floatx4* __restrict__ x, const floatx4* _
         if (BWD) {
             const floatx4 g = other[i];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = v[k] >= 0.f ? g[k] : g[k] * a[k];
+            for (int k = 0; k < 4; ++k) o[k] = v[k] > 0.f ? g[k] : g[k] * a[k];
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) o[k] = v[k] >= 0.f ? v[k] : v[k] * a[k];
+            for (int k = 0; k < 4; ++k) o[k] = v[k] > 0.f ? v[k] : v[k] * a[k];
             if (other) {
                 const floatx4 r = other[i];
 #pragma unroll
@@ -278,8 +279,12 @@ extern "C" int lwg_norm_bwd_nhwc_f32(const float* dy, const float* y, const floa
 // ---------------------------------------------------------------------------------------------- Adam
 // torch.optim.Adam (lwg_trainer.py:140-146; no weight decay, no amsgrad) over one flat fp32 parameter buffer:
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= lr / (1 - b1^t) * m / (sqrt(v / (1 - b2^t)) + eps)
+// One kernel serves both entry points: the step count comes from *t_dev (the graph-capturable form) or, with t_dev NULL, from the host's t.
+// Either way the bias corrections 1 - b^t are formed HERE, with the device's powf: at the same t the two forms give the same bits.
 __global__ void lwg_adam_kernel(floatx4* __restrict__ p, const floatx4* __restrict__ g, floatx4* __restrict__ m, floatx4* __restrict__ v,
-                                size_t n4, float lr, float b1, float b2, float eps, float bc1, float bc2) {
+                                size_t n4, float lr, float b1, float b2, float eps, const int* __restrict__ t_dev, int t_host) {
+    const float t = (float)(t_dev ? *t_dev : t_host);
+    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
     const float step = lr / bc1, isq = 1.f / sqrtf(bc2);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         floatx4 pp = p[i], mm = m[i], vv = v[i];
@@ -298,36 +303,16 @@ extern "C" int lwg_adam_step_f32(float* p, const float* g, float* m, float* v, s
                                  int t, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!p || !g || !m || !v || n == 0 || (n & 3) || t < 1) return (int)hipErrorInvalidValue;
-    const float bc1 = 1.f - powf(beta1, (float)t), bc2 = 1.f - powf(beta2, (float)t);
     const size_t n4 = n / 4;
     const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
     hipLaunchKernelGGL(lwg_adam_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<floatx4*>(p), reinterpret_cast<const floatx4*>(g),
-                       reinterpret_cast<floatx4*>(m), reinterpret_cast<floatx4*>(v), n4, lr, beta1, beta2, eps, bc1, bc2);
+                       reinterpret_cast<floatx4*>(m), reinterpret_cast<floatx4*>(v), n4, lr, beta1, beta2, eps, (const int*)nullptr, t);
     return (int)hipGetLastError();
 }
 
-// The same update with the step count on the DEVICE: *t_dev is incremented by a one-thread launch, then the update reads it and
-// forms the bias corrections itself - so a captured (hipGraph) training step replays with the right t (a host-side t would be
-// frozen into the graph at capture time).
+// The same update with the step count on the DEVICE: *t_dev is incremented by a one-thread launch, then the update reads it - so a
+// captured (hipGraph) training step replays with the right t (a host-side t would be frozen into the graph at capture time).
 __global__ void lwg_adam_tick_kernel(int* t_dev) { *t_dev += 1; }
-
-__global__ void lwg_adam_dev_kernel(floatx4* __restrict__ p, const floatx4* __restrict__ g, floatx4* __restrict__ m, floatx4* __restrict__ v,
-                                    size_t n4, float lr, float b1, float b2, float eps, const int* __restrict__ t_dev) {
-    const float t = (float)*t_dev;
-    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
-    const float step = lr / bc1, isq = 1.f / sqrtf(bc2);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        floatx4 pp = p[i], mm = m[i], vv = v[i];
-        const floatx4 gg = g[i];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-            vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-            pp[k] -= step * mm[k] / (sqrtf(vv[k]) * isq + eps);
-        }
-        p[i] = pp; m[i] = mm; v[i] = vv;
-    }
-}
 
 extern "C" int lwg_adam_step_dev_f32(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                                      int* t_dev, lwg_stream_t stream_) {
@@ -336,8 +321,8 @@ extern "C" int lwg_adam_step_dev_f32(float* p, const float* g, float* m, float* 
     const size_t n4 = n / 4;
     const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
     hipLaunchKernelGGL(lwg_adam_tick_kernel, dim3(1), dim3(1), 0, stream, t_dev);
-    hipLaunchKernelGGL(lwg_adam_dev_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<floatx4*>(p), reinterpret_cast<const floatx4*>(g),
-                       reinterpret_cast<floatx4*>(m), reinterpret_cast<floatx4*>(v), n4, lr, beta1, beta2, eps, t_dev);
+    hipLaunchKernelGGL(lwg_adam_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<floatx4*>(p), reinterpret_cast<const floatx4*>(g),
+                       reinterpret_cast<floatx4*>(m), reinterpret_cast<floatx4*>(v), n4, lr, beta1, beta2, eps, (const int*)t_dev, 0);
     return (int)hipGetLastError();
 }
 
@@ -493,8 +478,10 @@ extern "C" int lwg_unpack_wgrad_f32(const float* dwk, int D0, int D1, int KH, in
 
 // ---------------------------------------------------------------------------------------------------------------
 // MaxPool2d(kernel 2, stride 2) on NHWC, forward and backward (VGG19 perceptual loss of the personalization step,
-// criterions/vggloss.py:6-96).  The backward routes each gradient to the FIRST maximum of its window in scan order
-// (0,0) (0,1) (1,0) (1,1), as ATen's max_pool2d_with_indices does; H and W even.
+// criterions/vggloss.py:6-96).  Both directions scan the window in the order (0,0) (0,1) (1,0) (1,1) and keep the FIRST maximum
+// (v > m replaces m), as ATen's max_pool2d_with_indices does: the forward returns that element's bits (of tied -0 / +0 the first),
+// the backward routes the gradient to it; H and W even.  A window that is entirely -inf gives -inf and sends its gradient to (0,0),
+// as ATen does.  NaN inputs are outside the contract: the ordered compare drops a NaN (as fmaxf would) where ATen propagates it.
 __global__ void lwg_maxpool2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int OH, int OW, int C4) {
     const size_t total = (size_t)B * OH * OW * C4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -507,7 +494,13 @@ __global__ void lwg_maxpool2_fwd_kernel(const float* __restrict__ x, float* __re
         const floatx4 a = xb[0], bb = xb[C4], cc = xb[(size_t)2 * OW * C4], d = xb[(size_t)2 * OW * C4 + C4];
         floatx4 r;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = fmaxf(fmaxf(a[k], bb[k]), fmaxf(cc[k], d[k]));
+        for (int k = 0; k < 4; ++k) {
+            float m = a[k];
+            if (bb[k] > m) m = bb[k];
+            if (cc[k] > m) m = cc[k];
+            if (d[k] > m) m = d[k];
+            r[k] = m;
+        }
         reinterpret_cast<floatx4*>(y)[i] = r;
     }
 }

@@ -605,12 +605,12 @@ def crop_resize_bwd(dy, box, in_hw):
 
 
 def prelu(x, slope, res=None):
-    y = torch.where(x >= 0, x, x * slope)
+    y = torch.where(x > 0, x, x * slope)
     return y if res is None else res + y
 
 
 def prelu_bwd(x, slope, dy):
-    return torch.where(x >= 0, dy, dy * slope)
+    return torch.where(x > 0, dy, dy * slope)
 
 
 def install(monkeypatch):
