@@ -608,6 +608,32 @@ int lwg_png_deflate_u8(const uint8_t* u8, int B, int H, int W, int rows_per_segm
                        lwg_stream_t stream);
 size_t lwg_png_stream_capacity(int H, int W, int rows_per_segment);
 size_t lwg_png_deflate_ws_bytes(int B, int H, int W, int rows_per_segment);
+/* lwg_jpeg_scan_u8: the entropy-coded scan of a baseline JPEG frame, encoded on the device (csrc/jpeg_scan.hip; opt-in through
+ * output.FrameWriter(encoder="jpeg" | "mjpeg")).  u8 (B,H,W,3) uint8 RGB as lwg_frames_to_u8(bgr = 0) writes it (H != W allowed) -> scans
+ * (B, capacity) uint8, nbytes (B,) int32: frame b's scan, with its restart markers and without the file headers and EOI, is
+ * scans[b * capacity .. + nbytes[b]), capacity = lwg_jpeg_scan_capacity(H, W, mcus_per_segment); bytes behind nbytes[b] are not written.
+ * qtab: HOST pointer, 128 entries: the luminance then the chrominance quantisation table, natural (row-major) order - the quality rule
+ * lives in Python (output.jpeg_tables).  ws: lwg_jpeg_scan_ws_bytes(...) bytes of device memory, 16-byte aligned.  Two launches on
+ * `stream` (one workgroup per segment: pixels, DCT, codes, stuffing; then packing, markers and nbytes).  Integers only.
+ * Scan format (tests/jpegdev_emu.py is the definition and states every constant; the kernels equal it byte for byte; output.jpeg_from_scan
+ * puts SOI, APP0, DQT, SOF0, DHT, DRI, SOS in front and EOI behind):
+ *   Baseline sequential, 8 bit, three components Y Cb Cr at 4:4:4, ONE interleaved scan; MCU = one 8x8 block of each, raster order; H or W
+ *   not a multiple of 8 is padded by replicating the last row / column.  Restart interval = mcus_per_segment: a segment is that many
+ *   consecutive MCUs in raster order (it may span MCU rows; the last one is what is left), starts with DC predictors 0, ends with 1-bits to
+ *   the byte boundary, has 00 stuffed behind every FF, and segments are separated by FF D0+(k mod 8).
+ *   Colour: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16, clamped to 0..255, minus 128.  DCT: M[k][n] = rint(8192 a_k
+ *   cos((2n+1) k pi / 16)); columns T = (M X + 1024) >> 11, rows F = T M^T.  Coefficient: sign(F) ((|F| + Q 2^14) / (Q 2^15)), AC clamped to
+ *   +-1023.  Zigzag, DC difference, (run, size) symbols with ZRL and EOB under the four FIXED Annex K Huffman tables, one's-complement
+ *   amplitudes.  Hence capacity = MCUs x 3 x 208 x 2 + 2 (segments - 1): every coefficient with the longest code, every byte stuffed.
+ * hipErrorInvalidValue before any launch: NULL pointers, sizes <= 0 (or above 65 535: SOF0's fields), mcus_per_segment outside
+ * 1..lwg_jpeg_max_mcus_per_segment() (64: an MCU per lane) or above 65 535 (DRI's field), a table entry of 0, a capacity beyond int32, ws
+ * not 16-byte aligned.  The helpers are host-only and return 0 for such arguments. */
+int lwg_jpeg_scan_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint8_t* scans, int32_t* nbytes,
+                     lwg_stream_t stream);
+size_t lwg_jpeg_scan_capacity(int H, int W, int mcus_per_segment);
+size_t lwg_jpeg_scan_ws_bytes(int B, int H, int W, int mcus_per_segment);
+int lwg_jpeg_max_mcus_per_segment(void);
 int lwg_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int Cp, int P, lwg_stream_t stream);
 int lwg_nhwc_to_nchw_f32(const float* src, float* dst, int B, int C, int Cs, int P, lwg_stream_t stream);
 

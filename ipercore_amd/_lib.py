@@ -155,6 +155,10 @@ _SIGS = {
     "lwg_png_deflate_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
     "lwg_png_stream_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "lwg_png_deflate_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "lwg_jpeg_scan_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f, c_f]),
+    "lwg_jpeg_scan_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "lwg_jpeg_scan_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "lwg_jpeg_max_mcus_per_segment": (c_i, []),
     "lwg_morph_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_canny_f32": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                             ctypes.c_float, ctypes.c_float, c_f, c_f, c_f]),

@@ -85,6 +85,13 @@ class Imitator(object):
         self.temporal = bool(_opt_get(opt, "temporal", False))
         self.time_step = int(_opt_get(opt, "time_step", 1))
         self.png_encoder = str(_opt_get(opt, "png_encoder", "host"))      # output.FrameWriter's encoder: "host" (zlib threads) or "device"
+        # what inference writes: "png" (files; png_encoder decides who encodes), "jpeg" (files coded on the device) or "mjpeg" (ONE Motion-JPEG
+        # AVI file at output_fps - the reference's fuse_source_reference_output default); jpeg_quality: libjpeg's 1 .. 100
+        self.output_format = str(_opt_get(opt, "output_format", "png"))
+        if self.output_format not in ("png", "jpeg", "mjpeg"):
+            raise ValueError("opt.output_format must be 'png', 'jpeg' or 'mjpeg', not %r" % (self.output_format,))
+        self.jpeg_quality = int(_opt_get(opt, "jpeg_quality", 90))
+        self.output_fps = float(_opt_get(opt, "output_fps", 25))
         self.temporal_fifo = None
         self.primary_ids = 0                      # which source's camera / shape drives the target (Swapper sets it)
         self._create_networks()
@@ -293,6 +300,12 @@ class Imitator(object):
             self.first_cam = tgt[0:1, 0:3].clone()
         return tgt
 
+    def _frame_writer(self, output_dir, prefix):
+        from .output import FrameWriter
+        if self.output_format == "png":
+            return FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
+        return FrameWriter(output_dir, prefix=prefix, encoder=self.output_format, quality=self.jpeg_quality, fps=self.output_fps)
+
     @torch.no_grad()
     def inference(self, tgt_smpls, cam_strategy="smooth", output_dir="", prefix="pred_", use_selected_f2pts=False,
                   visualizer=None, verbose=True):
@@ -301,16 +314,14 @@ class Imitator(object):
         if self.temporal:
             preds = self.synthesize_temporal(tgt, cam_strategy, use_selected_f2pts=use_selected_f2pts)
             if output_dir:
-                from .output import FrameWriter
-                writer = FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
+                writer = self._frame_writer(output_dir, prefix)
                 writer.submit(preds, 0)
                 return writer.close()
             preds = preds.cpu().numpy()
             return [preds[i] for i in range(preds.shape[0])]
         if output_dir:
             # device-side uint8 conversion + pinned async D2H + threaded PNG encoding: the frame loop never waits for disk
-            from .output import FrameWriter
-            writer = FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
+            writer = self._frame_writer(output_dir, prefix)
             for s in range(0, tgt.shape[0], self.frame_batch):
                 writer.submit(self.synthesize(tgt[s:s + self.frame_batch], cam_strategy, t0=s, use_selected_f2pts=use_selected_f2pts), s)
             return writer.close()

@@ -1325,6 +1325,39 @@ def png_deflate(u8, rows_per_segment=16):
     return streams, nbytes
 
 
+def jpeg_max_mcus_per_segment():
+    """The largest restart interval ``jpeg_scan`` takes (include/lwg_hip.h lwg_jpeg_max_mcus_per_segment)."""
+    return int(_lib.lib().lwg_jpeg_max_mcus_per_segment())
+
+
+def jpeg_scan(u8, quality=90, mcus_per_segment=None):
+    """(B,H,W,3) uint8 RGB device frames -> (scans (B, capacity) uint8, nbytes (B,) int32): scans[b, :nbytes[b]] is the entropy-coded scan of
+    frame b's baseline JPEG (4:4:4, restart interval ``mcus_per_segment`` MCUs, default min(ceil(W / 8), the largest); include/lwg_hip.h
+    lwg_jpeg_scan_u8; ``output.jpeg_from_scan`` wraps it into a file).  capacity is the worst case, several times the raw frame: copy
+    prefixes.  Bytes behind nbytes[b] are not written."""
+    if not u8.is_cuda:
+        raise RuntimeError("jpeg_scan needs a device tensor: there is no CPU fallback")
+    if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
+        raise ValueError("jpeg_scan takes a (B,H,W,3) uint8 tensor")
+    from .output import jpeg_tables
+    luma, chroma = jpeg_tables(quality)
+    B, H, W, _ = u8.shape
+    lib = _lib.lib()
+    ri = int(mcus_per_segment) if mcus_per_segment is not None else min((W + 7) // 8, lib.lwg_jpeg_max_mcus_per_segment())
+    cap = lib.lwg_jpeg_scan_capacity(H, W, ri)
+    nws = lib.lwg_jpeg_scan_ws_bytes(max(B, 1), H, W, ri)
+    if cap == 0 or nws == 0:
+        raise ValueError(f"jpeg_scan: no encoding for {B} frames of {H} x {W} in segments of {ri} MCUs (1 .. {lib.lwg_jpeg_max_mcus_per_segment()})")
+    scans = torch.empty(B, cap, device=u8.device, dtype=torch.uint8)
+    nbytes = torch.empty(B, device=u8.device, dtype=torch.int32)
+    if B == 0:
+        return scans, nbytes
+    ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
+    _lib.check(lib.lwg_jpeg_scan_u8(_ptr(u8.contiguous(), torch.uint8), B, H, W, bytes(luma) + bytes(chroma), ri, _ptr(ws, torch.uint8),
+                                    _ptr(scans, torch.uint8), _ptr(nbytes, torch.int32), _stream()), "lwg_jpeg_scan_u8")
+    return scans, nbytes
+
+
 # ---------------------------------------------------------------------------------------------- backward of the convs
 def conv2d_wgrad(x0, spec, dy, x1=None, out_hw=None, ycoff=0):
     """dW of the conv described by ``spec`` for inputs x0 (x1) and output gradient dy (laid out like the forward y) ->

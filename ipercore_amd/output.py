@@ -16,9 +16,16 @@ and their lengths take the pinned-copy path, and a host thread only adds the chu
 The files are larger or smaller than the host encoder's depending on content (no matches: at least one bit per byte); they decode to the same
 pixels.
 
+``FrameWriter(encoder="jpeg" | "mjpeg")`` (opt-in; ``opt.output_format`` of the runners) writes lossy frames instead: ``lwg_jpeg_scan_u8`` codes each
+frame's baseline JPEG scan on the device (4:4:4, fixed Annex K Huffman tables, restart segments; include/lwg_hip.h), only the CODED bytes cross
+PCIe (the lengths first, then - from the helper thread that waits for them - the used prefix of every frame's buffer), and a host thread puts
+the constant headers in front (``jpeg_from_scan``).  ``"jpeg"`` writes ``"{prefix}{t:0>8}.jpg"`` files, ``"mjpeg"`` ONE Motion-JPEG AVI file
+(``MjpegAviWriter``: the container is ``struct.pack`` on the host, no codec library).
+
 File names are the reference's: ``"{prefix}{t:0>8}.png"`` (imitator.py:369).  Pixels on disk are RGB, exactly what
 ``cv2.imwrite`` stores for the BGR array the reference hands it.
 """
+import functools
 import os
 import queue
 import struct
@@ -63,20 +70,192 @@ def encode_png(path, hwc_u8, compress_level=1):
     return path
 
 
+# ---- JPEG: the tables and the file around a device-coded scan (include/lwg_hip.h lwg_jpeg_scan_u8) ---------------------------------------------
+# Annex K.1 / K.2 quantisation tables, natural (row-major) order
+_JPEG_Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_JPEG_Q_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# Annex K.3 - K.6 Huffman tables as a DHT segment carries them: (class << 4 | id, codes per length 1 .. 16, symbols); the kernels hold the same
+# lists (csrc/lwg_jpeg_code.h)
+_JPEG_DHT = (
+    (0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d), bytes.fromhex(
+        "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+        "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+        "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")),
+    (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), bytes.fromhex(
+        "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445464748494a"
+        "535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+        "c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")),
+)
+
+
+@functools.lru_cache(maxsize=None)
+def jpeg_tables(quality):
+    """quality 1 .. 100 -> (luminance, chrominance) quantisation tables, 64 ints each in natural order: the Annex K tables scaled by libjpeg's
+    rule (``jpeg_quality_scaling``), clamped to the baseline range 1 .. 255."""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError("jpeg quality must be in 1 .. 100, not %r" % (quality,))
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(tuple(min(255, max(1, (b * s + 50) // 100)) for b in base) for base in (_JPEG_Q_LUMA, _JPEG_Q_CHROMA))
+
+
+def _jpeg_marker(code, body):
+    return struct.pack(">BBH", 0xFF, code, len(body) + 2) + body
+
+
+@functools.lru_cache(maxsize=64)
+def jpeg_headers(w, h, quality, mcus_per_segment):
+    """Everything in front of the scan - SOI, APP0 JFIF, two DQT, SOF0 (8 bit, h x w, three components 1x1), four DHT, DRI, SOS: constant per
+    (w, h, quality, restart interval), built once."""
+    w, h, ri = int(w), int(h), int(mcus_per_segment)
+    if not (0 < w <= 65535 and 0 < h <= 65535 and 0 < ri <= 65535):
+        raise ValueError("jpeg: sizes and the restart interval are 16-bit fields")
+    out = [b"\xff\xd8", _jpeg_marker(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    for tq, table in enumerate(jpeg_tables(quality)):
+        out.append(_jpeg_marker(0xDB, bytes([tq]) + bytes(table[k] for k in _JPEG_ZIGZAG)))
+    out.append(_jpeg_marker(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    for tc_th, bits, vals in _JPEG_DHT:
+        out.append(_jpeg_marker(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals)))
+    out.append(_jpeg_marker(0xDD, struct.pack(">H", ri)))
+    out.append(_jpeg_marker(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return b"".join(out)
+
+
+def jpeg_from_scan(scan, w, h, quality, mcus_per_segment):
+    """The entropy-coded scan of a (h, w) frame (``ops.jpeg_scan``: bytes, or a uint8 array) -> the bytes of the JFIF file: the headers, the
+    scan, EOI.  The host's share of the device encoder: one concatenation."""
+    return jpeg_headers(int(w), int(h), int(quality), int(mcus_per_segment)) + bytes(scan) + b"\xff\xd9"
+
+
+class MjpegAviWriter(object):
+    """ONE RIFF AVI file of JPEG frames (Motion-JPEG): ``hdrl`` (``avih``, one ``strl``: ``strh`` vids / MJPG, ``strf`` BITMAPINFOHEADER), a
+    ``movi`` list of ``00dc`` chunks - each a complete JFIF frame, padded to even length - and ``idx1``.  ``add(index, data)`` may be called
+    from any thread in any order: one writer thread with a reorder buffer writes the frames in index order (0, 1, ...).  ``close()`` writes the
+    index, patches the sizes and frame counts and returns ``[path]``.  AVI 1.0 sizes are 32 bits: an error is raised before the file would
+    exceed ``MAX_BYTES`` (OpenDML is not written)."""
+
+    MAX_BYTES = 2 ** 31 - 1
+    _HDRL = 4 + (8 + 56) + (12 + (8 + 56) + (8 + 40))          # bytes of the hdrl list's data
+    _MOVI = 12 + 8 + _HDRL                                      # file offset of the movi LIST chunk
+
+    def __init__(self, path, w, h, fps=25):
+        self.path, self.w, self.h, self.fps = path, int(w), int(h), float(fps)
+        if self.w <= 0 or self.h <= 0 or not self.fps > 0:
+            raise ValueError("MjpegAviWriter: width, height and fps must be positive")
+        self._fp = open(path, "wb")
+        self._fp.write(self._header(0, 0, 0, 0))
+        self._pos = self._MOVI + 12
+        self._index = []               # (offset from the 'movi' fourcc, bytes) per frame
+        self._largest = 0
+        self._pending = {}
+        self._next = 0
+        self._closing = False
+        self._error = None
+        self._cv = threading.Condition()
+        self._thread = threading.Thread(target=self._run, daemon=True)
+        self._thread.start()
+
+    def _header(self, frames, movi_bytes, riff_bytes, largest):
+        usec = int(round(1e6 / self.fps))
+        rate, scale = int(round(self.fps * 1000)), 1000
+        avih = struct.pack("<14I", usec, 0, 0, 0x10, frames, 0, 1, largest, self.w, self.h, 0, 0, 0, 0)           # 0x10: AVIF_HASINDEX
+        strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, frames, largest, 0xFFFFFFFF, 0, 0, 0, self.w, self.h)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.w, self.h, 1, 24, b"MJPG", self.w * self.h * 3, 0, 0, 0, 0)
+        strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh \
+            + b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"LIST" + struct.pack("<I", 4 + 8 + len(avih) + len(strl)) + b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + strl
+        assert len(hdrl) == 8 + self._HDRL
+        return b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", movi_bytes) + b"movi"
+
+    def _run(self):
+        try:
+            while True:
+                with self._cv:
+                    while self._next not in self._pending and not self._closing:
+                        self._cv.wait()
+                    if self._next not in self._pending:
+                        return
+                    data = self._pending.pop(self._next)
+                pad = len(data) & 1
+                # what the file would come to with this frame, its index entry and the index chunk's header
+                if self._pos + 8 + len(data) + pad + 8 + 16 * (len(self._index) + 1) > self.MAX_BYTES:
+                    raise RuntimeError("MjpegAviWriter: %s would exceed %d bytes with frame %d (AVI 1.0 sizes are 32 bits; OpenDML is not written)"
+                                       % (self.path, self.MAX_BYTES, self._next))
+                self._fp.write(b"00dc" + struct.pack("<I", len(data)) + data + b"\x00" * pad)
+                self._index.append((self._pos - (self._MOVI + 8), len(data)))
+                self._largest = max(self._largest, len(data))
+                self._pos += 8 + len(data) + pad
+                with self._cv:
+                    self._next += 1
+        except Exception as e:
+            with self._cv:
+                self._error = e
+                self._pending.clear()
+
+    def add(self, index, data):
+        """Frame ``index`` (0-based, every index once) = the bytes of a complete JPEG file."""
+        with self._cv:
+            if self._error is not None:
+                raise self._error
+            if self._closing:
+                raise RuntimeError("MjpegAviWriter: closed")
+            if index < self._next or index in self._pending:
+                raise ValueError("MjpegAviWriter: frame %d was already added" % index)
+            self._pending[int(index)] = bytes(data)
+            self._cv.notify_all()
+
+    def close(self):
+        with self._cv:
+            self._closing = True
+            self._cv.notify_all()
+        self._thread.join()
+        try:
+            if self._error is not None:
+                raise self._error
+            if self._pending:
+                raise RuntimeError("MjpegAviWriter: frame %d is missing (%d later frames were added)" % (self._next, len(self._pending)))
+            n = len(self._index)
+            self._fp.write(b"idx1" + struct.pack("<I", 16 * n) + b"".join(struct.pack("<4sIII", b"00dc", 0x10, o, s) for o, s in self._index))
+            end = self._pos + 8 + 16 * n
+            self._fp.seek(0)
+            self._fp.write(self._header(n, self._pos - (self._MOVI + 8), end - 8, self._largest))
+        finally:
+            self._fp.close()
+        return [self.path]
+
+
 class FrameWriter(object):
-    """Asynchronous ``(B,3,S,S)`` fp32 device frames -> PNG files.  ``submit`` returns immediately; ``close`` joins."""
+    """Asynchronous ``(B,3,S,S)`` fp32 device frames -> PNG files (encoder "host" | "device"), JPEG files ("jpeg") or one Motion-JPEG AVI file
+    ("mjpeg").  ``submit`` returns immediately; ``close`` joins."""
 
     DEVICE_WORKERS = 4          # encoder="device": a worker checksums and writes (zlib.crc32 and the file write release the GIL); not sized by the machine
     ROWS_PER_SEGMENT = 16       # encoder="device": scanlines per deflate block (include/lwg_hip.h lwg_png_deflate_u8)
+    RING = 4                    # batches between the producer and the files (pinned buffers of the PNG encoders)
+    CODED_RING = 8              # encoder="jpeg" | "mjpeg": a batch passes two copies and their helper thread before a worker sees it; with 4 the
+                                # producer waits for the per-file form (GPU side 1 069 against 1 165 frames/s, profiles/jpeg_device_ab*.txt)
 
-    def __init__(self, output_dir, prefix="pred_", workers=None, ring=4, compress_level=1, encoder="host"):
-        if encoder not in ("host", "device"):
-            raise ValueError("encoder must be 'host' or 'device', not %r" % (encoder,))
+    def __init__(self, output_dir, prefix="pred_", workers=None, ring=None, compress_level=1, encoder="host", quality=90, fps=25):
+        if encoder not in ("host", "device", "jpeg", "mjpeg"):
+            raise ValueError("encoder must be 'host', 'device', 'jpeg' or 'mjpeg', not %r" % (encoder,))
         self.encoder = encoder
+        self.coded = encoder in ("jpeg", "mjpeg")          # the device codes JPEG scans; only their used bytes are copied
+        self.quality, self.fps = int(quality), fps
+        if self.coded:
+            jpeg_tables(self.quality)                      # (a quality outside 1 .. 100 raises here)
+        self._avi = None                                   # encoder="mjpeg": the MjpegAviWriter, opened by the first submit (it needs the frame size)
+        self._t_first = None
+        ring = int(ring or (self.CODED_RING if self.coded else self.RING))
+        self._slots = threading.Semaphore(ring)            # coded batches in flight (their device buffers are large: capacity is the worst case)
+        self._pool, self._pool_lock = [], threading.Lock() # pinned buffers of the coded bytes
         self.output_dir, self.prefix = output_dir, prefix
         os.makedirs(output_dir, exist_ok=True)
         self.compress_level = compress_level
-        if encoder == "device":
+        if encoder != "host":
             self.workers = int(workers or self.DEVICE_WORKERS)
         else:
             self.workers = int(workers or min(32, max(2, (os.cpu_count() or 4) // 2)))     # (64 measured: the launching thread loses the GIL more often - 869 against 1 090 frames/s on the GPU side, 802 against 865 end to end)
@@ -103,6 +282,21 @@ class FrameWriter(object):
             try:
                 batch["ready"].wait()                      # the D2H copy of this batch has landed
                 t = batch["t0"] + i
+                if self.coded:
+                    if batch["error"] is not None:
+                        raise batch["error"]
+                    a, n = batch["offs"][i], int(batch["nbytes"][i])
+                    data = jpeg_from_scan(batch["host"].numpy()[a:a + n], batch["w"], batch["h"], self.quality, batch["ri"])
+                    if self._avi is not None:
+                        path = self._avi.path
+                        self._avi.add(t - self._t_first, data)
+                    else:
+                        path = os.path.join(self.output_dir, self.prefix + "{:0>8}.jpg".format(t))
+                        with open(path, "wb") as fp:
+                            fp.write(data)
+                    with self._cv:
+                        self.paths[t] = path
+                    continue
                 path = os.path.join(self.output_dir, self.prefix + "{:0>8}.png".format(t))
                 if batch["nbytes"] is None:
                     encode_png(path, batch["host"].numpy()[i], self.compress_level)
@@ -119,7 +313,13 @@ class FrameWriter(object):
                 with self._cv:
                     batch["left"] -= 1
                     if batch["left"] == 0:
-                        self._free.put(batch["host"])
+                        if not self.coded:
+                            self._free.put(batch["host"])
+                        else:
+                            if batch["host"] is not None:
+                                with self._pool_lock:
+                                    self._pool.append(batch["host"])
+                            self._slots.release()
                     self._cv.notify_all()
 
     def _host_buffer(self, shape, pinned):
@@ -138,10 +338,83 @@ class FrameWriter(object):
             event.synchronize()
         batch["ready"].set()
 
+    def _wait_coded(self, batch, event, scans):
+        """The helper thread of a coded batch: the lengths have landed -> copy the used prefix of every frame's scan buffer, behind each other,
+        into one pinned buffer (on the copy stream, never from the producer thread), wait for them, release the device buffer."""
+        try:
+            event.synchronize()
+            n = [int(v) for v in batch["nbytes"]]
+            if min(n) < 0 or max(n) > scans.shape[1]:
+                raise RuntimeError("jpeg_scan returned lengths outside its buffers: %r" % (n,))
+            offs = [0]
+            for v in n:
+                offs.append(offs[-1] + ((v + 15) & ~15))
+            total = max(offs[-1], 16)
+            host = None
+            with self._pool_lock:
+                for k, buf in enumerate(self._pool):
+                    if buf.numel() >= total:
+                        host = self._pool.pop(k)
+                        break
+            if host is None:
+                host = torch.empty(max(1 << 20, 1 << (total - 1).bit_length()), dtype=torch.uint8, pin_memory=True)
+            batch["host"], batch["offs"] = host, offs
+            with torch.cuda.device(scans.device), torch.cuda.stream(self._copy_stream):
+                for i, v in enumerate(n):
+                    if v:
+                        host[offs[i]:offs[i] + v].copy_(scans[i, :v], non_blocking=True)
+                landed = torch.cuda.Event()
+                landed.record(self._copy_stream)
+            landed.synchronize()
+        except Exception as e:                             # every frame of the batch reports it
+            batch["error"] = e
+        finally:
+            del scans
+            batch["ready"].set()
+
+    def _submit_coded(self, pred, t0):
+        from . import ops
+        B, H, W = pred.shape[0], pred.shape[2], pred.shape[3]
+        self._slots.acquire()                              # blocks while ``ring`` batches are still being copied or written
+        try:
+            ri = min((W + 7) // 8, ops.jpeg_max_mcus_per_segment())
+            scans, nbytes = ops.jpeg_scan(ops.frames_to_u8(pred.contiguous()), self.quality, ri)
+            nbytes_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(device=pred.device)
+            if self.encoder == "mjpeg" and self._avi is None:
+                self._t_first = int(t0)
+                self._avi = MjpegAviWriter(os.path.join(self.output_dir, self.prefix + "video.avi"), W, H, self.fps)
+            produced = torch.cuda.Event()
+            produced.record(torch.cuda.current_stream(pred.device))
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(produced)
+                nbytes_host.copy_(nbytes, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record(self._copy_stream)
+            nbytes.record_stream(self._copy_stream)
+            scans.record_stream(self._copy_stream)
+        except Exception:
+            self._slots.release()
+            raise
+        batch = {"host": None, "offs": None, "t0": int(t0), "left": B, "ready": threading.Event(), "nbytes": nbytes_host, "h": H, "w": W, "ri": ri,
+                 "error": None}
+        with self._cv:
+            self._submitted += B
+        threading.Thread(target=self._wait_coded, args=(batch, event, scans), daemon=True).start()
+        for i in range(B):
+            self._jobs.put((batch, i))
+
     # ---- producer side ---------------------------------------------------------------------------------------
     def submit(self, pred, t0):
         """pred: (B,3,S,S) fp32 frames t0 .. t0+B-1, on the device (or on the CPU: tests)."""
         B = pred.shape[0]
+        if self.coded:
+            if not pred.is_cuda:
+                raise RuntimeError("FrameWriter(encoder=%r) needs device frames: there is no CPU fallback" % (self.encoder,))
+            if B:
+                self._submit_coded(pred, t0)
+            return
         event = None
         nbytes_host = None
         if self.encoder == "device" and not pred.is_cuda:
@@ -188,6 +461,13 @@ class FrameWriter(object):
             self._jobs.put(None)
         for t in self._threads:
             t.join()
+        if self._avi is not None:
+            try:
+                video = self._avi.close()
+            except Exception as e:
+                self._errors.append(e)
         if self._errors:
             raise self._errors[0]
+        if self._avi is not None:
+            return video
         return [self.paths[t] for t in sorted(self.paths)]
