@@ -336,6 +336,23 @@ int lwg_colsum_nhwc_f32(const float* x, size_t rows, int C, float* out, float* w
  * a launch outside the contract. */
 size_t lwg_conv2d_wgrad_winograd_ws_floats(const LwgConvArgs* args);
 int lwg_conv2d_wgrad_winograd_f32(const LwgConvArgs* args, const float* dy, float* ws, float* dw, int cin, int nout, lwg_stream_t stream);
+/* The weight gradient with bf16 OPERANDS (csrc/conv_wgrad_bf16.hip): x and dy are read as fp32, rounded to bf16 in registers (round to nearest
+ * even on finite values - torch's tensor.bfloat16()), multiplied on v_mfma_f32_32x32x16_bf16 and accumulated in fp32; neither operand exists as
+ * bf16 in memory.  bf16-operand grade: not the bits of lwg_conv2d_wgrad_unpacked_f32 - every product is off by at most (2^-7 + 2^-16) |x dy|, the
+ * accumulation of T = M terms by at most 2 (T + 8) 2^-24 sum |x^ dy^| (tests/wgradbf16_emu.py; measured: <= 0.94 of the first and
+ * <= 0.05 of the second bound, relative L2 against fp64 2.2e-3 - 2.5e-3 where the fp32 kernel has 1e-7 - 3e-7: table in DESIGN.md 3.10c) -, deterministic (slabs added in slab order, no float atomics).  Opt-in: nothing
+ * selects it by default.
+ * Arguments as for lwg_conv2d_wgrad_unpacked_f32 (`args` is the FORWARD launch description; dw (D0, D1, KH, KW), transposed, kidx, cin, nout, db as
+ *   there - db is the column sums of the fp32 dy values as loaded, before rounding, from the same two launches).  The contract: fp32 x0 (B,H,W,C0) /
+ *   x1 (B,H,W,C1), C0 % 32 == 0, C1 % 32 == 0 (0: no x1), N % 64 == 0; any tap list (1 .. LWG_MAX_TAPS) and stride >= 1; dy dense: omul 1,
+ *   ooy = oox = 0, YH == OH, YW == OW, M == B OH OW, column n at ycoff + n with ycoff + N <= YC, YC % 4 == 0, ycoff % 4 == 0; x0, x1 and dy each
+ *   < 3 GiB (32-bit buffer offsets).  ws: lwg_conv2d_wgrad_bf16_ws_floats(args) floats: a function of the launch shape and the CU count of the
+ *   current device (queried as for the Winograd form; 256 CUs where no device answers); 0 for NULL or a launch outside the contract.
+ * Returns 0, or 1 (hipErrorInvalidValue) - checked on the host before any launch - for a NULL pointer (args, dy, ws, dw, kidx), cin / nout out of
+ * range (< 1, beyond C0 + C1 / N or beyond dw's D0 / D1), a kidx entry outside KH KW or a launch outside the contract. */
+size_t lwg_conv2d_wgrad_bf16_ws_floats(const LwgConvArgs* args);
+int lwg_conv2d_wgrad_bf16_f32(const LwgConvArgs* args, const float* dy, float* ws, float* dw, int D0, int D1, int KH, int KW,
+                              int transposed, const int* kidx, int cin, int nout, float* db, lwg_stream_t stream);
 
 /* Elementwise / normalisation pieces of the personalization step and their backward (csrc/train_ops.hip); NHWC fp32.
  *   act codes: LWG_ACTIVATION_* plus 4 = LeakyReLU(0.2) (discriminators/patch_dis.py:33-47).

@@ -103,6 +103,8 @@ _SIGS = {
     "lwg_colsum_nhwc_f32": (c_i, [c_f, ctypes.c_size_t, c_i, c_f, c_f, c_f]),
     "lwg_conv2d_wgrad_winograd_ws_floats": (ctypes.c_size_t, [ctypes.POINTER(LwgConvArgs)]),
     "lwg_conv2d_wgrad_winograd_f32": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f, c_f, c_i, c_i, c_f]),
+    "lwg_conv2d_wgrad_bf16_ws_floats": (ctypes.c_size_t, [ctypes.POINTER(LwgConvArgs)]),
+    "lwg_conv2d_wgrad_bf16_f32": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f, c_f] + [c_i] * 5 + [ctypes.POINTER(ctypes.c_int), c_i, c_i, c_f, c_f]),
     "lwg_act_bwd_f32": (c_i, [c_f, c_f, ctypes.c_size_t, c_i, c_f, c_f]),
     "lwg_norm_fwd_nhwc_f32": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_norm_bwd_nhwc_f32": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f]),

@@ -20,6 +20,7 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_direct.h"
+#include "lwg_wgrad_reduce.h"
 
 #define LWG_OOB_OFFSET 0xC0000000u
 
@@ -326,11 +327,7 @@ static void lwg_launch_slab_reduce(const float* part, int nsplit, size_t total, 
 // The slab reduction of a weight gradient fused with its un-packing: element i of the OUTPUT (tap, c, n; n fastest) is the sum
 // over the slices of slab[k(tap, c)][n] and lands at the parameter tensor's own position (nn.Conv2d (N, Cin, KH, KW), or
 // (Cin, N, KH, KW) for transposed = 1) - what lwg_wgrad_reduce_kernel + lwg_unpack_wgrad_f32 did in two launches and one extra
-// pass over dW (~150 launch pairs per training step).
-struct LwgUnpackMap {
-    int D1, KHW, transposed, ntaps, cin, cin_pad, nout, n_pad;
-    int kidx[LWG_MAX_TAPS];
-};
+// pass over dW (~150 launch pairs per training step).  struct LwgUnpackMap: lwg_wgrad_reduce.h.
 
 // element i of the output -> its slab offset (src) and parameter-tensor offset (dst).  Elements [total_w, total_w + nout) are the bias
 // gradient (slab row ntaps * cin_pad, returned with bias = true and dst = n) when the launch carries one.
@@ -598,19 +595,28 @@ extern "C" int lwg_conv2d_wgrad_nhwc_f32(const LwgConvArgs* pa, const float* dy,
 extern "C" int lwg_conv2d_wgrad_unpacked_f32(const LwgConvArgs* pa, const float* dy, float* ws, float* dw, int D0, int D1, int KH, int KW,
                                              int transposed, const int* kidx, int cin, int nout, float* db, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (!pa || !dw || !kidx || cin < 1 || nout < 1 || cin > pa->C0 + pa->C1 || nout > pa->N) return (int)hipErrorInvalidValue;
-    if ((transposed ? cin : nout) > D0 || (transposed ? nout : cin) > D1 || pa->ntaps < 1 || pa->ntaps > LWG_MAX_TAPS) return (int)hipErrorInvalidValue;
     LwgUnpackMap u;
-    u.D1 = D1; u.KHW = KH * KW; u.transposed = transposed; u.ntaps = pa->ntaps; u.cin = cin; u.cin_pad = pa->C0 + pa->C1;
-    u.nout = nout; u.n_pad = pa->N;
-    for (int i = 0; i < pa->ntaps; ++i) {
-        if (kidx[i] < 0 || kidx[i] >= KH * KW) return (int)hipErrorInvalidValue;
-        u.kidx[i] = kidx[i];
-    }
+    if (!dw || !lwg_wgrad_unpack_map_make(pa, D0, D1, KH, KW, transposed, kidx, cin, nout, &u)) return (int)hipErrorInvalidValue;
     int splits = 0;
     if (int e = lwg_wgrad_launch(pa, dy, ws, stream, &splits, db ? 1 : 0); e != 0) return e;
-    lwg_launch_slab_reduce_unpack(ws, splits, ((size_t)u.ntaps * u.cin_pad + 1) * u.n_pad, (size_t)u.ntaps * cin * nout, u, dw, db, stream);
+    lwg_wgrad_reduce_unpack(ws, splits, u, dw, db, stream);
     return (int)hipGetLastError();
+}
+
+bool lwg_wgrad_unpack_map_make(const LwgConvArgs* pa, int D0, int D1, int KH, int KW, int transposed, const int* kidx, int cin, int nout, LwgUnpackMap* u) {
+    if (!pa || !kidx || cin < 1 || nout < 1 || cin > pa->C0 + pa->C1 || nout > pa->N) return false;
+    if ((transposed ? cin : nout) > D0 || (transposed ? nout : cin) > D1 || pa->ntaps < 1 || pa->ntaps > LWG_MAX_TAPS) return false;
+    u->D1 = D1; u->KHW = KH * KW; u->transposed = transposed; u->ntaps = pa->ntaps; u->cin = cin; u->cin_pad = pa->C0 + pa->C1;
+    u->nout = nout; u->n_pad = pa->N;
+    for (int i = 0; i < pa->ntaps; ++i) {
+        if (kidx[i] < 0 || kidx[i] >= KH * KW) return false;
+        u->kidx[i] = kidx[i];
+    }
+    return true;
+}
+
+void lwg_wgrad_reduce_unpack(const float* ws, int splits, const LwgUnpackMap& u, float* dw, float* db, hipStream_t stream) {
+    lwg_launch_slab_reduce_unpack(ws, splits, ((size_t)u.ntaps * u.cin_pad + 1) * u.n_pad, (size_t)u.ntaps * u.cin * u.nout, u, dw, db, stream);
 }
 
 // out[c] = sum over rows of x (rows, C); ws: 64 * C floats.

@@ -228,10 +228,14 @@ def wgrad_conv_is_winograd(x0, spec, dy, x1, kh, kw):
 
 def wgrad_conv(x0, spec, dy, x1, kh, kw, cin, n, db=None):
     """nn.Conv2d weight gradient (N, Cin, kh, kw) of the launch ``spec``: on the device ONE reduction launch writes it in place
-    (ops.conv2d_wgrad_unpacked) - and the bias gradient into ``db`` (n,) when given; the host-logic tests take the two-step form."""
+    (ops.conv2d_wgrad_unpacked; ops.conv2d_wgrad_bf16 for the eligible launches under ops.WGRAD_PRECISION = "bf16") - and the bias gradient into
+    ``db`` (n,) when given; the host-logic tests take the two-step form."""
     if wgrad_conv_is_winograd(x0, spec, dy, x1, kh, kw):
         assert db is None, "the Winograd weight gradient carries no bias gradient (ops.colsum)"
         return ops.conv2d_wgrad_winograd(x0, spec, dy, torch.empty(n, cin, 3, 3, device=dy.device, dtype=torch.float32), cin, n, x1=x1)
+    if ops.WGRAD_PRECISION == "bf16" and ops._wgrad_bf16_use(x0, spec, dy, x1):          # bf16 operands, fp32 accumulation; db stays fused
+        return ops.conv2d_wgrad_bf16(x0, spec, dy, torch.empty(n, cin, kh, kw, device=dy.device, dtype=torch.float32), False, range(kh * kw), cin, n,
+                                     x1=x1, db=db)
     if dy.is_cuda:
         return ops.conv2d_wgrad_unpacked(x0, spec, dy, torch.empty(n, cin, kh, kw, device=dy.device, dtype=torch.float32), False,
                                          range(kh * kw), cin, n, x1=x1, db=db)
@@ -249,6 +253,8 @@ def wgrad_conv_transpose(x0, specs, dy, cin, n, adj_spec=None):
         g = torch.empty(cin, n, 4, 4, device=dy.device, dtype=torch.float32)           # all 16 positions are covered either way
         if adj_spec is not None:
             kidx = [ky * 4 + kx for py in (0, 1) for px in (0, 1) for ky, _ in _CT_TAPS[py] for kx, _ in _CT_TAPS[px]]   # pack_dgrad_conv_transpose's tap order
+            if ops.WGRAD_PRECISION == "bf16" and ops._wgrad_bf16_use(dy, adj_spec, x0):
+                return ops.conv2d_wgrad_bf16(dy, adj_spec, x0, g, False, kidx, n, cin)
             return ops.conv2d_wgrad_unpacked(dy, adj_spec, x0, g, False, kidx, n, cin)
         i = 0
         for py in (0, 1):

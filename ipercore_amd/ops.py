@@ -1389,14 +1389,19 @@ def conv2d_wgrad_unpacked(x0, spec, dy, dw, transposed, kidx, cin, nout, x1=None
 # "direct": every weight gradient on lwg_conv_wgrad_kernel.  "winograd": the 3x3 / stride 1 / pad 1 launches with both channel counts % 64 == 0
 # (_wgrad_wino_use) run lwg_conv2d_wgrad_winograd_f32 - dU = sum V^T Z, dw = G^T dU G: 16 products per 2x2 output tile and channel pair instead of
 # 36 (csrc/conv_wgrad_winograd.hip); fp32-grade, not the direct kernel's bits, bias gradient by ops.colsum.  Every other launch exactly as "direct".
+# "bf16" (entered through ``wgrad_mode``): the launches with C0 % 32 == 0, C1 % 32 == 0, N % 64 == 0 and a dense dy (_wgrad_bf16_use; any taps and
+# stride) run lwg_conv2d_wgrad_bf16_f32 - both fp32 operands rounded to bf16 in the kernel, v_mfma_f32_32x32x16_bf16, fp32 accumulation, the fused
+# bias gradient from the fp32 dy (csrc/conv_wgrad_bf16.hip); bf16-operand grade.  Every other launch exactly as "direct".
 WGRAD_PRECISION = "direct"
 
 
 class wgrad_precision(object):
-    """Context manager: ``with ops.wgrad_precision("winograd"): ...`` (trainers.TrainOpts.wgrad_precision)."""
+    """Context manager: ``with ops.wgrad_precision("winograd"): ...`` - the two fp32-grade modes, as before the bf16 mode existed (it keeps rejecting
+    every other name: tests/test_wgrad_winograd_cpu.py pins that); ``wgrad_mode`` takes all three."""
+    MODES = ("direct", "winograd")
 
     def __init__(self, mode):
-        assert mode in ("direct", "winograd")
+        assert mode in self.MODES
         self.mode = mode
 
     def __enter__(self):
@@ -1407,6 +1412,11 @@ class wgrad_precision(object):
     def __exit__(self, *exc):
         global WGRAD_PRECISION
         WGRAD_PRECISION = self.prev
+
+
+class wgrad_mode(wgrad_precision):
+    """The same switch with every value of trainers.TrainOpts.wgrad_precision: ``with ops.wgrad_mode("bf16"): ...`` (nests with ``wgrad_precision``)."""
+    MODES = ("direct", "winograd", "bf16")
 
 
 def _wgrad_wino_use(x0, spec, dy, x1=None):
@@ -1440,6 +1450,50 @@ def conv2d_wgrad_winograd(x0, spec, dy, dw, cin, nout, x1=None):
     _lib.check(_lib.lib().lwg_conv2d_wgrad_winograd_f32(a, _ptr(dy), _ptr(ws), _ptr(dw), cin, nout, _stream()), "lwg_conv2d_wgrad_winograd_f32")
     if CONV_HOOK is not None:
         CONV_HOOK(False, a.M, spec, EPI_NONE, {"kernels": 2, "kind": "wgrad_winograd"})
+    return dw
+
+
+def _wgrad_bf16_shapes_ok(xs, spec, dys, x1s=None):
+    """The shape part of lwg_conv2d_wgrad_bf16_f32's contract for x0 / dy / x1 of shapes xs / dys / x1s, launched as ``conv_args`` would (dy is the
+    whole output: ycoff 0): C0 % 32 == 0, C1 % 32 == 0, C0 + C1 == spec.Cin, N % 64 == 0, omul 1, dy (B, OH, OW, N) dense, every tensor < 3 GiB."""
+    if len(xs) != 4 or len(dys) != 4 or (x1s is not None and (len(x1s) != 4 or tuple(x1s[:3]) != tuple(xs[:3]))):
+        return False
+    C0, C1 = xs[3], 0 if x1s is None else x1s[3]
+    if min(xs) < 1 or min(dys) < 1 or C0 % 32 != 0 or C1 % 32 != 0 or C0 + C1 != spec.Cin or spec.N % 64 != 0 or not 1 <= spec.ntaps <= _lib.LWG_MAX_TAPS or \
+            spec.stride < 1 or spec.omul != 1 or spec.ooy != 0 or spec.oox != 0 or dys[0] != xs[0] or dys[3] != spec.N:
+        return False
+    return xs[0] * xs[1] * xs[2] * max(C0, C1) * 4 < 0xC0000000 and dys[0] * dys[1] * dys[2] * dys[3] * 4 < 0xC0000000
+
+
+def _wgrad_bf16_use(x0, spec, dy, x1=None):
+    """Launches lwg_conv2d_wgrad_bf16_f32 takes (its C contract): fp32 device tensors, C0 % 32 == 0, C1 % 32 == 0, N % 64 == 0, any tap list and stride,
+    dy dense (B, OH, OW, N) with omul 1, every tensor < 3 GiB.  The small-Cin first layers (Cin 4 .. 16) and the parity launches of a transposed
+    convolution (omul 2) are outside it."""
+    ts = (x0, dy) if x1 is None else (x0, dy, x1)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        return False
+    return _wgrad_bf16_shapes_ok(tuple(x0.shape), spec, tuple(dy.shape), None if x1 is None else tuple(x1.shape))
+
+
+def conv2d_wgrad_bf16(x0, spec, dy, dw, transposed, kidx, cin, nout, x1=None, out_hw=None, ycoff=0, db=None):
+    """``conv2d_wgrad_unpacked`` with bf16 operands and fp32 accumulation (lwg_conv2d_wgrad_bf16_f32: one slab launch + one reduction launch, the bias
+    gradient ``db`` - fp32 column sums of dy - from the same two) for a launch inside ``_wgrad_bf16_use``; bf16-operand grade, deterministic."""
+    a = conv_args(x0, spec, dy, x1=x1, out_hw=out_hw, ycoff=ycoff)
+    D0, D1, KH, KW = dw.shape
+    assert dw.is_contiguous() and len(kidx) == spec.ntaps
+    nws = _lib.lib().lwg_conv2d_wgrad_bf16_ws_floats(a)
+    if nws == 0:
+        raise ValueError("launch outside lwg_conv2d_wgrad_bf16_f32's contract (ops._wgrad_bf16_use)")
+    if db is not None:
+        assert db.is_contiguous() and db.dtype == torch.float32 and db.numel() == nout
+    if CONV_HOOK is not None:
+        CONV_HOOK(True, a.M, spec, EPI_NONE, None)
+    ws = torch.empty(nws, device=x0.device, dtype=torch.float32)
+    arr = (ctypes.c_int * spec.ntaps)(*[int(k) for k in kidx])
+    _lib.check(_lib.lib().lwg_conv2d_wgrad_bf16_f32(a, _ptr(dy), _ptr(ws), _ptr(dw), D0, D1, KH, KW, 1 if transposed else 0, arr, cin, nout,
+                                                    None if db is None else _ptr(db), _stream()), "lwg_conv2d_wgrad_bf16_f32")
+    if CONV_HOOK is not None:
+        CONV_HOOK(False, a.M, spec, EPI_NONE, {"kernels": 2, "kind": "wgrad_bf16"})
     return dw
 
 

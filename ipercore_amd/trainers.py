@@ -644,7 +644,11 @@ class TrainOpts(object):
     conv_precision = "winograd"
     # "direct": every weight gradient on the direct fp32 MFMA kernel.  "winograd" (opt-in): the 3 x 3 / stride 1 weight gradients with both
     # channel counts % 64 == 0 in F(2x2,3x3) Winograd form (ops.wgrad_precision, csrc/conv_wgrad_winograd.hip): fp32-grade,
-    # not the direct kernel's bits; their bias gradients come from the column-sum kernel
+    # not the direct kernel's bits; their bias gradients come from the column-sum kernel.  "bf16" (opt-in): every weight gradient with input
+    # channel counts % 32 == 0 and N % 64 == 0 - any taps and stride, the transposed convolutions' one-launch adjoint form included
+    # (ops._wgrad_bf16_use) - rounds both fp32 operands to bf16 in the kernel, multiplies on the bf16 matrix pipe and accumulates in fp32
+    # (csrc/conv_wgrad_bf16.hip, ops.wgrad_mode): bf16-operand grade, deterministic, the fused bias gradient stays fp32.  A captured trainer
+    # re-captures its step when the value changes
     wgrad_precision = "direct"
     # "2x2": the step's Winograd launches are F(2x2,3x3) ones, whole or split over K.  "4x4" (opt-in): the eligible forward and data-gradient
     # launches with Cin >= ops.WINO4_MIN_CIN that the library's plan takes (lwg_conv2d_winograd4_plan) run the F(4x4,3x3) kernel - 2.25
@@ -919,7 +923,7 @@ class LWGTrainer(object):
         prev = ops.PANEL_CACHE, ops.BRANCH_STREAM
         ops.PANEL_CACHE, ops.BRANCH_STREAM = getattr(self, "_panel_cache", None), getattr(self, "_branch_stream", None)
         try:
-            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_precision(getattr(self.opts, "wgrad_precision", "direct")), \
+            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_mode(getattr(self.opts, "wgrad_precision", "direct")), \
                     ops.train_conv_tiles(tiles):
                 if self._graphable():
                     return self._graph_step()
