@@ -557,6 +557,12 @@ int lwg_encode_fim_f32(const int32_t* fim, const float* map_fn, int B, int S, in
  * shapedirs (nv,3,nbeta); posedirs ((nj-1)*9, nv*3); J_regressor (nj,nv); parents (nj) int32;
  * lbs_weights (nv,nj); offsets NULL | (nv,3) | (B,nv,3); links NULL | (nlinks,2) int32 (to, from).
  * ws: lwg_smpl_lbs_ws_floats(B,nv,nj) floats.
+ * 1 <= B <= 65535 (B rides in grid.y), 2 <= nj <= 64, beta_stride == nbeta; anything else, or a NULL among the
+ * required pointers, returns hipErrorInvalidValue before anything is launched or written.  cam NULL (or j2d NULL):
+ * j2d is not written.  parents[j] < j and link ids in [0, nv) are the caller's to keep.
+ * A rotation vector whose three components all equal -1e-8f makes rv + 1e-8 vanish: the angle is 0, the axis
+ * -1e-8 / 0, and that joint's rotation is NaN, which spreads through the frame's vertices and joints - as in the
+ * reference (rotations.py:318-332).
  * ------------------------------------------------------------------------------------------------ */
 size_t lwg_smpl_lbs_ws_floats(int B, int nv, int nj);
 int lwg_smpl_lbs_f32(const float* pose, int pose_stride, const float* beta, int beta_stride, int nbeta,

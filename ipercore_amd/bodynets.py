@@ -77,8 +77,8 @@ class SMPLH(nn.Module):
         return theta.contiguous()
 
     def _links_2d(self, links_ids, device):
-        """links_ids (n, 2|3) -> (n, 2) int32 (from, to) pairs shared by the whole batch (base_smpl.py:44-45: every row is
-        applied).  A per-batch (B, nv, 3) tensor whose rows are all the same sample - what FlowComposition.forward builds with
+        """links_ids (n, 2|3) -> (n, 2) int32 (to, from) pairs shared by the whole batch: column 0 is the vertex written, column 1
+        the vertex read, as the kernel and base_smpl.py:44-45 take them (every row is applied).  A per-batch (B, nv, 3) tensor whose rows are all the same sample - what FlowComposition.forward builds with
         ``links_ids.expand(bs, ns, nv, c)`` (flowcomposition.py:695-701) - reduces to the rows whose has_linked flag is 1
         (base_smpl.py:47-49); genuinely different per-sample links return None (``forward`` then skins row by row)."""
         ids = torch.as_tensor(links_ids)

@@ -235,8 +235,8 @@ extern "C" int lwg_smpl_lbs_f32(const float* pose, int pose_stride, const float*
                                 int nv, int nj, float* verts, float* j3d, float* j2d, float* ws, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!pose || !beta || !v_template || !shapedirs || !posedirs || !J_regressor || !parents || !lbs_weights || !verts || !j3d ||
-        !ws || B <= 0 || nv <= 0 || nj <= 1 || nj > LWG_MAX_JOINTS || beta_stride != nbeta)
-        return (int)hipErrorInvalidValue;
+        !ws || B <= 0 || B > 65535 || nv <= 0 || nj <= 1 || nj > LWG_MAX_JOINTS || beta_stride != nbeta)
+        return (int)hipErrorInvalidValue;                     // B rides in grid.y of the joints and blend kernels
     const int nv3 = nv * 3, npf = (nj - 1) * 9;
     float* v_shaped = ws;
     float* vraw = v_shaped + (size_t)B * nv3;
