@@ -304,6 +304,23 @@ int lwg_conv_transpose4_winograd24_f32(const LwgConvArgs* args, lwg_stream_t str
  * per fp32 product, fp32 accumulation; dropped terms < 2^-23 |a b|.  Same contract and restrictions as the bf16 entry point. */
 int lwg_conv2d_nhwc_f32_split(const LwgConvArgs* args, lwg_stream_t stream);
 
+/* fp32 convolution with ONE bf16 product per multiply ("bf16 operands", csrc/conv_igemm_bf16op.hip; opt-in, ops.conv_precision("bf16_operands")):
+ * y = epilogue(conv(bf16(x), bf16(w)) accumulated in fp32 + bias) - both fp32 operands are rounded to bf16 (round to nearest even) in the kernel,
+ * the products run on the bf16 matrix pipe, everything else stays fp32.  Launch description of lwg_conv2d_nhwc_f32 with args->w = THAT entry
+ * point's fp32 panel [K/4][N][4]: any taps (1 .. LWG_MAX_TAPS), any stride, omul / ooy / oox, any channel slice ycoff % 4 == 0 of a YC % 4 == 0
+ * output; xdt = ydt = LWG_DT_F32; one or two inputs with (C0 + C1) % 32 == 0 and - when C1 > 0 - C0 % 32 == 0 and x1 given; N % 64 == 0;
+ * LWG_EPI_NONE with activation none / ReLU / tanh / sigmoid, or LWG_EPI_RESIDUAL (res given) with those or LWG_ACTIVATION_RELU_MASK.
+ * LWG_EPI_SPADE, LWG_DT_F32_Q4 / bf16 tensors, the ReLU mask without a residual and every other violation return hipErrorInvalidValue before any
+ * launch.  A batch whose input exceeds the 32-bit buffer range runs in batch slices (not with a workspace).
+ * lwg_conv2d_bf16op_ws_floats: the floats of workspace the _ws form wants for this launch = slices * M * N; 0 for NULL, for a launch the plan
+ * runs whole (it fills the chip, or its epilogue is a plain residual) - then ws may be NULL.
+ * lwg_conv2d_nhwc_f32_bf16op_ws: ws = NULL runs whole; else the K loop runs in slices of whole 32-channel chunks into dense [slice][M][N] slabs
+ * that the finishing kernel of lwg_conv2d_nhwc_f32_ws adds in slice order, then bias, activation / ReLU mask: deterministic, no float atomics.
+ * The result depends on the launch description alone. */
+int lwg_conv2d_nhwc_f32_bf16op(const LwgConvArgs* args, lwg_stream_t stream);
+size_t lwg_conv2d_bf16op_ws_floats(const LwgConvArgs* args);
+int lwg_conv2d_nhwc_f32_bf16op_ws(const LwgConvArgs* args, float* ws, lwg_stream_t stream);
+
 /* Backward of the same convolutions (personalization step, tools/trainers/lwg_trainer.py:326-352: loss.backward()
  * through torch.nn.Conv2d / ConvTranspose2d).
  * lwg_conv2d_wgrad_nhwc_f32: dW[K,N] = A[M,K]^T dY[M,N] on the matrix cores.  `args` is the FORWARD launch description

@@ -97,6 +97,9 @@ _SIGS = {
     "lwg_conv_transpose4_is_one_grid": (c_i, [ctypes.POINTER(LwgConvArgs)]),
     "lwg_conv_slice_count": (c_i, [ctypes.POINTER(LwgConvArgs)]),
     "lwg_conv2d_nhwc_f32_split": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
+    "lwg_conv2d_nhwc_f32_bf16op": (c_i, [ctypes.POINTER(LwgConvArgs), c_f]),
+    "lwg_conv2d_bf16op_ws_floats": (ctypes.c_size_t, [ctypes.POINTER(LwgConvArgs)]),
+    "lwg_conv2d_nhwc_f32_bf16op_ws": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f]),
     "lwg_conv2d_wgrad_ws_floats": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "lwg_conv2d_wgrad_nhwc_f32": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f, c_f, c_f]),
     "lwg_conv2d_wgrad_unpacked_f32": (c_i, [ctypes.POINTER(LwgConvArgs), c_f, c_f, c_f] + [c_i] * 5 + [ctypes.POINTER(ctypes.c_int), c_i, c_i, c_f, c_f]),

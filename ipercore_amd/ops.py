@@ -35,6 +35,10 @@ def _ptr(t, dtype=torch.float32):
 # "bf16_winograd": "bf16" with the eligible 3x3 / stride 1 launches (_bf16_wino_eligible) on the fused bf16 F(2x2, 3x3) Winograd kernel
 # (csrc/conv_winograd_bf16.hip: 4 multiplies per output instead of 9; V and U rounded once to bf16 - 1.2-1.9x the direct bf16 kernel's error, not its
 # bits); every other bf16 launch exactly as in "bf16".
+# "bf16_operands" (opt-in, the training step's: trainers.TrainOpts.conv_precision): fp32 tensors, ONE bf16 product per multiply - the launches
+# _bf16op_use takes (fp32 in and out, Cin % 32 == 0, N % 64 == 0, plain or residual epilogue, any taps / stride / parity form) round both fp32
+# operands to bf16 in the kernel, multiply on the bf16 matrix pipe and accumulate in fp32 (csrc/conv_igemm_bf16op.hip, the fp32 panel as it is;
+# DESIGN.md 3.10d; tests/convbf16op_emu.py is the definition): bf16-operand grade, deterministic; every other launch exactly as "fp32".
 CONV_PRECISION = "fp32"
 
 
@@ -44,7 +48,7 @@ class conv_precision(object):
     workgroups on a 64^2 layer: 3.6 against 2.4 ms per frame at frame batch 1), 20 % slower on frame batches.  Each engine is batch-invariant in itself."""
 
     def __init__(self, mode):
-        assert mode in ("fp32", "bf16", "bf16_winograd", "split", "winograd", "winograd2x2")
+        assert mode in ("fp32", "bf16", "bf16_winograd", "split", "winograd", "winograd2x2", "bf16_operands")
         self.mode = mode
 
     def __enter__(self):
@@ -62,7 +66,7 @@ _MODE_WINO4 = True      # the mode's say on the F(4x4, 3x3) kernel (False inside
 
 # bench.py installs a callable(begin, M, spec, epi, info) to bracket conv entry-point calls with HIP events; info (the closing call only, else
 # None) = {"kernels": launches behind the call (lwg_conv_slice_count: batch slices), "kind": which kernel family ran ("direct", "winograd",
-# "split", "bf16", "bf16_winograd", "up4")} - launch / executed-flop accounting only
+# "split", "bf16", "bf16_winograd", "bf16op", "up4")} - launch / executed-flop accounting only
 CONV_HOOK = None
 
 
@@ -269,6 +273,47 @@ def _w16x3(spec):
         lo = (r1 - mid.float()).to(torch.bfloat16)
         return torch.stack([hi, mid, lo]).view(3, K4 // 2, 8, N).permute(0, 1, 3, 2).contiguous()
     return _derived(spec, "w16x3", build)
+
+
+def _bf16op_use(spec, x0, y, x1=None, epi=EPI_NONE, act=ACT_NONE, q4=False, ycoff=0):
+    """Launches of the "bf16_operands" mode that run lwg_conv2d_nhwc_f32_bf16op[_ws] - the single place for the rule, a rule on the layer and
+    launch description (never on the batch or the data): fp32 NHWC in and out (no channel-quad planes), Cin % 32 == 0 - a second input on
+    32 channels -, N % 64 == 0, a plain or residual epilogue (the ReLU mask with the residual only), the output slice on 4 channels.  Any taps,
+    stride and parity form (omul / ooy / oox).  Everything else - the small-Cin first layers, SPADE, q4 - keeps the "fp32" route.
+    One class of launches is excluded on speed, and not here (a conv2d call does not know its siblings): ``_bf16op_use_parity4``, the
+    small parity groups of a ``conv_transpose2d`` call.  The per-shape table is profiles/conv_bf16op_layers.txt."""
+    if q4 or x0.dtype != torch.float32 or y.dtype != torch.float32 or spec.Cin % 32 != 0 or spec.N % 64 != 0:
+        return False
+    if x1 is not None and (x1.dtype != torch.float32 or x0.shape[3] % 32 != 0):
+        return False
+    if epi not in (EPI_NONE, EPI_RESIDUAL) or (act == ACT_RELU_MASK and epi != EPI_RESIDUAL):
+        return False
+    return y.shape[-1] % 4 == 0 and ycoff % 4 == 0
+
+
+def _bf16op_use_parity4(specs, x, y, act=ACT_NONE, splitk=False, out_hw=None, q4=False):
+    """``_bf16op_use`` for the four parity launches of ONE ``conv_transpose2d`` call (a transposed convolution's forward, a 4x4 / stride-2 convolution's
+    data gradient) - the one class of launches the mode leaves on the "fp32" route for speed, by a rule on the launch description: a group that the
+    "fp32" mode runs as ONE grid (lwg_conv_transpose4_is_one_grid: a parity has fewer than 300 tiles of 128 x 128) AND whose parity launches the
+    library's plan would split over K (lwg_conv2d_bf16op_ws_floats > 0; training callers, splitk=True).  There the mode would make eight kernels -
+    four slab launches, four finishing kernels - against one grid: measured 1.07 - 1.41 of the one-grid form's time on all seven such groups of the
+    512^2 step (82 - 108 us against 59 - 95), while every other parity group gains (0.42 - 0.75; profiles/conv_bf16op_parity_groups_before_rule.txt,
+    DESIGN.md 3.10d)."""
+    s0 = specs[0]
+    if not _bf16op_use(s0, x, y, None, EPI_NONE, act, q4):
+        return False
+    if not (splitk and F32_UP4 and x.is_cuda and _parity_specs_ok(specs)):
+        return True
+    hw = None if out_hw is None else tuple(out_hw(s0))
+    key = (tuple(x.shape), tuple(y.shape), s0.N, hw)            # the two library answers are functions of B, OH, OW, Cin, N, ntaps = 4: asked once
+    use = _PARITY4_PLAN.get(key)
+    if use is None:
+        a = conv_args(x, s0, y, act=act, out_hw=hw)
+        use = _PARITY4_PLAN[key] = not (_lib.lib().lwg_conv_transpose4_is_one_grid(a) and _lib.lib().lwg_conv2d_bf16op_ws_floats(a))
+    return use
+
+
+_PARITY4_PLAN = {}
 
 
 _WINO_TAPS = sorted((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))
@@ -597,7 +642,7 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
     synthesis path: a frame's result must not depend on how many frames share its launch (batch invariance is a parity check).
     q4: y is (B, YC/4, YH, YW, 4), channel-quad planes (the fp32 MFMA path only: what ``head_compose(..., q4=True)`` reads)."""
     a = conv_args(x0, spec, y, x1, epi, act, res, xn, mean, rstd, out_hw, ycoff, q4)
-    if q4 and (splitk or CONV_PRECISION not in ("fp32", "winograd") or x0.dtype != torch.float32):
+    if q4 and (splitk or CONV_PRECISION not in ("fp32", "winograd", "bf16_operands") or x0.dtype != torch.float32):
         raise ValueError("channel-quad-plane outputs: fp32 activations on the fp32 MFMA path, no split-K")
     if CONV_HOOK is not None:
         CONV_HOOK(True, a.M, spec, epi, None)
@@ -677,6 +722,14 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
         else:
             a.w = _ptr(_wwino(spec))
             _lib.check(_lib.lib().lwg_conv2d_winograd_f32(a, _stream()), "lwg_conv2d_winograd_f32")
+    elif CONV_PRECISION == "bf16_operands" and _bf16op_use(spec, x0, y, x1, epi, act, q4, ycoff):
+        kind = "bf16op"                             # the fp32 panel as it is: rounded in the kernel
+        nws = _lib.lib().lwg_conv2d_bf16op_ws_floats(a) if splitk else 0
+        if nws:
+            ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
+            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_bf16op_ws(a, _ptr(ws), _stream()), "lwg_conv2d_nhwc_f32_bf16op_ws")
+        else:
+            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_bf16op(a, _stream()), "lwg_conv2d_nhwc_f32_bf16op")
     elif CONV_PRECISION == "split" and spec.Cin % 32 == 0:
         a.w = _ptr(_w16x3(spec), torch.bfloat16)
         kind = "split"
@@ -845,8 +898,10 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
         else:
             _fused_transpose_launch(a, s0, _wwino_t(specs), "lwg_conv_transpose4_winograd_f32", "winograd_up4", False)
         return y
-    if (F32_UP4 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION in ("fp32", "winograd") and s0.Cin % 32 == 0
-            and _parity_specs_ok(specs)):
+    # ("bf16_operands": the parity launches the mode takes go to conv2d below; a layer it refuses - q4 planes, or a one-grid group whose parity
+    # launches would run split-K: _bf16op_use_parity4 - keeps exactly the "fp32" form)
+    if (F32_UP4 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and s0.Cin % 32 == 0 and _parity_specs_ok(specs)
+            and (CONV_PRECISION in ("fp32", "winograd") or (CONV_PRECISION == "bf16_operands" and not _bf16op_use_parity4(specs, x, y, act, splitk, out_hw, q4)))):
         # fp32, small launch (one frame: a parity is a workgroup per CU or less): ONE grid of four times the workgroups
         # (lwg_conv_transpose4_nhwc_f32); large launches stay four conv2d calls (the library would issue the same four launches). The
         # values are those of the four conv2d calls bit for bit (same tiles, same K order).

@@ -640,7 +640,15 @@ class TrainOpts(object):
     # "winograd" (default since round 5): the 3 x 3 / stride 1 forward and data-gradient convolutions run as F(2x2,3x3) Winograd
     # convolutions on the fp32 matrix pipe (csrc/conv_winograd.hip; launches too small to fill the chip keep the direct split-K form:
     # ops.WINO_MIN_GRID), everything else - and every weight gradient - on the direct fp32 MFMA kernels; "fp32": all direct;
-    # "split": forward and data-gradient convs with Cin % 32 == 0 on the bf16x6 kernel (fp32-level accuracy)
+    # "split": forward and data-gradient convs with Cin % 32 == 0 on the bf16x6 kernel (fp32-level accuracy);
+    # "bf16_operands" (opt-in): every forward and data-gradient launch with fp32 tensors, Cin % 32 == 0 and N % 64 == 0, a plain or residual /
+    # ReLU-mask epilogue - any taps and stride, the parity launches of the transposed convolutions and of the stride-2 data gradients included
+    # (ops._bf16op_use; but not the small parity groups that "fp32" runs as one grid and the mode would split over K: ops._bf16op_use_parity4)
+    # - rounds both fp32 operands to bf16 in the kernel, multiplies ONCE on the bf16 matrix pipe and accumulates in fp32
+    # (csrc/conv_igemm_bf16op.hip): bf16-operand grade, deterministic, activations and master weights stay fp32; every other
+    # launch exactly as "fp32".  It holds for everything under the trainer's precision context: G, D and the frozen VGG19 / Sphere20a loss
+    # networks.  Independent of wgrad_precision (the usual whole recipe is ("bf16_operands", "bf16")) and of conv_tiles, which has no effect in
+    # the mode (no Winograd launch is left).  A captured trainer re-captures its step when the value changes
     conv_precision = "winograd"
     # "direct": every weight gradient on the direct fp32 MFMA kernel.  "winograd" (opt-in): the 3 x 3 / stride 1 weight gradients with both
     # channel counts % 64 == 0 in F(2x2,3x3) Winograd form (ops.wgrad_precision, csrc/conv_wgrad_winograd.hip): fp32-grade,
@@ -920,6 +928,11 @@ class LWGTrainer(object):
             self._panel_cache.invalidate()                  # the fragment panels of the other mode's kernels must not ride along in the per-step refresh
             self._graphs = None                             # (a captured step holds the old panels' addresses: it is re-captured for the new mode anyway)
         self._panel_tiles = tiles
+        conv = self.opts.conv_precision
+        if getattr(self, "_panel_cache", None) is not None and getattr(self, "_panel_conv", conv) != conv:
+            self._panel_cache.invalidate()                  # likewise the derived panels of the other precision mode (the Winograd fragment panels
+            self._graphs = None                             # that no launch of "bf16_operands" reads): the new capture registers what it uses
+        self._panel_conv = conv
         prev = ops.PANEL_CACHE, ops.BRANCH_STREAM
         ops.PANEL_CACHE, ops.BRANCH_STREAM = getattr(self, "_panel_cache", None), getattr(self, "_branch_stream", None)
         try:
@@ -1086,6 +1099,9 @@ class LWGTrainer(object):
         if self._graphs["tiles"] != ops.TRAIN_CONV_TILES:    # ... and so is the choice between the F(2x2,3x3) and F(4x4,3x3) launches
             self._graphs = None
             return self._graph_step()
+        if self._graphs["conv"] != (ops.CONV_PRECISION, ops._MODE_WINO4):    # ... and the forward / data-gradient kernels of the precision mode
+            self._graphs = None
+            return self._graph_step()
         gr = self._graphs
         if multi:
             # [A: G fwd / bwd] -> {G's all-reduce on RCCL's stream || [D: D fwd / bwd on the second stream]} -> {Adam(G) || D's all-reduce}
@@ -1188,7 +1204,8 @@ class LWGTrainer(object):
                 self.optimizer_D.step()
         for o, sn in zip(opts_, snaps):                     # capturing step() advanced the host mirrors only; nothing ran on the device
             o.t = sn[4]
-        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION, "tiles": ops.TRAIN_CONV_TILES}
+        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION, "tiles": ops.TRAIN_CONV_TILES,
+                        "conv": (ops.CONV_PRECISION, ops._MODE_WINO4)}
         self._captured_lr = (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr)
         self._static_losses = (loss_G.detach(), None if loss_D is None else loss_D.detach())
         self._static_inp = self.inp
