@@ -4,7 +4,9 @@ PyTorch-ROCm is plumbing here: it owns device memory and the stream; every compu
 ``liblwg_hip.so``.  All wrappers require contiguous CUDA tensors and raise otherwise - there is no eager /
 CPU fallback on the product path.
 """
+import collections
 import ctypes
+import functools
 
 import torch
 
@@ -302,7 +304,7 @@ def _bf16op_use_parity4(specs, x, y, act=ACT_NONE, splitk=False, out_hw=None, q4
     s0 = specs[0]
     if not _bf16op_use(s0, x, y, None, EPI_NONE, act, q4):
         return False
-    if not (splitk and F32_UP4 and x.is_cuda and _parity_specs_ok(specs)):
+    if not (splitk and _up4_f32_ok(x, specs, y)):               # conv_transpose2d's own condition for asking about the one-grid form
         return True
     hw = None if out_hw is None else tuple(out_hw(s0))
     key = (tuple(x.shape), tuple(y.shape), s0.N, hw)            # the two library answers are functions of B, OH, OW, Cin, N, ntaps = 4: asked once
@@ -445,16 +447,6 @@ def _wino4_plan(a):
     return slices.value * a.M * a.N
 
 
-def _wino_route(a, spec, y, splitk):
-    """(F(4x4) ?, workspace floats) of an eligible launch of the "winograd" mode, or None = not on a Winograd kernel."""
-    if _wino4_use(spec, splitk):
-        n4 = _wino4_plan(a) if splitk else 0
-        if n4 is not None:
-            return True, n4
-    n = _wino_plan(a, spec, y, splitk)
-    return None if n is None else (False, n)
-
-
 def _wwino4(spec):
     """The fragment panel of lwg_conv2d_winograd4_f32, built once per spec from the fp32 GEMM panel by ONE launch (lwg_winograd4_panel_f32):
     U = G w G^T (6 x 6) per (input, output) channel pair in fp64, rounded once, stored [4][Cin/8][4][2][9 N] (include/lwg_hip.h)."""
@@ -595,9 +587,7 @@ def conv_args(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=Non
     a.omul, a.ooy, a.oox = spec.omul, spec.ooy, spec.oox
     a.epi, a.act = epi, act
     a.res, a.xn, a.mean, a.rstd = _ptr(res, ydt), _ptr(xn, ydt), _ptr(mean), _ptr(rstd)
-    for i in range(spec.ntaps):
-        a.dy[i] = spec.dy[i]
-        a.dx[i] = spec.dx[i]
+    a.dy[:spec.ntaps], a.dx[:spec.ntaps] = spec.dy, spec.dx
     return a
 
 
@@ -631,6 +621,88 @@ def _hook_end(a, spec, epi, kind, slices=True, extra=0):
     CONV_HOOK(False, a.M, spec, epi, {"kernels": n, "kind": kind})
 
 
+# What ONE conv launch runs - decided once (conv2d_route, conv_transpose2d_route) and read by whoever needs the answer; a value, no behaviour.
+# kind: what CONV_HOOK is told; entry: the library function (None: the four parity conv2d calls of a transposed convolution); form: "plain"
+# entry(a, stream), "ws" entry(a, workspace of nws floats, stream) or "lists" entry(a, LwgConvLists, stream); sliced / extra: as _hook_end takes
+# them (sliced=False: per-image buffer descriptors, one launch at any batch size); panel: the builder ("_wwino", ... - looked up on the module
+# at the launch) of the derived panel the entry reads, None = the fp32 GEMM panel.
+ConvRoute = collections.namedtuple("ConvRoute", "kind entry form nws sliced extra panel")
+
+
+@functools.lru_cache(maxsize=None)
+def _route(kind, entry, panel=None, nws=0, sliced=True, extra=0, lists=False):
+    """The record of a launch: split over K through a workspace (nws > 0: the ``_ws`` entry, ``extra`` finishing kernels), list-driven, or plain."""
+    if nws:
+        return ConvRoute(kind, entry + "_ws", "ws", nws, sliced, extra, panel)
+    return ConvRoute(kind, entry, "lists" if lists else "plain", 0, sliced, 0, panel)
+
+
+def conv2d_route(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, mean=None, rstd=None,
+                 out_hw=None, ycoff=0, splitk=False, q4=False, lists=None, a=None):
+    """The ``ConvRoute`` of the ``conv2d`` call with these arguments (a: its filled argument block, where the caller has one) under the current
+    modes and switches.  Raises conv2d's ValueErrors; asks the library's host planners (training launches, splitk=True, only) and launches nothing."""
+    mode, xdt, ydt, f32, bf = CONV_PRECISION, x0.dtype, y.dtype, torch.float32, torch.bfloat16
+    if q4 and (splitk or mode not in ("fp32", "winograd", "bf16_operands") or xdt != f32):
+        raise ValueError("channel-quad-plane outputs: fp32 activations on the fp32 MFMA path, no split-K")
+    w4 = mode == "winograd" and _wino4_use(spec, splitk)
+    hr = xdt == bf and _hr_eligible(spec, x0, y, out_hw)
+    if lists is not None and not (w4 and xdt == f32 and ydt == f32) and not (hr and ydt == bf and mode == "bf16" and x1 is None and spec.ntaps == 9):
+        raise ValueError("lists: the F(4x4, 3x3) launches of the \"winograd\" mode and the 3 x 3 launches of the \"bf16\" mode only (conv2d_lists_apply)")
+    if xdt == bf:
+        # bf16 activation storage (BASELINE configs[3]): bf16 in, bf16 out, bf16 MFMA operands, fp32 accumulation
+        if ydt != bf or spec.Cin % 64 != 0:
+            raise ValueError("bf16 convolutions need bf16 outputs and Cin % 64 == 0")
+        if mode == "bf16_winograd" and _bf16_wino_eligible(spec, x0, y, x1, epi, act, out_hw, ycoff):
+            return _route("bf16_winograd", "lwg_conv2d_winograd_bf16", "_wwino16", sliced=False)
+        if hr or _pw_eligible(spec, x0, y, x1, epi, out_hw):
+            if lists is not None:                       # the sub-tile lists and the calibration frame: ONE kernel, never sliced
+                return _route("bf16", "lwg_conv2d_nhwc_bf16_hr_list", "_w16hr", sliced=False, lists=True)
+            return _route("bf16", "lwg_conv2d_nhwc_bf16_hr", "_w16hr")
+        return _route("bf16", "lwg_conv2d_nhwc_bf16", "_w16v2")
+    if ydt == bf:
+        # the first layer of a network in bf16 mode: fp32 image-like input (Cin < 32), bf16 output
+        if BF16_C8 and spec.Cin == 8 and spec.N == 64 and spec.ntaps <= 10 and x1 is None and epi == EPI_NONE and spec.omul == 1:
+            return _route("direct", "lwg_conv2d_nhwc_c8_bf16", "_w16c8")
+        return _route("direct", "lwg_conv2d_nhwc_f32")
+    if splitk and a is None:                            # only the planners of the training launches read the argument block
+        a = conv_args(x0, spec, y, x1, epi, act, res, xn, mean, rstd, out_hw, ycoff, q4)
+    if mode == "winograd" and _wino_eligible(spec, x0, y, x1, epi, act, out_hw, q4, ycoff):
+        # F(4x4) where _wino4_use admits the launch and, a training launch, _wino4_plan takes it; else F(2x2) by _wino_plan; else the direct kernels
+        n4 = None if not w4 else _wino4_plan(a) if splitk else 0
+        if n4 is not None and lists is not None:        # the granularity -> its entry point: a plain 4-tuple is block lists with their calibration frame
+            name = "lwg_conv2d_winograd4_list_f32"
+            if len(lists) == 2 and isinstance(lists[0], SkipLists) and lists[0].fine is not None and spade_skip_fine_apply(x0):
+                q8 = lists[0].fine8 is not None and spade_skip_q8_apply(x0, spec.N // 64)
+                name = "lwg_conv2d_winograd4_q8_f32" if q8 else "lwg_conv2d_winograd4_fine_f32"
+            return _route("winograd4", name, "_wwino4", sliced=False, lists=True)
+        if n4 is not None:                              # n4 > 0: a training launch (train_conv_tiles("4x4")) split over K
+            return _route("winograd4", "lwg_conv2d_winograd4_f32", "_wwino4", nws=n4, sliced=False, extra=1)
+        n = _wino_plan(a, spec, y, splitk)
+        if n is not None:
+            return _route("winograd", "lwg_conv2d_winograd_f32", "_wwino", nws=n, sliced=False, extra=1)
+    # (``lists`` is not read below: a launch the guard let through on _wino4_use alone, but which _wino_eligible or the plans refuse, runs
+    # without its lists, silently - as it always has)
+    if mode == "bf16_operands" and _bf16op_use(spec, x0, y, x1, epi, act, q4, ycoff):       # the fp32 panel as it is: rounded in the kernel
+        return _route("bf16op", "lwg_conv2d_nhwc_f32_bf16op", nws=_lib.lib().lwg_conv2d_bf16op_ws_floats(a) if splitk else 0, extra=1)
+    if mode == "split" and spec.Cin % 32 == 0:
+        return _route("split", "lwg_conv2d_nhwc_f32_split", "_w16x3")
+    return _route("direct", "lwg_conv2d_nhwc_f32", nws=_lib.lib().lwg_conv2d_ws_floats(a) if splitk else 0)   # > 0: a small-M / large-K launch, split-K
+
+
+def _conv_lists(entry, lists, x0, spec, y, epi):
+    """The LwgConvLists of a list-driven entry point out of conv2d's ``lists``: the 4-tuple, or the triple of the entry's granularity + cal."""
+    hr = entry == "lwg_conv2d_nhwc_bf16_hr_list"        # its 8 x 16 pixel block is one 16 x 8 sub-tile
+    if len(lists) == 2 and isinstance(lists[0], SkipLists):     # entry -> the SkipLists triple it reads (None: the block lists themselves)
+        attr = {"lwg_conv2d_winograd4_list_f32": None, "lwg_conv2d_winograd4_fine_f32": "fine", "lwg_conv2d_winograd4_q8_f32": "fine8", "lwg_conv2d_nhwc_bf16_hr_list": "fine"}[entry]
+        lists = tuple(lists[0] if attr is None else getattr(lists[0], attr)) + (lists[1],)
+    if hr:
+        nsub = x0.shape[0] * ((x0.shape[1] + 7) // 8) * ((x0.shape[2] + 15) // 16)
+        if min(lists[0].numel(), lists[1].numel()) < nsub or lists[2].numel() < 2 or \
+                lists[3].numel() != x0.shape[1] * x0.shape[2] * (spec.N if epi == EPI_SPADE else y.shape[3]):
+            raise ValueError("lists: the sub-tile lists of this frame batch and ONE calibration frame at its feature size")
+    return _lib.LwgConvLists(*[_ptr(t, torch.int32) for t in lists[:3]], _ptr(lists[3], torch.bfloat16 if hr and epi != EPI_SPADE else torch.float32))
+
+
 def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, mean=None, rstd=None,
            out_hw=None, ycoff=0, splitk=False, q4=False, lists=None):
     """y <- conv(cat[x0, x1]) per ``spec``; x*: (B,H,W,C) NHWC; y: (B,YH,YW,YC) NHWC (written in place).
@@ -642,105 +714,27 @@ def conv2d(x0, spec, y, x1=None, epi=EPI_NONE, act=ACT_NONE, res=None, xn=None, 
     synthesis path: a frame's result must not depend on how many frames share its launch (batch invariance is a parity check).
     q4: y is (B, YC/4, YH, YW, 4), channel-quad planes (the fp32 MFMA path only: what ``head_compose(..., q4=True)`` reads)."""
     a = conv_args(x0, spec, y, x1, epi, act, res, xn, mean, rstd, out_hw, ycoff, q4)
-    if q4 and (splitk or CONV_PRECISION not in ("fp32", "winograd", "bf16_operands") or x0.dtype != torch.float32):
-        raise ValueError("channel-quad-plane outputs: fp32 activations on the fp32 MFMA path, no split-K")
+    # the guards are the route's (it raises before it asks or decides anything): a refused call has announced nothing to the hook
+    kind, entry, form, nws, sliced, extra, panel = conv2d_route(x0, spec, y, x1, epi, act, res, xn, mean, rstd, out_hw, ycoff, splitk, q4, lists, a)
     if CONV_HOOK is not None:
         CONV_HOOK(True, a.M, spec, epi, None)
-    if lists is not None and not (x0.dtype == torch.float32 and y.dtype == torch.float32 and CONV_PRECISION == "winograd" and _wino4_use(spec, splitk)) and \
-            not (x0.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and CONV_PRECISION == "bf16" and x1 is None and spec.ntaps == 9 and
-                 _hr_eligible(spec, x0, y, out_hw)):
-        raise ValueError("lists: the F(4x4, 3x3) launches of the \"winograd\" mode and the 3 x 3 launches of the \"bf16\" mode only (conv2d_lists_apply)")
-    kind, sliced, extra = "direct", True, 0
-    if x0.dtype == torch.bfloat16:
-        kind = "bf16"
-        # bf16 activation storage (BASELINE configs[3]): bf16 in, bf16 out, bf16 MFMA operands, fp32 accumulation
-        if y.dtype != torch.bfloat16 or spec.Cin % 64 != 0:
-            raise ValueError("bf16 convolutions need bf16 outputs and Cin % 64 == 0")
-        if CONV_PRECISION == "bf16_winograd" and _bf16_wino_eligible(spec, x0, y, x1, epi, act, out_hw, ycoff):
-            kind, sliced = "bf16_winograd", False       # per-image buffer descriptors: one launch at any batch size
-            panel, bias = _wwino16(spec, epi == EPI_SPADE)
-            a.w, a.bias = _ptr(panel, torch.bfloat16), _ptr(bias)
-            for i, (dy, dx) in enumerate(_WINO_TAPS):                # the panel's tap order
-                a.dy[i], a.dx[i] = dy, dx
-            _lib.check(_lib.lib().lwg_conv2d_winograd_bf16(a, _stream()), "lwg_conv2d_winograd_bf16")
-        elif _hr_eligible(spec, x0, y, out_hw) or _pw_eligible(spec, x0, y, x1, epi, out_hw):
-            _hr_args(a, spec, epi)
-            if lists is not None:
-                # the sub-tile lists (the kernel's 8 x 16 pixel block is one sub-tile) and the calibration frame: ONE kernel, never sliced
-                sliced = False
-                if len(lists) == 2 and isinstance(lists[0], SkipLists):
-                    lists = tuple(lists[0].fine) + (lists[1],)
-                i32 = torch.int32
-                nsub = x0.shape[0] * ((x0.shape[1] + 7) // 8) * ((x0.shape[2] + 15) // 16)
-                if min(lists[0].numel(), lists[1].numel()) < nsub or lists[2].numel() < 2 or \
-                        lists[3].numel() != x0.shape[1] * x0.shape[2] * (spec.N if epi == EPI_SPADE else y.shape[3]):
-                    raise ValueError("lists: the sub-tile lists of this frame batch and ONE calibration frame at its feature size")
-                ld = _lib.LwgConvLists(_ptr(lists[0], i32), _ptr(lists[1], i32), _ptr(lists[2], i32),
-                                       _ptr(lists[3], torch.float32 if epi == EPI_SPADE else torch.bfloat16))
-                _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr_list(a, ctypes.byref(ld), _stream()), "lwg_conv2d_nhwc_bf16_hr_list")
-            else:
-                _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16_hr(a, _stream()), "lwg_conv2d_nhwc_bf16_hr")
-        else:
-            a.w = _ptr(_w16v2(spec), torch.bfloat16)
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_bf16(a, _stream()), "lwg_conv2d_nhwc_bf16")
-    elif y.dtype == torch.bfloat16:
-        # the first layer of a network in bf16 mode: fp32 image-like input (Cin < 32), bf16 output
-        if BF16_C8 and spec.Cin == 8 and spec.N == 64 and spec.ntaps <= 10 and x1 is None and epi == EPI_NONE and spec.omul == 1:
-            a.w = _ptr(_w16c8(spec), torch.bfloat16)
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_c8_bf16(a, _stream()), "lwg_conv2d_nhwc_c8_bf16")
-        else:
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32(a, _stream()), "lwg_conv2d_nhwc_f32")
-    elif CONV_PRECISION == "winograd" and _wino_eligible(spec, x0, y, x1, epi, act, out_hw, q4, ycoff) and \
-            (route := _wino_route(a, spec, y, splitk)) is not None:
-        kind, sliced = "winograd", False            # per-image buffer descriptors: one launch at any batch size
-        four, nws = route
-        if four:
-            a.w = _ptr(_wwino4(spec))
-            kind = "winograd4"
-            if lists is not None:
-                # the granularity -> its (heavy, light, counts) and entry point: a plain 4-tuple is block lists with their calibration frame
-                name = "lwg_conv2d_winograd4_list_f32"
-                if len(lists) == 2 and isinstance(lists[0], SkipLists):
-                    sl, cal = lists
-                    trip = sl
-                    if sl.fine is not None and spade_skip_fine_apply(x0):
-                        trip, name = sl.fine, "lwg_conv2d_winograd4_fine_f32"
-                        if sl.fine8 is not None and spade_skip_q8_apply(x0, spec.N // 64):
-                            trip, name = sl.fine8, "lwg_conv2d_winograd4_q8_f32"
-                    lists = tuple(trip) + (cal,)
-                ld = _lib.LwgConvLists(*[_ptr(t, torch.int32) for t in lists[:3]], _ptr(lists[3]))
-                _lib.check(getattr(_lib.lib(), name)(a, ctypes.byref(ld), _stream()), name)
-            elif nws:                               # a training launch (train_conv_tiles("4x4")) split over K
-                ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
-                _lib.check(_lib.lib().lwg_conv2d_winograd4_f32_ws(a, _ptr(ws), _stream()), "lwg_conv2d_winograd4_f32_ws")
-            else:
-                _lib.check(_lib.lib().lwg_conv2d_winograd4_f32(a, _stream()), "lwg_conv2d_winograd4_f32")
-        elif nws:
-            a.w = _ptr(_wwino(spec))
-            ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
-            _lib.check(_lib.lib().lwg_conv2d_winograd_f32_ws(a, _ptr(ws), _stream()), "lwg_conv2d_winograd_f32_ws")
-        else:
-            a.w = _ptr(_wwino(spec))
-            _lib.check(_lib.lib().lwg_conv2d_winograd_f32(a, _stream()), "lwg_conv2d_winograd_f32")
-    elif CONV_PRECISION == "bf16_operands" and _bf16op_use(spec, x0, y, x1, epi, act, q4, ycoff):
-        kind = "bf16op"                             # the fp32 panel as it is: rounded in the kernel
-        nws = _lib.lib().lwg_conv2d_bf16op_ws_floats(a) if splitk else 0
-        if nws:
-            ws, extra = torch.empty(nws, device=x0.device, dtype=torch.float32), 1
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_bf16op_ws(a, _ptr(ws), _stream()), "lwg_conv2d_nhwc_f32_bf16op_ws")
-        else:
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_bf16op(a, _stream()), "lwg_conv2d_nhwc_f32_bf16op")
-    elif CONV_PRECISION == "split" and spec.Cin % 32 == 0:
-        a.w = _ptr(_w16x3(spec), torch.bfloat16)
-        kind = "split"
-        _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_split(a, _stream()), "lwg_conv2d_nhwc_f32_split")
+    if panel == "_w16hr":
+        _hr_args(a, spec, epi)
+    elif panel == "_wwino16":
+        w, bias = _wwino16(spec, epi == EPI_SPADE)
+        a.w, a.bias = _ptr(w, torch.bfloat16), _ptr(bias)
+        a.dy[:9], a.dx[:9] = zip(*_WINO_TAPS)                         # the panel's tap order
+    elif panel is not None:
+        a.w = _ptr(globals()[panel](spec), torch.float32 if panel in ("_wwino", "_wwino4") else torch.bfloat16)    # (_w16v2, _w16c8, _w16x3: bf16)
+    if form == "ws":
+        ws = torch.empty(nws, device=x0.device, dtype=torch.float32)
+        rc = getattr(_lib.lib(), entry)(a, _ptr(ws), _stream())
+    elif form == "lists":
+        ld = _conv_lists(entry, lists, x0, spec, y, epi)
+        rc = getattr(_lib.lib(), entry)(a, ctypes.byref(ld), _stream())
     else:
-        nws = _lib.lib().lwg_conv2d_ws_floats(a) if splitk else 0    # > 0: a small-M / large-K launch the library runs split-K
-        if nws:
-            ws = torch.empty(nws, device=x0.device, dtype=torch.float32)
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32_ws(a, _ptr(ws), _stream()), "lwg_conv2d_nhwc_f32_ws")
-        else:
-            _lib.check(_lib.lib().lwg_conv2d_nhwc_f32(a, _stream()), "lwg_conv2d_nhwc_f32")
+        rc = getattr(_lib.lib(), entry)(a, _stream())
+    _lib.check(rc, entry)
     if CONV_HOOK is not None:
         _hook_end(a, spec, epi, kind, sliced, extra)
     return y
@@ -756,6 +750,11 @@ def _parity_specs_ok(specs):
     s0 = specs[0]
     return (len(specs) == 4 and all(s.ntaps == 4 and s.omul == 2 and s.stride == 1 and (s.ooy, s.oox) == (i >> 1, i & 1) and s.N == s0.N and s.Cin == s0.Cin
                                     and [(dy - (i >> 1), dx - (i & 1)) for dy, dx in zip(s.dy, s.dx)] == list(zip(s0.dy, s0.dx)) for i, s in enumerate(specs)))
+
+
+def _up4_f32_ok(x, specs, y):
+    """The fp32 transposed convolutions lwg_conv_transpose4_nhwc_f32 can take as ONE grid - where lwg_conv_transpose4_is_one_grid then agrees."""
+    return (F32_UP4 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and specs[0].Cin % 32 == 0 and _parity_specs_ok(specs))
 
 
 def _wwino_t(specs):
@@ -874,6 +873,33 @@ def _w32up(specs):
     return _derived(specs, "w32up", lambda: torch.stack([s.w.reshape(-1) for s in specs]).contiguous())
 
 
+def _up4_route(x, specs, y, act, splitk, out_hw, q4):
+    """(``ConvRoute``, the filled argument block of its ONE launch - None with the four parity calls) of a ``conv_transpose2d`` call."""
+    s0, mode, f32 = specs[0], CONV_PRECISION, x.dtype == torch.float32 and y.dtype == torch.float32
+    if (BF16_UP4 and BF16_HR and x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and len(specs) == 4 and s0.Cin in (64, 128)
+            and s0.N % 64 == 0 and all(s.ntaps == 4 and s.omul == 2 and (s.ooy, s.oox) == (i >> 1, i & 1) for i, s in enumerate(specs))):
+        return _route("up4", "lwg_conv_transpose4_nhwc_bf16", "_w16up"), conv_args(x, s0, y, act=act)
+    if WINO_UP4 and mode == "winograd" and not splitk and out_hw is None and x.is_cuda and f32 and s0.Cin % 32 == 0 and s0.N % 32 == 0 and _parity_specs_ok(specs):
+        # the synthesis path in the "winograd" mode: ONE fused Winograd launch (per-image work in a fixed order: a frame does not depend on its batch),
+        # F(2x4, 2x2) for images of >= WINO_UP4_24_MIN_HW input pixels (DESIGN.md 3.12c).  Training callers (splitk=True) keep the direct forms.
+        name, panel = ("lwg_conv_transpose4_winograd24_f32", "_wwino_t24") if _up4_24(x) else ("lwg_conv_transpose4_winograd_f32", "_wwino_t")
+        return _route("winograd_up4", name, panel, sliced=False), conv_args(x, s0, y, act=act, q4=q4)
+    if _up4_f32_ok(x, specs, y) and (mode in ("fp32", "winograd") or (mode == "bf16_operands" and not _bf16op_use_parity4(specs, x, y, act, splitk, out_hw, q4))):
+        # fp32, small launch (a parity is a workgroup per CU or less): ONE grid of four times the workgroups; large launches stay four conv2d calls
+        # (the library would issue the same four launches) - the same values bit for bit (same tiles, same K order).  "bf16_operands": a layer
+        # the mode refuses (q4 planes, a one-grid group whose parity launches would run split-K) keeps exactly this "fp32" form
+        a = conv_args(x, s0, y, act=act, q4=q4)
+        if _lib.lib().lwg_conv_transpose4_is_one_grid(a):
+            return _route("up4", "lwg_conv_transpose4_nhwc_f32", "_w32up"), a
+    return _route("parity4", None), None
+
+
+def conv_transpose2d_route(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=False):
+    """The ``ConvRoute`` of the ``conv_transpose2d`` call with these arguments: the fused bf16 launch, the F(2x2, 2x2) or F(2x4, 2x2) Winograd launch,
+    the one-grid fp32 launch (panel: the builder that takes the four specs), or entry None = four parity ``conv2d`` calls (each with its own route)."""
+    return _up4_route(x, specs, y, act, splitk, out_hw, q4)[0]
+
+
 def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=False):
     """y (B,2H,2W,N) <- ConvTranspose2d(4, 2, 1) of x (B,H,W,Cin) given its four parity specs (packing.pack_conv_transpose).
     bf16 activations with Cin <= 128: ONE launch (lwg_conv_transpose4_nhwc_bf16: the input block is staged once for the four
@@ -882,33 +908,10 @@ def conv_transpose2d(x, specs, y, act=ACT_NONE, splitk=False, out_hw=None, q4=Fa
     otherwise the one-grid form for small fp32 launches or the four parity launches of ``conv2d``.  ``splitk`` / ``out_hw`` are handed to those four launches (the
     training callers' plan: the one-grid form and the four-launch fall-back then differ only in launch count); ``out_hw`` is a
     callable spec -> (OH, OW) or None.  q4 (fp32 only): y is (B, N/4, 2H, 2W, 4), channel-quad planes (see ``conv2d``)."""
-    s0 = specs[0]
-    if (BF16_UP4 and BF16_HR and x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and len(specs) == 4 and s0.Cin in (64, 128)
-            and s0.N % 64 == 0 and all(s.ntaps == 4 and s.omul == 2 and (s.ooy, s.oox) == (i >> 1, i & 1) for i, s in enumerate(specs))):
-        _fused_transpose_launch(conv_args(x, s0, y, act=act), s0, _w16up(specs), "lwg_conv_transpose4_nhwc_bf16", "up4")
+    r, a = _up4_route(x, specs, y, act, splitk, out_hw, q4)
+    if r.entry is not None:
+        _fused_transpose_launch(a, specs[0], globals()[r.panel](specs), r.entry, r.kind, r.sliced)
         return y
-    if (WINO_UP4 and CONV_PRECISION == "winograd" and not splitk and out_hw is None and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32
-            and s0.Cin % 32 == 0 and s0.N % 32 == 0 and _parity_specs_ok(specs)):
-        # the synthesis path in the "winograd" mode: the layer as ONE fused F(2x2, 2x2) Winograd launch (36 products per 4 x 4 input patch instead
-        # of 64; per-image work in a fixed order: a frame does not depend on its batch).  Training callers (splitk=True) keep the direct forms.
-        # Images of >= WINO_UP4_24_MIN_HW input pixels: F(2x4, 2x2) (60 products per 2 x 4 input patch instead of 72; DESIGN.md 3.12c).
-        a = conv_args(x, s0, y, act=act, q4=q4)
-        if _up4_24(x):
-            _fused_transpose_launch(a, s0, _wwino_t24(specs), "lwg_conv_transpose4_winograd24_f32", "winograd_up4", False)
-        else:
-            _fused_transpose_launch(a, s0, _wwino_t(specs), "lwg_conv_transpose4_winograd_f32", "winograd_up4", False)
-        return y
-    # ("bf16_operands": the parity launches the mode takes go to conv2d below; a layer it refuses - q4 planes, or a one-grid group whose parity
-    # launches would run split-K: _bf16op_use_parity4 - keeps exactly the "fp32" form)
-    if (F32_UP4 and x.is_cuda and x.dtype == torch.float32 and y.dtype == torch.float32 and s0.Cin % 32 == 0 and _parity_specs_ok(specs)
-            and (CONV_PRECISION in ("fp32", "winograd") or (CONV_PRECISION == "bf16_operands" and not _bf16op_use_parity4(specs, x, y, act, splitk, out_hw, q4)))):
-        # fp32, small launch (one frame: a parity is a workgroup per CU or less): ONE grid of four times the workgroups
-        # (lwg_conv_transpose4_nhwc_f32); large launches stay four conv2d calls (the library would issue the same four launches). The
-        # values are those of the four conv2d calls bit for bit (same tiles, same K order).
-        a = conv_args(x, s0, y, act=act, q4=q4)
-        if _lib.lib().lwg_conv_transpose4_is_one_grid(a):
-            _fused_transpose_launch(a, s0, _w32up(specs), "lwg_conv_transpose4_nhwc_f32", "up4")
-            return y
     for s in specs:
         conv2d(x, s, y, act=act, splitk=splitk, out_hw=None if out_hw is None else out_hw(s), q4=q4)
     return y
@@ -1472,6 +1475,12 @@ class wgrad_precision(object):
 class wgrad_mode(wgrad_precision):
     """The same switch with every value of trainers.TrainOpts.wgrad_precision: ``with ops.wgrad_mode("bf16"): ...`` (nests with ``wgrad_precision``)."""
     MODES = ("direct", "winograd", "bf16")
+
+
+def launch_modes():
+    """Every mode switch a captured step freezes into its kernels: a capture made under one value of this tuple is replayed only under that value
+    (trainers.LWGTrainer).  A new switch of this kind belongs HERE - nowhere else is there a list to extend."""
+    return CONV_PRECISION, _MODE_WINO4, WGRAD_PRECISION, TRAIN_CONV_TILES
 
 
 def _wgrad_wino_use(x0, spec, dy, x1=None):

@@ -923,21 +923,11 @@ class LWGTrainer(object):
             self._panel_cache = ops.PanelCache([p for n in nets if n is not None for p in list(n.parameters()) + list(n.buffers())])
         if on_gpu and getattr(self.opts, "branch_streams", False) and getattr(self, "_branch_stream", None) is None:
             self._branch_stream = torch.cuda.Stream()
-        tiles = getattr(self.opts, "conv_tiles", "2x2")
-        if getattr(self, "_panel_cache", None) is not None and getattr(self, "_panel_tiles", tiles) != tiles:
-            self._panel_cache.invalidate()                  # the fragment panels of the other mode's kernels must not ride along in the per-step refresh
-            self._graphs = None                             # (a captured step holds the old panels' addresses: it is re-captured for the new mode anyway)
-        self._panel_tiles = tiles
-        conv = self.opts.conv_precision
-        if getattr(self, "_panel_cache", None) is not None and getattr(self, "_panel_conv", conv) != conv:
-            self._panel_cache.invalidate()                  # likewise the derived panels of the other precision mode (the Winograd fragment panels
-            self._graphs = None                             # that no launch of "bf16_operands" reads): the new capture registers what it uses
-        self._panel_conv = conv
+        self._sync_modes()
         prev = ops.PANEL_CACHE, ops.BRANCH_STREAM
         ops.PANEL_CACHE, ops.BRANCH_STREAM = getattr(self, "_panel_cache", None), getattr(self, "_branch_stream", None)
         try:
-            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_mode(getattr(self.opts, "wgrad_precision", "direct")), \
-                    ops.train_conv_tiles(tiles):
+            with ops.conv_precision(self.opts.conv_precision), ops.wgrad_mode(self.opts.wgrad_precision), ops.train_conv_tiles(self.opts.conv_tiles):
                 if self._graphable():
                     return self._graph_step()
                 if getattr(self.opts, "dp_schedule", "hooks") == "segmented" and self._multi():
@@ -949,6 +939,18 @@ class LWGTrainer(object):
                 return self._optimize_parameters()
         finally:
             ops.PANEL_CACHE, ops.BRANCH_STREAM = prev
+
+    def _sync_modes(self):
+        """The step's mode options against the last step's: any change drops the captured graphs (the other mode's kernels, the old panels' addresses);
+        one of conv_precision or conv_tiles also empties the panel cache - the other kernels' derived panels must not ride along in the per-step refresh."""
+        o = self.opts
+        key = (o.conv_precision, o.conv_tiles, o.wgrad_precision)
+        old = getattr(self, "_modes", key)
+        if old != key:
+            self._graphs = None
+            if old[:2] != key[:2] and getattr(self, "_panel_cache", None) is not None:
+                self._panel_cache.invalidate()
+        self._modes = key
 
     def _multi(self):
         """Is this step data parallel?  ``force_dp`` (tests): run the data-parallel schedule in a one-rank group too, so the RCCL calls
@@ -1085,21 +1087,10 @@ class LWGTrainer(object):
                 torch.cuda.synchronize()
                 self.step_mode = "eager launches (graph capture failed)"
                 return self._optimize_parameters()
-        if self._captured_lr != (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr):
-            # the learning rate is a kernel argument frozen into the graph: a changed lr needs a new capture
-            self._graphs = None
-            return self._graph_step()
-        multi = self._multi()
-        if self._graphs["dp"] != multi:                      # captured for the other form (a process group appeared / went away)
-            self._graphs = None
-            return self._graph_step()
-        if self._graphs["wgrad"] != ops.WGRAD_PRECISION:     # the weight-gradient kernels are frozen into the graph too
-            self._graphs = None
-            return self._graph_step()
-        if self._graphs["tiles"] != ops.TRAIN_CONV_TILES:    # ... and so is the choice between the F(2x2,3x3) and F(4x4,3x3) launches
-            self._graphs = None
-            return self._graph_step()
-        if self._graphs["conv"] != (ops.CONV_PRECISION, ops._MODE_WINO4):    # ... and the forward / data-gradient kernels of the precision mode
+        multi, lr = self._multi(), (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr)
+        # frozen into the graph: the learning rate (a kernel argument), the data-parallel form (a process group appeared / went away) and the kernels
+        # of every mode - precision, F(2x2,3x3) / F(4x4,3x3) tiles, weight gradient (ops.launch_modes): a change of any needs a new capture
+        if self._captured_lr != lr or self._graphs["dp"] != multi or self._graphs["modes"] != ops.launch_modes():
             self._graphs = None
             return self._graph_step()
         gr = self._graphs
@@ -1204,8 +1195,7 @@ class LWGTrainer(object):
                 self.optimizer_D.step()
         for o, sn in zip(opts_, snaps):                     # capturing step() advanced the host mirrors only; nothing ran on the device
             o.t = sn[4]
-        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "wgrad": ops.WGRAD_PRECISION, "tiles": ops.TRAIN_CONV_TILES,
-                        "conv": (ops.CONV_PRECISION, ops._MODE_WINO4)}
+        self._graphs = {"A": gA, "D": gD, "B": gB, "C": gC, "dp": multi, "modes": ops.launch_modes()}
         self._captured_lr = (self.optimizer_G.lr, None if self.optimizer_D is None else self.optimizer_D.lr)
         self._static_losses = (loss_G.detach(), None if loss_D is None else loss_D.detach())
         self._static_inp = self.inp

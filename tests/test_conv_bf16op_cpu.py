@@ -222,10 +222,41 @@ def test_parity_group_rule():
 
 
 def test_trainer_drops_the_panel_cache_on_a_precision_switch():
-    import inspect
+    """LWGTrainer._sync_modes on a bare trainer: a change of conv_precision or conv_tiles empties the panel cache exactly once and drops the
+    captured graphs, a change of wgrad_precision drops the graphs and leaves the cache, an unchanged step does neither."""
     from ipercore_amd.trainers import LWGTrainer
-    src = inspect.getsource(LWGTrainer.optimize_parameters)
-    assert "_panel_conv" in src and src.count("self._panel_cache.invalidate()") == 2
+
+    class _Cache:
+        n = 0
+
+        def invalidate(self):
+            self.n += 1
+    tr = LWGTrainer.__new__(LWGTrainer)
+    tr.opts, tr._panel_cache, graphs = TrainOpts(), _Cache(), {"A": object()}
+
+    def step(**changes):
+        for k, v in changes.items():
+            assert getattr(tr.opts, k) != v
+            setattr(tr.opts, k, v)
+        tr._graphs, before = graphs, tr._panel_cache.n
+        tr._sync_modes()
+        return tr._panel_cache.n - before, tr._graphs is None
+
+    assert step() == (0, False) and step() == (0, False)                    # the first step has nothing to compare with; an unchanged one
+    assert step(conv_precision="bf16_operands") == (1, True)
+    assert step() == (0, False)
+    assert step(conv_tiles="4x4") == (1, True)
+    assert step(wgrad_precision="bf16") == (0, True)
+    assert step(wgrad_precision="winograd") == (0, True)
+    assert step() == (0, False)
+    assert step(conv_precision="winograd", conv_tiles="2x2") == (1, True)   # both at once: still one invalidation
+    assert step(conv_precision="fp32", wgrad_precision="direct") == (1, True)
+    assert step() == (0, False)
+    tr._panel_cache = None                                                  # no panel cache (use_panel_cache off): the graphs still go
+    assert tr.opts.conv_tiles == "2x2"
+    tr.opts.conv_tiles, tr._graphs = "4x4", graphs
+    tr._sync_modes()
+    assert tr._graphs is None
 
 
 def test_trainopts_documents_the_value():
