@@ -14,13 +14,12 @@
 //     workgroup is walked in chunks of 32 rows: A chunk [32][128] and dY chunk [32][128] are staged in LDS
 //     (double buffered, loads of chunk i+1 in flight during the MFMAs of chunk i).  v_mfma_f32_32x32x2: lanes 0-31
 //     supply reduction index 2s, lanes 32-63 index 2s+1, so a fragment is one ds_read_b32 of a [m][k] row.
-//   * The reduction is split over gridDim.y workgroups; each writes its partial tile to a workspace slab and
-//     lwg_wgrad_reduce adds the slabs in slab order (deterministic - no float atomics).
+//   * The reduction is split over gridDim.y workgroups; slabs, split plan and tile width: lwg_wgrad_slab.h.
 #include <type_traits>
 
 #include "lwg_common.h"
 #include "lwg_conv_direct.h"
-#include "lwg_wgrad_reduce.h"
+#include "lwg_wgrad_slab.h"
 
 #define LWG_OOB_OFFSET 0xC0000000u
 
@@ -30,10 +29,8 @@ __device__ __forceinline__ floatx4 lwg_wg_buf_load(const float* base, unsigned b
 }
 
 // a: the FORWARD geometry (x0/x1, taps, stride, OH/OW/M, N, output mapping YH/YW/YC/ycoff/omul/ooy/oox); a.y is unused.
-// dy_: gradient of the forward output, laid out like the forward y.  part: [gridDim.y][Ktot][N] partial sums.
-// BN: columns of the output tile.  128: wave tile 64 (k) x 64 (n) = 2 x 2 MFMA tiles.  64: wave tile 64 (k) x 32 (n) = 2 x 1 - for
-// the N = 64 layers (last up-sampling layer, first discriminator / encoder layers), where a 128-column tile spends half of its MFMAs on
-// columns that do not exist (33 - 53 TFLOP/s on those launches).
+// dy_: gradient of the forward output, laid out like the forward y.  part: the slabs.
+// BN: columns of the output tile (lwg_wgrad_bn).  128: wave tile 64 (k) x 64 (n) = 2 x 2 MFMA tiles.  64: wave tile 64 (k) x 32 (n) = 2 x 1.
 template <bool SMALLC, int BN>
 __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_kernel(const LwgConvArgs a, const float* __restrict__ dy_, int Ktot,
                                                                int chunks_per_split, float* __restrict__ part, int want_bias) {
@@ -110,8 +107,7 @@ __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_kernel(const LwgConvArg
         rox = rem - roy * a.OW;
     }
     floatx4 rx[4], ry[NYP];
-    // Bias gradient (column sums of dY) as row Ktot of the slab: the workgroups of k-tile 0 add up the dY quads they stage anyway
-    // (NYP vector adds per chunk) - no separate pass over dY (lwg_colsum_nhwc_f32: 102 launch pairs per training step).
+    // Bias gradient, the slab's last row: NYP vector adds per chunk instead of lwg_colsum_nhwc_f32's 102 launch pairs per training step
     const bool do_bias = want_bias != 0 && tile_k == 0;
     floatx4 cs[NYP];
 #pragma unroll
@@ -250,8 +246,8 @@ __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_kernel(const LwgConvArg
             chunk(k0{}, std::false_type{});
         }
     }
-    // ---- partial tile -> workspace slab blockIdx.y.  Lane owns column n = lane&31, rows k = (r&3) + 8*(r>>2) + 4*khalf ----
-    float* slab = part + (size_t)blockIdx.y * (Ktot + 1) * a.N;     // a slab = Ktot weight rows + the bias-gradient row
+    // ---- partial tile -> slab blockIdx.y.  Lane owns column n = lane&31, rows k = (r&3) + 8*(r>>2) + 4*khalf ----
+    float* slab = lwg_wgrad_slab(part, blockIdx.y, Ktot, a.N);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -278,8 +274,8 @@ __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_kernel(const LwgConvArg
     }
 }
 
-// dW[i] = sum_s part[s][i] in slab order; optionally also the bias gradient db[n] = sum_m dY[m, n] is NOT computed here
-// (it is a plain column sum, done by lwg_colsum_nhwc_f32).
+// out[i] = sum_s part[s * stride + i] in slab order, i < total: the packed weight gradient of lwg_conv2d_wgrad_nhwc_f32 (the slabs' bias row is
+// left behind: stride = total + N) and the second pass of lwg_colsum_nhwc_f32.  The un-packing entry points take the fused kernels below.
 __global__ void lwg_wgrad_reduce_kernel(const float* __restrict__ part, int nsplit, size_t total, size_t stride, float* __restrict__ dw) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         float s = 0.f;
@@ -324,27 +320,9 @@ static void lwg_launch_slab_reduce(const float* part, int nsplit, size_t total, 
     }
 }
 
-// The slab reduction of a weight gradient fused with its un-packing: element i of the OUTPUT (tap, c, n; n fastest) is the sum
-// over the slices of slab[k(tap, c)][n] and lands at the parameter tensor's own position (nn.Conv2d (N, Cin, KH, KW), or
-// (Cin, N, KH, KW) for transposed = 1) - what lwg_wgrad_reduce_kernel + lwg_unpack_wgrad_f32 did in two launches and one extra
-// pass over dW (~150 launch pairs per training step).  struct LwgUnpackMap: lwg_wgrad_reduce.h.
-
-// element i of the output -> its slab offset (src) and parameter-tensor offset (dst).  Elements [total_w, total_w + nout) are the bias
-// gradient (slab row ntaps * cin_pad, returned with bias = true and dst = n) when the launch carries one.
-__device__ __forceinline__ void lwg_unpack_map(const LwgUnpackMap& u, size_t i, size_t& src, size_t& dst, bool& bias) {
-    const int n = (int)(i % u.nout), r = (int)(i / u.nout);
-    bias = r >= u.ntaps * u.cin;
-    if (bias) {
-        src = (size_t)u.ntaps * u.cin_pad * u.n_pad + n;
-        dst = (size_t)n;
-        return;
-    }
-    const int c = r % u.cin, tap = r / u.cin;
-    const int k = (u.cin_pad & 31) == 0 ? ((c >> 5) * u.ntaps + tap) * 32 + (c & 31) : tap * u.cin_pad + c;
-    src = (size_t)k * u.n_pad + n;
-    dst = ((size_t)(u.transposed ? c : n) * u.D1 + (u.transposed ? n : c)) * u.KHW + u.kidx[tap];
-}
-
+// The slab reduction of a weight gradient fused with its un-packing (lwg_unpack_map: element i of the output is the sum over the slabs of its
+// slab entry and lands at the parameter tensor's own position) - what lwg_wgrad_reduce_kernel + lwg_unpack_wgrad_f32 did in two launches and one
+// extra pass over dW (~150 launch pairs per training step).
 template <int G>
 __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack_kernel(const float* __restrict__ part, int nsplit, size_t slab, size_t total,
                                                                      const LwgUnpackMap u, float* __restrict__ out, float* __restrict__ db) {
@@ -382,13 +360,9 @@ __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack_kernel(const float
 // loop is unrolled by four (independent loads in flight; the sums are still added in slab order: deterministic).
 __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack4_kernel(const float* __restrict__ part, int nsplit, size_t slab, size_t total4,
                                                                       const LwgUnpackMap u, float* __restrict__ out, float* __restrict__ db) {
-    const int nq = u.nout >> 2;
     for (size_t i4 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i4 < total4; i4 += (size_t)gridDim.x * blockDim.x) {
-        const int n = (int)(i4 % nq) * 4, r = (int)(i4 / nq);
-        const bool bias = r >= u.ntaps * u.cin;              // the quads past the weight elements: the bias-gradient row of the slabs
-        const int c = r % u.cin, tap = bias ? 0 : r / u.cin;
-        const int k = bias ? u.ntaps * u.cin_pad : ((u.cin_pad & 31) == 0 ? ((c >> 5) * u.ntaps + tap) * 32 + (c & 31) : tap * u.cin_pad + c);
-        const float* src = part + (size_t)k * u.n_pad + n;
+        const LwgUnpackQuad q = lwg_unpack_quad(u, i4);
+        const float* src = part + q.src;
         floatx4 s = {0.f, 0.f, 0.f, 0.f};
         int kk = 0;
         for (; kk + 4 <= nsplit; kk += 4) {
@@ -399,15 +373,12 @@ __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack4_kernel(const floa
             s += v0; s += v1; s += v2; s += v3;
         }
         for (; kk < nsplit; ++kk) s += *reinterpret_cast<const floatx4*>(src + (size_t)kk * slab);
-        if (bias) {
-            *reinterpret_cast<floatx4*>(db + n) = s;
+        if (q.bias) {
+            *reinterpret_cast<floatx4*>(db + q.n) = s;
             continue;
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const size_t dst = ((size_t)(u.transposed ? c : n + j) * u.D1 + (u.transposed ? n + j : c)) * u.KHW + u.kidx[tap];
-            out[dst] = s[j];
-        }
+        for (int j = 0; j < 4; ++j) out[lwg_unpack_dst(u, q.tap, q.c, q.n + j)] = s[j];
     }
 }
 
@@ -420,14 +391,11 @@ __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack4g_kernel(const flo
     constexpr int EPB = 256 / G;
     __shared__ floatx4 sh[256];
     const int e = threadIdx.x % EPB, g = threadIdx.x / EPB;
-    const int nq = u.nout >> 2;
     const size_t i4 = (size_t)blockIdx.x * EPB + e;
     const bool live = i4 < total4;
-    const int n = live ? (int)(i4 % nq) * 4 : 0, r = live ? (int)(i4 / nq) : 0;
-    const bool bias = r >= u.ntaps * u.cin;
-    const int c = r % u.cin, tap = bias ? 0 : r / u.cin;
-    const int k = bias ? u.ntaps * u.cin_pad : ((u.cin_pad & 31) == 0 ? ((c >> 5) * u.ntaps + tap) * 32 + (c & 31) : tap * u.cin_pad + c);
-    const float* src = part + (size_t)k * u.n_pad + n;
+    const int nq = u.nout >> 2;
+    const LwgUnpackQuad q = lwg_unpack_quad_at(u, live ? (int)(i4 % nq) * 4 : 0, live ? (int)(i4 / nq) : 0);
+    const float* src = part + q.src;
     floatx4 s = {0.f, 0.f, 0.f, 0.f};
     if (live) {
         int kk = g;
@@ -444,22 +412,17 @@ __global__ __launch_bounds__(256) void lwg_slab_reduce_unpack4g_kernel(const flo
     floatx4 t = sh[e];
 #pragma unroll
     for (int j = 1; j < G; ++j) t += sh[j * EPB + e];
-    if (bias) {
-        *reinterpret_cast<floatx4*>(db + n) = t;
+    if (q.bias) {
+        *reinterpret_cast<floatx4*>(db + q.n) = t;
         return;
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const size_t dst = ((size_t)(u.transposed ? c : n + j) * u.D1 + (u.transposed ? n + j : c)) * u.KHW + u.kidx[tap];
-        out[dst] = t[j];
-    }
+    for (int j = 0; j < 4; ++j) out[lwg_unpack_dst(u, q.tap, q.c, q.n + j)] = t[j];
 }
 
-// total: weight elements (ntaps * cin * nout); db != NULL appends the nout bias-gradient elements (slab row Ktot) to the same launch
-static void lwg_launch_slab_reduce_unpack(const float* part, int nsplit, size_t slab, size_t total, const LwgUnpackMap& u, float* out, float* db,
-                                          hipStream_t stream) {
-    const size_t weights = total;
-    if (db) total += (size_t)u.nout;
+// db != NULL appends the nout bias-gradient elements (the slabs' bias row) to the same launch
+void lwg_wgrad_reduce_unpack(const float* part, int nsplit, const LwgUnpackMap& u, float* out, float* db, hipStream_t stream) {
+    const size_t slab = lwg_unpack_slab_floats(u), weights = lwg_unpack_weights(u), total = weights + (db ? (size_t)u.nout : 0);
     if (weights >= 65536 && (u.nout & 3) == 0 && (u.n_pad & 3) == 0 && (slab & 3) == 0) {
         const size_t total4 = total / 4;
         if (total4 < 65536 && nsplit >= 32) {        // few quads, many slabs: several lanes per quad
@@ -526,25 +489,12 @@ __global__ __launch_bounds__(256) void lwg_colsum_partial_kernel(const float* __
     if (w == 0 && c < C) ws[(size_t)blockIdx.y * C + c] = (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
 }
 
-// Reduction splits: enough workgroups to fill the 256 CUs twice (2 workgroups/CU), at most 48 MB of slabs (every slab is
-// written and read once more by the reduction), at least 4 chunks of 32 rows per workgroup.
-static int lwg_wgrad_bn(int N) { return (N % 128 != 0 && N % 128 <= 64) ? 64 : 128; }    // 64-column tiles when the last 128 would be half empty
-
-static int lwg_wgrad_splits(int Ktot, int N, int M) {
-    const int bn = lwg_wgrad_bn(N);
-    const int tiles = ((Ktot + 127) / 128) * ((N + bn - 1) / bn);
-    const int nchunks = (M + 31) / 32;
-    int splits = 512 / tiles;          // tiles * splits <= 512 = one full wave of workgroups at 2 per CU (no ragged second wave)
-    const long slab = (long)(Ktot + 1) * N * 4;
-    if ((long)splits * slab > (48l << 20)) splits = (int)((48l << 20) / slab);     // <= 48 MB of slabs per launch
-    if (splits > nchunks / 4) splits = nchunks / 4;
-    if (splits < 1) splits = 1;
-    const int cps = (nchunks + splits - 1) / splits;          // chunks per workgroup; drop the splits that would get none
-    return (nchunks + cps - 1) / cps;                          // (128 chunks over 14 splits: 10 each -> 13 workgroups have work)
+static LwgSplitPlan lwg_wgrad_splits(int Ktot, int N, int M) {
+    return lwg_wgrad_split_plan(lwg_wgrad_tiles(Ktot, N), (M + 31) / 32, 512, (long long)lwg_wgrad_slab_floats(Ktot, N) * 4, 48ll << 20);
 }
 
 extern "C" size_t lwg_conv2d_wgrad_ws_floats(int Ktot, int N, int M) {
-    return (size_t)lwg_wgrad_splits(Ktot, N, M) * (size_t)(Ktot + 1) * N;     // a slab = Ktot weight rows + the bias-gradient row
+    return (size_t)lwg_wgrad_splits(Ktot, N, M).splits * lwg_wgrad_slab_floats(Ktot, N);
 }
 
 // Validation + the slab launch shared by the two entry points; *splits_out slices of (Ktot, N) land in ws.
@@ -559,18 +509,14 @@ static int lwg_wgrad_launch(const LwgConvArgs* pa, const float* dy, float* ws, h
     if (smallc && (a.C1 != 0 || Cin > 16 || (Cin & (Cin - 1)) != 0 || (1 << a.cshift) != (Cin >> 2))) return (int)hipErrorInvalidValue;
     if (!smallc && a.C1 != 0 && (a.C0 % 32 != 0 || !a.x1)) return (int)hipErrorInvalidValue;
     const int Ktot = a.ntaps * Cin;
-    const int bn = lwg_wgrad_bn(a.N);
-    const int tiles = ((Ktot + 127) / 128) * ((a.N + bn - 1) / bn);
-    const int nchunks = (a.M + 31) / 32;
-    const int splits = lwg_wgrad_splits(Ktot, a.N, a.M);
-    const int cps = (nchunks + splits - 1) / splits;
+    const LwgSplitPlan plan = lwg_wgrad_splits(Ktot, a.N, a.M);
     const size_t lds = (size_t)4 * 32 * 128 * sizeof(float) + LWG_MAX_TAPS * sizeof(int);
     auto launch = [&](auto sc, auto bnc) {
-        return lwg_launch_lds<lwg_conv_wgrad_kernel<decltype(sc)::value != 0, decltype(bnc)::value>>(dim3(tiles, splits), dim3(256), lds, stream, a, dy, Ktot, cps, ws, want_bias);
+        return lwg_launch_lds<lwg_conv_wgrad_kernel<decltype(sc)::value != 0, decltype(bnc)::value>>(dim3(lwg_wgrad_tiles(Ktot, a.N), plan.splits), dim3(256), lds, stream, a, dy, Ktot, plan.cps, ws, want_bias);
     };
-    const hipError_t e = bn == 64 ? (smallc ? launch(IntC<1>(), IntC<64>()) : launch(IntC<0>(), IntC<64>()))
-                                  : (smallc ? launch(IntC<1>(), IntC<128>()) : launch(IntC<0>(), IntC<128>()));
-    *splits_out = splits;
+    const hipError_t e = lwg_wgrad_bn(a.N) == 64 ? (smallc ? launch(IntC<1>(), IntC<64>()) : launch(IntC<0>(), IntC<64>()))
+                                                 : (smallc ? launch(IntC<1>(), IntC<128>()) : launch(IntC<0>(), IntC<128>()));
+    *splits_out = plan.splits;
     return (int)e;
 }
 
@@ -581,8 +527,8 @@ extern "C" int lwg_conv2d_wgrad_nhwc_f32(const LwgConvArgs* pa, const float* dy,
     if (!dw) return (int)hipErrorInvalidValue;
     int splits = 0;
     if (int e = lwg_wgrad_launch(pa, dy, ws, stream, &splits); e != 0) return e;
-    const size_t total = (size_t)pa->ntaps * (pa->C0 + pa->C1) * pa->N;
-    lwg_launch_slab_reduce(ws, splits, total, total + (size_t)pa->N, dw, stream);
+    const int Ktot = pa->ntaps * (pa->C0 + pa->C1);
+    lwg_launch_slab_reduce(ws, splits, (size_t)Ktot * pa->N, lwg_wgrad_slab_floats(Ktot, pa->N), dw, stream);
     return (int)hipGetLastError();
 }
 
@@ -603,36 +549,16 @@ extern "C" int lwg_conv2d_wgrad_unpacked_f32(const LwgConvArgs* pa, const float*
     return (int)hipGetLastError();
 }
 
-bool lwg_wgrad_unpack_map_make(const LwgConvArgs* pa, int D0, int D1, int KH, int KW, int transposed, const int* kidx, int cin, int nout, LwgUnpackMap* u) {
-    if (!pa || !kidx || cin < 1 || nout < 1 || cin > pa->C0 + pa->C1 || nout > pa->N) return false;
-    if ((transposed ? cin : nout) > D0 || (transposed ? nout : cin) > D1 || pa->ntaps < 1 || pa->ntaps > LWG_MAX_TAPS) return false;
-    u->D1 = D1; u->KHW = KH * KW; u->transposed = transposed; u->ntaps = pa->ntaps; u->cin = cin; u->cin_pad = pa->C0 + pa->C1;
-    u->nout = nout; u->n_pad = pa->N;
-    for (int i = 0; i < pa->ntaps; ++i) {
-        if (kidx[i] < 0 || kidx[i] >= KH * KW) return false;
-        u->kidx[i] = kidx[i];
-    }
-    return true;
-}
-
-void lwg_wgrad_reduce_unpack(const float* ws, int splits, const LwgUnpackMap& u, float* dw, float* db, hipStream_t stream) {
-    lwg_launch_slab_reduce_unpack(ws, splits, ((size_t)u.ntaps * u.cin_pad + 1) * u.n_pad, (size_t)u.ntaps * u.cin * u.nout, u, dw, db, stream);
-}
-
 // out[c] = sum over rows of x (rows, C); ws: 64 * C floats.
 extern "C" int lwg_colsum_nhwc_f32(const float* x, size_t rows, int C, float* out, float* ws, lwg_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if (!x || !out || !ws || rows == 0 || C <= 0) return (int)hipErrorInvalidValue;
-    if ((C & 3) == 0 && C <= 1024 && (256 % (C / 4 < 256 ? C / 4 : 256)) == 0) {
-        const int nblk = rows >= 512 * 64 ? 512 : (int)((rows + 63) / 64);      // ws holds nblk * C floats (callers size it 512 * C)
-        const int rpb = (int)((rows + nblk - 1) / nblk);
-        hipLaunchKernelGGL(lwg_colsum_partial4_kernel, dim3(nblk), dim3(256), 0, stream, x, rows, C, rpb, ws);
-        lwg_launch_slab_reduce(ws, nblk, (size_t)C, (size_t)C, out, stream);
-        return (int)hipGetLastError();
-    }
-    const int nblk = rows >= 64 * 64 ? 64 : (int)((rows + 63) / 64);
+    const bool quads = (C & 3) == 0 && C <= 1024 && (256 % (C / 4 < 256 ? C / 4 : 256)) == 0;
+    const int most = quads ? 512 : 64;                                           // row blocks: ws holds nblk * C floats (callers size it 512 * C)
+    const int nblk = rows >= (size_t)most * 64 ? most : (int)((rows + 63) / 64);
     const int rpb = (int)((rows + nblk - 1) / nblk);
-    hipLaunchKernelGGL(lwg_colsum_partial_kernel, dim3((C + 63) / 64, nblk), dim3(256), 0, stream, x, rows, C, rpb, ws);
+    if (quads) hipLaunchKernelGGL(lwg_colsum_partial4_kernel, dim3(nblk), dim3(256), 0, stream, x, rows, C, rpb, ws);
+    else hipLaunchKernelGGL(lwg_colsum_partial_kernel, dim3((C + 63) / 64, nblk), dim3(256), 0, stream, x, rows, C, rpb, ws);
     lwg_launch_slab_reduce(ws, nblk, (size_t)C, (size_t)C, out, stream);
     return (int)hipGetLastError();
 }

@@ -15,15 +15,13 @@
 //     free.  Wave w gathers the w-th 32-k group of the tile, so tap and source tensor are wave-uniform (descriptor in SGPRs).
 //   * Two LDS stages: the loads of chunk i + 1 are issued before the MFMAs of chunk i, their conversion and LDS writes follow them; one
 //     barrier per chunk.
-//   * The reduction is split over gridDim.y workgroups; each writes its partial tile to a workspace slab laid out like the direct kernel's
-//     ([Ktot + 1][N], row Ktot = the bias gradient) and the direct kernel's reduction (lwg_wgrad_reduce.h) adds the slabs in slab order
-//     (deterministic - no float atomics) into the parameter's own layout.
-//   * Bias gradient: the workgroups of k-tile 0 add up the fp32 dY values they load, BEFORE rounding (row Ktot of the slab).
+//   * The reduction is split over gridDim.y workgroups; the direct kernel's slabs, reduction, split plan and tile width: lwg_wgrad_slab.h.
+//   * Bias gradient: the workgroups of k-tile 0 add up the fp32 dY values they load, BEFORE rounding.
 #include <type_traits>
 
 #include "lwg_common.h"
 #include "lwg_conv_direct.h"
-#include "lwg_wgrad_reduce.h"
+#include "lwg_wgrad_slab.h"
 
 #define WGB_OOB 0xC0000000u
 #define WGB_BR 64                                        // rows of a chunk
@@ -38,7 +36,7 @@ __device__ __forceinline__ floatx4 wgb_buf_load(const float* base, unsigned byte
 }
 
 // a: the FORWARD geometry (x0 / x1, taps, stride, OH / OW / M, N, YC, ycoff; dy dense: omul 1, YH == OH, YW == OW); a.y is unused.
-// dy_: gradient of the forward output.  part: [gridDim.y][Ktot + 1][N] partial sums.
+// dy_: gradient of the forward output.  part: the slabs.
 template <int BN>
 __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_bf16_kernel(const LwgConvArgs a, const float* __restrict__ dy_, int Ktot,
                                                                     int chunks_per_split, float* __restrict__ part, int want_bias) {
@@ -200,8 +198,8 @@ __global__ __launch_bounds__(256, 2) void lwg_conv_wgrad_bf16_kernel(const LwgCo
         }
         if (c < c_end) chunk(k0c{}, false);
     }
-    // ---- partial tile -> workspace slab blockIdx.y.  Lane owns column n = lane & 31, rows k = (r & 3) + 8 (r >> 2) + 4 khalf ----
-    float* slab = part + (size_t)blockIdx.y * (Ktot + 1) * a.N;     // a slab = Ktot weight rows + the bias-gradient row
+    // ---- partial tile -> slab blockIdx.y.  Lane owns column n = lane & 31, rows k = (r & 3) + 8 (r >> 2) + 4 khalf ----
+    float* slab = lwg_wgrad_slab(part, blockIdx.y, Ktot, a.N);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -238,26 +236,15 @@ static bool wgb_contract_ok(const LwgConvArgs& a) {
     return cd_inputs_fit(a, 4ull) && lwg_buf_fits((unsigned long long)a.B * a.YH * a.YW * (unsigned long long)a.YC * 4ull);
 }
 
-static int wgb_bn(int N) { return (N % 128 != 0) ? 64 : 128; }      // N % 64 == 0: 64-column tiles when the last 128 would be half empty
-
-// Reduction splits - a function of the launch shape and the CU count only: two workgroups per CU, at most 48 MB of slabs (every slab is
-// written and read once more by the reduction), at least 4 chunks of 64 rows per workgroup.
-static int wgb_splits(const LwgConvArgs& a, int cus) {
-    const int Ktot = a.ntaps * (a.C0 + a.C1), bn = wgb_bn(a.N);
-    const int tiles = ((Ktot + 127) / 128) * ((a.N + bn - 1) / bn);
-    const int nchunks = (a.M + WGB_BR - 1) / WGB_BR;
-    int splits = 2 * cus / tiles;
-    const long long slab = (long long)(Ktot + 1) * a.N * 4;
-    if ((long long)splits * slab > (48ll << 20)) splits = (int)((48ll << 20) / slab);
-    if (splits > nchunks / 4) splits = nchunks / 4;
-    if (splits < 1) splits = 1;
-    const int cps = (nchunks + splits - 1) / splits;          // chunks per workgroup; drop the splits that would get none
-    return (nchunks + cps - 1) / cps;
+// a function of the launch shape and the CU count only
+static LwgSplitPlan wgb_splits(const LwgConvArgs& a, int cus) {
+    const int Ktot = a.ntaps * (a.C0 + a.C1);
+    return lwg_wgrad_split_plan(lwg_wgrad_tiles(Ktot, a.N), (a.M + WGB_BR - 1) / WGB_BR, 2 * cus, (long long)lwg_wgrad_slab_floats(Ktot, a.N) * 4, 48ll << 20);
 }
 
 extern "C" size_t lwg_conv2d_wgrad_bf16_ws_floats(const LwgConvArgs* pa) {
     if (!pa || !wgb_contract_ok(*pa)) return 0;
-    return (size_t)wgb_splits(*pa, lwg_device_cus()) * ((size_t)pa->ntaps * (pa->C0 + pa->C1) + 1) * pa->N;
+    return (size_t)wgb_splits(*pa, lwg_device_cus()).splits * lwg_wgrad_slab_floats(pa->ntaps * (pa->C0 + pa->C1), pa->N);
 }
 
 extern "C" int lwg_conv2d_wgrad_bf16_f32(const LwgConvArgs* pa, const float* dy, float* ws, float* dw, int D0, int D1, int KH, int KW,
@@ -267,15 +254,13 @@ extern "C" int lwg_conv2d_wgrad_bf16_f32(const LwgConvArgs* pa, const float* dy,
     if (!pa || !dy || !ws || !dw || !wgb_contract_ok(*pa) || !lwg_wgrad_unpack_map_make(pa, D0, D1, KH, KW, transposed, kidx, cin, nout, &u))
         return (int)hipErrorInvalidValue;
     const LwgConvArgs& a = *pa;
-    const int Ktot = a.ntaps * (a.C0 + a.C1), bn = wgb_bn(a.N);
-    const int tiles = ((Ktot + 127) / 128) * ((a.N + bn - 1) / bn);
-    const int nchunks = (a.M + WGB_BR - 1) / WGB_BR;
-    const int splits = wgb_splits(a, lwg_device_cus());
-    const int cps = (nchunks + splits - 1) / splits;
+    const int Ktot = a.ntaps * (a.C0 + a.C1), bn = lwg_wgrad_bn(a.N);
+    const LwgSplitPlan plan = wgb_splits(a, lwg_device_cus());
+    const dim3 grid(lwg_wgrad_tiles(Ktot, a.N), plan.splits);
     const size_t lds = (size_t)2 * (128 + bn) * WGB_PITCH * 2 + LWG_MAX_TAPS * sizeof(int);
-    const hipError_t e = bn == 64 ? lwg_launch_lds<lwg_conv_wgrad_bf16_kernel<64>>(dim3(tiles, splits), dim3(256), lds, stream, a, dy, Ktot, cps, ws, db ? 1 : 0)
-                                  : lwg_launch_lds<lwg_conv_wgrad_bf16_kernel<128>>(dim3(tiles, splits), dim3(256), lds, stream, a, dy, Ktot, cps, ws, db ? 1 : 0);
+    const hipError_t e = bn == 64 ? lwg_launch_lds<lwg_conv_wgrad_bf16_kernel<64>>(grid, dim3(256), lds, stream, a, dy, Ktot, plan.cps, ws, db ? 1 : 0)
+                                  : lwg_launch_lds<lwg_conv_wgrad_bf16_kernel<128>>(grid, dim3(256), lds, stream, a, dy, Ktot, plan.cps, ws, db ? 1 : 0);
     if (e != hipSuccess) return (int)e;
-    lwg_wgrad_reduce_unpack(ws, splits, u, dw, db, stream);
+    lwg_wgrad_reduce_unpack(ws, plan.splits, u, dw, db, stream);
     return (int)hipGetLastError();
 }

@@ -21,6 +21,7 @@
 
 #include "lwg_common.h"
 #include "lwg_conv_direct.h"
+#include "lwg_wgrad_slab.h"
 
 #define WGW_OOB 0xC0000000u
 #define WGW_CT 8                                         // tiles per chunk
@@ -258,23 +259,14 @@ static bool wgw_contract_ok(const LwgConvArgs& a) {
 
 static int wgw_tiles(const LwgConvArgs& a) { return a.B * ((a.H + 1) / 2) * ((a.W + 1) / 2); }
 
-// Reduction splits - a function of the launch shape and the CU count only: one workgroup per CU (128 KB of LDS), at most 64 MB of slabs
-// (every slab is written and read once more by the reduction), at least 4 chunks of 8 tiles per workgroup.
-static int wgw_splits(const LwgConvArgs& a, int cus) {
-    const int blocks = ((a.C0 + a.C1) / 64) * (a.N / 64);
-    const int nchunks = (wgw_tiles(a) + WGW_CT - 1) / WGW_CT;
-    int splits = cus / blocks;
-    const long long slab = 64ll * (a.C0 + a.C1) * a.N;
-    if ((long long)splits * slab > (64ll << 20)) splits = (int)((64ll << 20) / slab);
-    if (splits > nchunks / 4) splits = nchunks / 4;
-    if (splits < 1) splits = 1;
-    const int cps = (nchunks + splits - 1) / splits;          // chunks per workgroup; drop the splits that would get none
-    return (nchunks + cps - 1) / cps;
+// a function of the launch shape and the CU count only (lwg_wgrad_slab.h: the plan)
+static LwgSplitPlan wgw_splits(const LwgConvArgs& a, int cus) {
+    return lwg_wgrad_split_plan(((a.C0 + a.C1) / 64) * (a.N / 64), (wgw_tiles(a) + WGW_CT - 1) / WGW_CT, cus, 64ll * (a.C0 + a.C1) * a.N, 64ll << 20);
 }
 
 extern "C" size_t lwg_conv2d_wgrad_winograd_ws_floats(const LwgConvArgs* pa) {
     if (!pa || !wgw_contract_ok(*pa)) return 0;
-    return (size_t)wgw_splits(*pa, lwg_device_cus()) * 16 * (size_t)(pa->C0 + pa->C1) * pa->N;
+    return (size_t)wgw_splits(*pa, lwg_device_cus()).splits * 16 * (size_t)(pa->C0 + pa->C1) * pa->N;
 }
 
 extern "C" int lwg_conv2d_wgrad_winograd_f32(const LwgConvArgs* pa, const float* dy, float* ws, float* dw, int cin, int nout, lwg_stream_t stream_) {
@@ -283,11 +275,10 @@ extern "C" int lwg_conv2d_wgrad_winograd_f32(const LwgConvArgs* pa, const float*
     const LwgConvArgs& a = *pa;
     const int Ctot = a.C0 + a.C1;
     const int TH = (a.H + 1) / 2, TW = (a.W + 1) / 2, T = wgw_tiles(a);
-    const int nchunks = (T + WGW_CT - 1) / WGW_CT;
-    const int splits = wgw_splits(a, lwg_device_cus());
-    const int cps = (nchunks + splits - 1) / splits;
+    const LwgSplitPlan plan = wgw_splits(a, lwg_device_cus());
+    const int splits = plan.splits;
     const size_t lds = (size_t)2 * WGW_STAGE * sizeof(float);
-    if (hipError_t e = lwg_launch_lds<lwg_conv_wgrad_winograd_kernel>(dim3((Ctot / 64) * (a.N / 64), splits), dim3(512), lds, stream, a, dy, TH, TW, T, cps, ws); e != hipSuccess) return (int)e;
+    if (hipError_t e = lwg_launch_lds<lwg_conv_wgrad_winograd_kernel>(dim3((Ctot / 64) * (a.N / 64), splits), dim3(512), lds, stream, a, dy, TH, TW, T, plan.cps, ws); e != hipSuccess) return (int)e;
     const size_t slab = (size_t)16 * Ctot * a.N, total = (size_t)cin * nout;
     if (total < 65536 && splits >= 32)
         hipLaunchKernelGGL(lwg_wgw_reduce_kernel<16>, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, ws, splits, slab, Ctot, a.N, cin, nout, dw);

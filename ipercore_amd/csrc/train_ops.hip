@@ -5,6 +5,7 @@
 // All tensors NHWC fp32; HBM-bound streaming kernels with 16-byte accesses; reductions are two-pass and deterministic.
 #include "lwg_common.h"
 #include "lwg_conv_args.h"
+#include "lwg_wgrad_slab.h"
 
 #define LWG_ACT_LRELU 4   // LeakyReLU(0.2) (patch discriminator); extends the activation codes of lwg_common.h for these kernels
 
@@ -330,24 +331,13 @@ extern "C" int lwg_adam_step_dev_f32(float* p, const float* g, float* m, float* 
 // Weight panels straight from the parameter tensors (personalization step: every step re-packs every weight - forward panel,
 // data-gradient panel - and un-packs every weight gradient; as chains of torch view / permute / cat / copy kernels that was
 // ~1600 launches and 15 % of the step).  One launch per panel:
-//   panel[(k / 4), n, k % 4]  with  k = ((c / 32) * ntaps + tap) * 32 + c % 32   (cin_pad % 32 == 0)   or   tap * cin_pad + c
+//   panel[(k / 4), n, k % 4]  with  k = lwg_korder_k(tap, c)  (lwg_wgrad_slab.h)
 //   value = W[n][c][kidx[tap]] (transposed = 0: Conv2d forward, ConvTranspose2d data gradient)
 //         = W[c][n][kidx[tap]] (transposed = 1: ConvTranspose2d forward, Conv2d data gradient),   0 beyond (cin, nout)
 // W is (D0, D1, KH, KW) contiguous, kidx[tap] = ky * KW + kx of the weight slice a GEMM tap reads.
 struct LwgTapIdx {
     int kidx[LWG_MAX_TAPS];
 };
-
-__device__ __forceinline__ void lwg_korder_decode(int k, int ntaps, int cin_pad, int& tap, int& c) {
-    if ((cin_pad & 31) == 0) {
-        const int chunk = k / (ntaps * 32), rem = k - chunk * ntaps * 32;
-        tap = rem >> 5;
-        c = chunk * 32 + (rem & 31);
-    } else {
-        tap = k / cin_pad;
-        c = k - tap * cin_pad;
-    }
-}
 
 __global__ void lwg_pack_panel_kernel(const float* __restrict__ w, int D1, int KHW, int transposed, LwgTapIdx taps, int ntaps, int cin,
                                       int cin_pad, int nout, int n_pad, int Kp, float* __restrict__ out) {
@@ -361,7 +351,7 @@ __global__ void lwg_pack_panel_kernel(const float* __restrict__ w, int D1, int K
             if (k < ntaps * cin_pad && n < nout) {
                 int tap, c;
                 lwg_korder_decode(k, ntaps, cin_pad, tap, c);
-                if (c < cin) v[kk] = w[((size_t)(transposed ? c : n) * D1 + (transposed ? n : c)) * KHW + taps.kidx[tap]];
+                if (c < cin) v[kk] = w[lwg_param_offset(transposed, D1, KHW, c, n) + taps.kidx[tap]];
             }
         }
         *reinterpret_cast<floatx4*>(out + (size_t)i * 4) = v;
@@ -411,7 +401,7 @@ __global__ void lwg_pack_panels_kernel(const LwgPackDesc* __restrict__ descs, in
         const size_t ob = ((size_t)(c0 >> 5) * ntaps * 8 + ((c0 & 31) >> 2)) * n_pad + n;      // float4 index of tap 0
         size_t src[4];
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) src[kk] = ((size_t)(tr ? c0 + kk : n) * D1 + (tr ? n : c0 + kk)) * KHW;
+        for (int kk = 0; kk < 4; ++kk) src[kk] = lwg_param_offset(tr, D1, KHW, c0 + kk, n);
         for (int tap = 0; tap < ntaps; ++tap) {
             floatx4 v = {0.f, 0.f, 0.f, 0.f};
             if (n < nout) {
@@ -432,7 +422,7 @@ __global__ void lwg_pack_panels_kernel(const LwgPackDesc* __restrict__ descs, in
         if (k < ntaps * cin_pad && n < nout) {
             int tap, c;
             lwg_korder_decode(k, ntaps, cin_pad, tap, c);
-            if (c < cin) v[kk] = w[((size_t)(tr ? c : n) * D1 + (tr ? n : c)) * KHW + d->kidx[tap]];
+            if (c < cin) v[kk] = w[lwg_param_offset(tr, D1, KHW, c, n) + d->kidx[tap]];
         }
     }
     *reinterpret_cast<floatx4*>(d->out + (size_t)i * 4) = v;
@@ -454,8 +444,8 @@ __global__ void lwg_unpack_wgrad_kernel(const float* __restrict__ dwk, int D1, i
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int n = i % nout, r = i / nout;
         const int c = r % cin, tap = r / cin;
-        const int k = (cin_pad & 31) == 0 ? ((c >> 5) * ntaps + tap) * 32 + (c & 31) : tap * cin_pad + c;
-        dw[((size_t)(transposed ? c : n) * D1 + (transposed ? n : c)) * KHW + taps.kidx[tap]] = dwk[(size_t)k * n_pad + n];
+        const int k = lwg_korder_k(ntaps, cin_pad, tap, c);
+        dw[lwg_param_offset(transposed, D1, KHW, c, n) + taps.kidx[tap]] = dwk[(size_t)k * n_pad + n];
     }
 }
 
