@@ -674,6 +674,28 @@ int lwg_jpeg_scan_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab
 size_t lwg_jpeg_scan_capacity(int H, int W, int mcus_per_segment);
 size_t lwg_jpeg_scan_ws_bytes(int B, int H, int W, int mcus_per_segment);
 int lwg_jpeg_max_mcus_per_segment(void);
+/* lwg_fuse_sources_u8 / lwg_fuse_canvas_u8: the comparison canvas of the reference's fuse_src_ref_multi_outputs
+ * (tools/utils/multimedia/video.py:451-505), composed on the device (csrc/fuse_canvas.hip; the layout is csrc/lwg_fuse_geom.h's and
+ * tests/fusecanvas_emu.py is the definition, which the kernels equal byte for byte; opt-in through output.FrameWriter(fuse=...)).
+ * lwg_fuse_sources_u8, once per source set: src (ns,3,S,S) fp32 in [-1,1] -> panel (S,Wp,3) uint8 RGB, Wp = lwg_fuse_panel_width(ns, S):
+ *   fuse_source (:297-357) as its code runs - ns = 1: the image; 2: sources 0 | 1 stacked at half size (Wp = S/2); 3..7: a 2 x 2 grid of
+ *   0, 1 (left column) and 2, 3 (right column; black for ns = 3) at half size (Wp = S); ns >= 8: sources 0, 1, 4, 5 stacked at quarter size
+ *   (Wp = S/4).  ns 2..7 need an even S, ns >= 8 S % 4 == 0.  A source pixel becomes u = clamp(rint((x + 1) * 127.5), 0, 255) (each
+ *   operation rounded in fp32, ties to even, NaN -> 0: the 8-bit value load_images made it from), a half / quarter size pixel
+ *   (a + b + c + d + 2) >> 2 over source rows and columns f i + f/2 - 1, f i + f/2 - cv2.resize(INTER_LINEAR) of uint8 at the factors 2 and 4.
+ * lwg_fuse_canvas_u8, per frame batch: panel; ref (B,S,S,3) uint8 RGB or NULL; outs: HOST array of n_out (1..4) device pointers, each
+ *   (B,3,S,S) fp32 -> canvas (B,S,Wc,3) uint8, a row = [panel | pad | ref | pad | out0 | pad | out1 ...] (merge_multi_outs / merge_src_out,
+ *   :173-213; without ref the 'ref | pad' pair is dropped), Wc = Wp + (has_ref + n_out) (S + pad) = lwg_fuse_canvas_width(...), pad >= 0
+ *   columns of pad_val (0..255).  The out regions hold lwg_frames_to_u8(bgr = 0)'s bytes for any input value.  One launch; every store is an
+ *   aligned 32-bit word except a last partial word of the batch; nothing outside B S Wc 3 bytes is written.
+ * hipErrorInvalidValue before any launch: NULL pointers (ref excepted), base pointers not 4-byte aligned, B <= 0, sizes outside the rules
+ * above, Wp not a panel width of S, a canvas or fp32 frame of 2^31 bytes or more, a canvas row above 65 526 bytes (a workgroup holds whole
+ * rows).  The two width helpers are host-only and return 0 for such arguments. */
+int lwg_fuse_sources_u8(const float* src, int ns, int S, uint8_t* panel, lwg_stream_t stream);
+int lwg_fuse_canvas_u8(const uint8_t* panel, int Wp, const uint8_t* ref, const float* const* outs, int n_out, int B, int S, int pad, int pad_val,
+                       uint8_t* canvas, lwg_stream_t stream);
+int lwg_fuse_panel_width(int ns, int S);
+int lwg_fuse_canvas_width(int ns, int S, int pad, int has_ref, int n_out);
 int lwg_nchw_to_nhwc_f32(const float* src, float* dst, int B, int C, int Cp, int P, lwg_stream_t stream);
 int lwg_nhwc_to_nchw_f32(const float* src, float* dst, int B, int C, int Cs, int P, lwg_stream_t stream);
 

@@ -164,6 +164,10 @@ _SIGS = {
     "lwg_jpeg_scan_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "lwg_jpeg_scan_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "lwg_jpeg_max_mcus_per_segment": (c_i, []),
+    "lwg_fuse_sources_u8": (c_i, [c_f, c_i, c_i, c_f, c_f]),
+    "lwg_fuse_canvas_u8": (c_i, [c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "lwg_fuse_panel_width": (c_i, [c_i, c_i]),
+    "lwg_fuse_canvas_width": (c_i, [c_i] * 5),
     "lwg_morph_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_canny_f32": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                             ctypes.c_float, ctypes.c_float, c_f, c_f, c_f]),

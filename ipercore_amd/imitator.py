@@ -92,6 +92,15 @@ class Imitator(object):
             raise ValueError("opt.output_format must be 'png', 'jpeg' or 'mjpeg', not %r" % (self.output_format,))
         self.jpeg_quality = int(_opt_get(opt, "jpeg_quality", 90))
         self.output_fps = float(_opt_get(opt, "output_fps", 25))
+        # the reference's comparison video next to the usual output (services/run_imitator.py:169 -> fuse_src_ref_multi_outputs): "src_out" =
+        # [source panel | pad | frame], "src_ref_out" = [source panel | pad | reference frame | pad | frame] (inference(..., ref_imgs=...)), one
+        # Motion-JPEG file "{prefix}fused.avi" at output_fps / jpeg_quality, composed on the device (output.FrameWriter(fuse=...)); "none": nothing
+        self.fuse_output = str(_opt_get(opt, "fuse_output", "none"))
+        if self.fuse_output not in ("none", "src_out", "src_ref_out"):
+            raise ValueError("opt.fuse_output must be 'none', 'src_out' or 'src_ref_out', not %r" % (self.fuse_output,))
+        self.fuse_pad = int(_opt_get(opt, "fuse_pad", 10))
+        self.fuse_pad_val = int(_opt_get(opt, "fuse_pad_val", 0))
+        self.fused_video_path = None              # what the last inference wrote, if fuse_output asked for it
         self.temporal_fifo = None
         self.primary_ids = 0                      # which source's camera / shape drives the target (Swapper sets it)
         self._create_networks()
@@ -306,25 +315,75 @@ class Imitator(object):
             return FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
         return FrameWriter(output_dir, prefix=prefix, encoder=self.output_format, quality=self.jpeg_quality, fps=self.output_fps)
 
+    def _fused_writer(self, output_dir, prefix, ref_imgs, n_frames, batches):
+        """-> (writer, reference feed) of "{prefix}fused.avi", or (None, None) with opt.fuse_output unset.  Raises before a frame is made."""
+        self.fused_video_path = None
+        if self.fuse_output == "none":
+            if ref_imgs is not None:
+                raise ValueError("ref_imgs are shown by opt.fuse_output = 'src_ref_out' only")
+            return None, None
+        if not output_dir:
+            raise ValueError("opt.fuse_output = %r writes a file: inference needs output_dir" % (self.fuse_output,))
+        with_ref = self.fuse_output == "src_ref_out"
+        if with_ref and ref_imgs is None:
+            raise ValueError("opt.fuse_output = 'src_ref_out' needs inference(..., ref_imgs=...)")
+        from .output import FrameWriter, FuseSpec, RefFrames
+        refs = RefFrames(ref_imgs, n_frames, self.image_size, batches) if with_ref else None
+        spec = FuseSpec(ops.fuse_source_panel(self.src_info["img"]), pad=self.fuse_pad, pad_val=self.fuse_pad_val, with_ref=with_ref)
+        return FrameWriter(output_dir, prefix=prefix, encoder="mjpeg", quality=self.jpeg_quality, fps=self.output_fps, fuse=spec,
+                           video_name="fused.avi"), refs
+
+    @staticmethod
+    def _submit_fused(fused, refs, k, preds, t0):
+        if fused is None:
+            return
+        fused.submit(preds, t0, ref=None if refs is None else refs.get(k))
+        if refs is not None:
+            refs.done(k, fused.ref_uploaded)
+
+    def _close_fused(self, fused, refs):
+        if fused is not None:
+            try:
+                self.fused_video_path = fused.close()[0]
+            finally:
+                if refs is not None:
+                    refs.close()
+
     @torch.no_grad()
     def inference(self, tgt_smpls, cam_strategy="smooth", output_dir="", prefix="pred_", use_selected_f2pts=False,
-                  visualizer=None, verbose=True):
-        """imitator.py:327-382."""
+                  visualizer=None, verbose=True, ref_imgs=None):
+        """imitator.py:327-382.  With opt.fuse_output set the frames also go, from the same device tensors, into the comparison video
+        "{prefix}fused.avi" (``self.fused_video_path``; the one-line replacement of fuse_src_ref_multi_outputs); ref_imgs: the reference
+        frames of "src_ref_out" - a (n,S,S,3) uint8 RGB array / tensor or n image paths, n = the number of target frames."""
         tgt = self.prepare_sequence(tgt_smpls, cam_strategy)
+        n = tgt.shape[0]
+        batches = [(0, n)] if self.temporal else [(s, min(self.frame_batch, n - s)) for s in range(0, n, self.frame_batch)]
+        fused, refs = self._fused_writer(output_dir, prefix, ref_imgs, n, batches)
         if self.temporal:
             preds = self.synthesize_temporal(tgt, cam_strategy, use_selected_f2pts=use_selected_f2pts)
             if output_dir:
                 writer = self._frame_writer(output_dir, prefix)
                 writer.submit(preds, 0)
-                return writer.close()
+                self._submit_fused(fused, refs, 0, preds, 0)
+                try:
+                    paths = writer.close()
+                finally:
+                    self._close_fused(fused, refs)
+                return paths
             preds = preds.cpu().numpy()
             return [preds[i] for i in range(preds.shape[0])]
         if output_dir:
             # device-side uint8 conversion + pinned async D2H + threaded PNG encoding: the frame loop never waits for disk
             writer = self._frame_writer(output_dir, prefix)
-            for s in range(0, tgt.shape[0], self.frame_batch):
-                writer.submit(self.synthesize(tgt[s:s + self.frame_batch], cam_strategy, t0=s, use_selected_f2pts=use_selected_f2pts), s)
-            return writer.close()
+            for k, (s, nb) in enumerate(batches):
+                preds = self.synthesize(tgt[s:s + nb], cam_strategy, t0=s, use_selected_f2pts=use_selected_f2pts)
+                writer.submit(preds, s)
+                self._submit_fused(fused, refs, k, preds, s)
+            try:
+                paths = writer.close()
+            finally:
+                self._close_fused(fused, refs)
+            return paths
         outputs = []
         for s in range(0, tgt.shape[0], self.frame_batch):
             preds = self.synthesize(tgt[s:s + self.frame_batch], cam_strategy, t0=s, use_selected_f2pts=use_selected_f2pts).cpu().numpy()
@@ -342,6 +401,7 @@ class Viewer(Imitator):
 
     @torch.no_grad()
     def inference(self, tgt_smpls, cam_strategy="smooth", output_dir="", visualizer=None, verbose=True):
+        """opt.fuse_output = "src_out" adds "pred_fused.avi" (a novel view has no reference frames: "src_ref_out" raises)."""
         return super().inference(tgt_smpls, cam_strategy=cam_strategy, output_dir=output_dir, prefix="pred_",
                                  visualizer=visualizer, verbose=verbose)
 

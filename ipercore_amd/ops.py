@@ -1416,6 +1416,73 @@ def jpeg_scan(u8, quality=90, mcus_per_segment=None):
     return scans, nbytes
 
 
+def png_rows_per_segment(H, W, most=16):
+    """The largest of 16, 8, 4, 2, 1 rows (at most ``most``) whose deflate segment of an (H, W) frame ``png_deflate`` takes (a segment holds
+    at most 65 535 raw bytes: 16 rows up to W = 1 364, which covers every square frame up to 1024 and not a fused canvas of three 512 panels)."""
+    lib = _lib.lib()
+    for r in (16, 8, 4, 2, 1):
+        if r <= int(most) and lib.lwg_png_stream_capacity(int(H), int(W), r):
+            return r
+    raise ValueError(f"png_deflate: no encoding for {H} x {W} frames (one row is more than a 65535-byte segment)")
+
+
+def fuse_source_panel(src_img):
+    """(ns,3,S,S) (or (1,ns,3,S,S)) fp32 source images in [-1,1] on the device -> the (S,Wp,3) uint8 RGB source panel of the reference's
+    comparison video (fuse_source, tools/utils/multimedia/video.py:297-357; include/lwg_hip.h lwg_fuse_sources_u8).  The panel is what the
+    reference's CODE shows, its two quirks included: ns = 7 shows sources 0..3 (padded to eight paths, then handed to fuse_four_images), and
+    ns >= 8 shows sources 0, 1, 4, 5 in one quarter-size column (fuse_eight_images hands four paths to fuse_two_images, which reads two)."""
+    if not src_img.is_cuda:
+        raise RuntimeError("fuse_source_panel needs a device tensor: there is no CPU fallback")
+    if src_img.dim() == 5 and src_img.shape[0] == 1:
+        src_img = src_img[0]
+    if src_img.dim() != 4 or src_img.shape[1] != 3 or src_img.shape[2] != src_img.shape[3] or src_img.dtype != torch.float32:
+        raise ValueError("fuse_source_panel takes a (ns,3,S,S) fp32 tensor")
+    ns, _, S, _ = src_img.shape
+    lib = _lib.lib()
+    Wp = lib.lwg_fuse_panel_width(ns, S)
+    if Wp == 0:
+        raise ValueError(f"fuse_source_panel: no panel for {ns} sources of {S} x {S} (ns >= 1; 2..7 sources need an even size, 8 and more S % 4 == 0)")
+    panel = torch.empty(S, Wp, 3, device=src_img.device, dtype=torch.uint8)
+    _lib.check(lib.lwg_fuse_sources_u8(_ptr(src_img.contiguous()), ns, S, _ptr(panel, torch.uint8), _stream()), "lwg_fuse_sources_u8")
+    return panel
+
+
+def fuse_canvas(panel, refs, outs, pad=10, pad_val=0):
+    """panel (S,Wp,3) uint8 (``fuse_source_panel``), refs (B,S,S,3) uint8 RGB or None, outs: one (B,3,S,S) fp32 tensor or a sequence of 1..4 ->
+    the (B,S,Wc,3) uint8 canvas [panel | pad | ref | pad | out0 | pad | out1 ...] of the reference's merge_multi_outs / merge_src_out
+    (video.py:173-213; include/lwg_hip.h lwg_fuse_canvas_u8), its out regions ``frames_to_u8``'s bytes.  Device tensors only."""
+    if torch.is_tensor(outs):
+        outs = (outs,)
+    outs = tuple(outs)
+    if not 1 <= len(outs) <= 4:
+        raise ValueError("fuse_canvas takes 1 .. 4 output tensors")
+    for t in (panel, refs) + outs:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("fuse_canvas needs device tensors: there is no CPU fallback")
+    B, C, S, S2 = outs[0].shape
+    if C != 3 or S != S2 or any(tuple(o.shape) != (B, 3, S, S) or o.dtype != torch.float32 for o in outs):
+        raise ValueError("fuse_canvas: every output is a (B,3,S,S) fp32 tensor of the same shape")
+    if panel.dtype != torch.uint8 or panel.dim() != 3 or panel.shape[0] != S or panel.shape[2] != 3:
+        raise ValueError("fuse_canvas: the panel is a (S,Wp,3) uint8 tensor")
+    if refs is not None and (refs.dtype != torch.uint8 or tuple(refs.shape) != (B, S, S, 3)):
+        raise ValueError("fuse_canvas: the reference frames are a (B,S,S,3) uint8 tensor")
+    Wp, pad, pad_val = int(panel.shape[1]), int(pad), int(pad_val)
+    if pad < 0 or not 0 <= pad_val <= 255:
+        raise ValueError("fuse_canvas: pad >= 0 and 0 <= pad_val <= 255")
+    Wc = Wp + ((refs is not None) + len(outs)) * (S + pad)
+    canvas = torch.empty(B, S, Wc, 3, device=outs[0].device, dtype=torch.uint8)
+    if B == 0:
+        return canvas
+    outs = tuple(o.contiguous() for o in outs)
+    ptrs = (ctypes.c_void_p * len(outs))(*[_ptr(o) for o in outs])
+    err = _lib.lib().lwg_fuse_canvas_u8(_ptr(panel.contiguous(), torch.uint8), Wp, None if refs is None else _ptr(refs.contiguous(), torch.uint8), ptrs,
+                                        len(outs), B, S, pad, pad_val, _ptr(canvas, torch.uint8), _stream())
+    if err == 1:
+        raise ValueError(f"fuse_canvas: no canvas for S = {S}, panel width {Wp}, pad {pad}, {len(outs)} outputs (include/lwg_hip.h lwg_fuse_canvas_u8)")
+    _lib.check(err, "lwg_fuse_canvas_u8")
+    return canvas
+
+
 # ---------------------------------------------------------------------------------------------- backward of the convs
 def conv2d_wgrad(x0, spec, dy, x1=None, out_hw=None, ycoff=0):
     """dW of the conv described by ``spec`` for inputs x0 (x1) and output gradient dy (laid out like the forward y) ->

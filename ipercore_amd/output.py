@@ -22,6 +22,11 @@ PCIe (the lengths first, then - from the helper thread that waits for them - the
 the constant headers in front (``jpeg_from_scan``).  ``"jpeg"`` writes ``"{prefix}{t:0>8}.jpg"`` files, ``"mjpeg"`` ONE Motion-JPEG AVI file
 (``MjpegAviWriter``: the container is ``struct.pack`` on the host, no codec library).
 
+``FrameWriter(fuse=FuseSpec(panel, ...))`` (opt-in; ``opt.fuse_output`` of the runners) hands the encoders the reference's comparison canvas
+instead of the bare frame: ``lwg_fuse_canvas_u8`` composes [source panel | pad | reference frame | pad | frame ...] (fuse_src_ref_multi_outputs,
+tools/utils/multimedia/video.py:451-505) from the fp32 frames in the launch that would have converted them; everything behind that one step is
+the same writer.  ``RefFrames`` feeds the reference frames (an array, or image paths decoded a bounded number of batches ahead).
+
 File names are the reference's: ``"{prefix}{t:0>8}.png"`` (imitator.py:369).  Pixels on disk are RGB, exactly what
 ``cv2.imwrite`` stores for the BGR array the reference hands it.
 """
@@ -229,9 +234,92 @@ class MjpegAviWriter(object):
         return [self.path]
 
 
+class FuseSpec(object):
+    """What ``FrameWriter(fuse=...)`` composes around every frame: the source panel (``ops.fuse_source_panel``: (S,Wp,3) uint8 on the device),
+    ``pad`` columns of ``pad_val`` between the regions, and whether a reference frame stands between the panel and the outputs (``with_ref``:
+    every ``submit`` then needs ``ref``) - fuse_src_ref_multi_outputs' ``pad`` / ``pad_val`` and, without the reference, fuse_source_output."""
+
+    def __init__(self, panel, pad=10, pad_val=0, with_ref=True):
+        self.panel, self.pad, self.pad_val, self.with_ref = panel, int(pad), int(pad_val), bool(with_ref)
+        if self.pad < 0 or not 0 <= self.pad_val <= 255:
+            raise ValueError("FuseSpec: pad >= 0 and 0 <= pad_val <= 255")
+
+
+class RefFrames(object):
+    """The reference frames of a fused video, batch by batch, as pinned host tensors: ``get(k)`` -> (n_k,S,S,3) uint8 RGB of batch k of
+    ``batches`` = [(first frame, frames), ...], in order, each once.  ``ref_imgs``: a (n,S,S,3) uint8 array / tensor (a device tensor is
+    sliced and returned as it is), or n image paths - decoded by PIL on ``THREADS`` threads into a ring of pinned buffers, ``AHEAD`` batches in
+    front of the consumer; a file that is not S x S is resized as ``imitator.load_images`` resizes (PIL bilinear: close to, not identical
+    with, cv2.resize).  ``done(k, event)``: batch k's buffer may be decoded into again once ``event`` (its upload) has passed."""
+
+    AHEAD = 2
+    THREADS = 4
+
+    def __init__(self, ref_imgs, n_frames, S, batches):
+        self.S, self.batches = int(S), [(int(s), int(n)) for s, n in batches]
+        self._paths = self._array = self._pool = None
+        if isinstance(ref_imgs, (list, tuple)) and all(isinstance(p, (str, os.PathLike)) for p in ref_imgs):
+            n = len(ref_imgs)
+            self._paths = [os.fspath(p) for p in ref_imgs]
+        else:
+            a = ref_imgs if torch.is_tensor(ref_imgs) else torch.from_numpy(np.ascontiguousarray(ref_imgs))
+            if a.dtype != torch.uint8 or a.dim() != 4 or tuple(a.shape[1:]) != (self.S, self.S, 3):
+                raise ValueError("ref_imgs: a (n,%d,%d,3) uint8 RGB array or a list of image paths" % (self.S, self.S))
+            n = a.shape[0]
+            self._array = a
+        if n != int(n_frames):
+            raise ValueError("ref_imgs holds %d frames for %d target frames (the reference asserts the same)" % (n, int(n_frames)))
+        if self._paths is not None and self.batches:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(self.THREADS)
+            most = max(nb for _, nb in self.batches)
+            self._ring = [torch.empty((most, self.S, self.S, 3), dtype=torch.uint8, pin_memory=torch.cuda.is_available()) for _ in range(self.AHEAD + 1)]
+            self._busy = [None] * len(self._ring)          # the upload event of the batch that used the buffer last
+            self._futures = {}
+            self._scheduled = 0
+            self._fill(0)
+
+    def _decode(self, path, dst):
+        from PIL import Image
+        im = Image.open(path).convert("RGB")
+        if im.size != (self.S, self.S):
+            im = im.resize((self.S, self.S), Image.BILINEAR)
+        dst.copy_(torch.from_numpy(np.array(im)))
+
+    def _fill(self, k):
+        """Schedule the decodes of every batch up to k + AHEAD."""
+        while self._scheduled < min(len(self.batches), k + self.AHEAD + 1):
+            j = self._scheduled
+            slot = j % len(self._ring)
+            if self._busy[slot] is not None:
+                self._busy[slot].synchronize()
+                self._busy[slot] = None
+            s, n = self.batches[j]
+            self._futures[j] = [self._pool.submit(self._decode, self._paths[s + i], self._ring[slot][i]) for i in range(n)]
+            self._scheduled += 1
+
+    def get(self, k):
+        s, n = self.batches[k]
+        if self._array is not None:
+            return self._array[s:s + n]
+        for f in self._futures.pop(k):
+            f.result()
+        return self._ring[k % len(self._ring)][:n]
+
+    def done(self, k, event=None):
+        if self._pool is not None:
+            self._busy[k % len(self._ring)] = event
+            self._fill(k + 1)
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+
+
 class FrameWriter(object):
     """Asynchronous ``(B,3,S,S)`` fp32 device frames -> PNG files (encoder "host" | "device"), JPEG files ("jpeg") or one Motion-JPEG AVI file
-    ("mjpeg").  ``submit`` returns immediately; ``close`` joins."""
+    ("mjpeg": ``"{prefix}{video_name}"``).  ``submit`` returns immediately; ``close`` joins.  ``fuse``: a ``FuseSpec`` - what is encoded is the
+    comparison canvas around every frame instead of the frame (device frames only)."""
 
     DEVICE_WORKERS = 4          # encoder="device": a worker checksums and writes (zlib.crc32 and the file write release the GIL); not sized by the machine
     ROWS_PER_SEGMENT = 16       # encoder="device": scanlines per deflate block (include/lwg_hip.h lwg_png_deflate_u8)
@@ -239,7 +327,12 @@ class FrameWriter(object):
     CODED_RING = 8              # encoder="jpeg" | "mjpeg": a batch passes two copies and their helper thread before a worker sees it; with 4 the
                                 # producer waits for the per-file form (GPU side 1 069 against 1 165 frames/s, profiles/jpeg_device_ab*.txt)
 
-    def __init__(self, output_dir, prefix="pred_", workers=None, ring=None, compress_level=1, encoder="host", quality=90, fps=25):
+    def __init__(self, output_dir, prefix="pred_", workers=None, ring=None, compress_level=1, encoder="host", quality=90, fps=25, fuse=None,
+                 video_name="video.avi"):
+        if fuse is not None and not isinstance(fuse, FuseSpec):
+            raise TypeError("fuse must be a FuseSpec or None")
+        self.fuse, self.video_name = fuse, str(video_name)
+        self.ref_uploaded = None                           # fuse: the event behind the last upload of host reference frames (RefFrames.done)
         if encoder not in ("host", "device", "jpeg", "mjpeg"):
             raise ValueError("encoder must be 'host', 'device', 'jpeg' or 'mjpeg', not %r" % (encoder,))
         self.encoder = encoder
@@ -372,19 +465,54 @@ class FrameWriter(object):
             del scans
             batch["ready"].set()
 
-    def _submit_coded(self, pred, t0):
+    def _upload(self, host, device):
+        """Host frames -> a device tensor through the copy stream (asynchronous when ``host`` is pinned); the current stream waits for it."""
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=device)
+        cur = torch.cuda.current_stream(device)
+        with torch.cuda.stream(self._copy_stream):
+            dev = torch.empty(tuple(host.shape), dtype=host.dtype, device=device)
+            dev.copy_(host, non_blocking=True)
+            self.ref_uploaded = torch.cuda.Event()
+            self.ref_uploaded.record(self._copy_stream)
+        cur.wait_event(self.ref_uploaded)
+        dev.record_stream(cur)
+        return dev
+
+    def _to_u8(self, pred, ref=None, more=()):
+        """THE conversion step in front of every encoder: device frames (B,3,S,S) fp32 -> (B,H,W,3) uint8 RGB on the device - the frame itself
+        (``lwg_frames_to_u8``), or with ``fuse`` the comparison canvas around it (``lwg_fuse_canvas_u8``: H = S, W = Wc)."""
         from . import ops
-        B, H, W = pred.shape[0], pred.shape[2], pred.shape[3]
+        if self.fuse is None:
+            if ref is not None or len(more):
+                raise ValueError("FrameWriter.submit: ref / more need FrameWriter(fuse=...)")
+            return ops.frames_to_u8(pred.contiguous())
+        if self.fuse.with_ref:
+            if ref is None:
+                raise ValueError("FrameWriter(fuse=FuseSpec(with_ref=True)).submit needs the batch's reference frames")
+            if not torch.is_tensor(ref):
+                ref = torch.from_numpy(np.ascontiguousarray(ref))
+            if not ref.is_cuda:
+                ref = self._upload(ref, pred.device)
+        else:
+            ref = None
+        return ops.fuse_canvas(self.fuse.panel, ref, (pred,) + tuple(more), self.fuse.pad, self.fuse.pad_val)
+
+    def _submit_coded(self, pred, t0, ref, more):
+        from . import ops
+        B = pred.shape[0]
         self._slots.acquire()                              # blocks while ``ring`` batches are still being copied or written
         try:
+            u8 = self._to_u8(pred, ref, more)
+            H, W = u8.shape[1], u8.shape[2]
             ri = min((W + 7) // 8, ops.jpeg_max_mcus_per_segment())
-            scans, nbytes = ops.jpeg_scan(ops.frames_to_u8(pred.contiguous()), self.quality, ri)
+            scans, nbytes = ops.jpeg_scan(u8, self.quality, ri)
             nbytes_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
             if self._copy_stream is None:
                 self._copy_stream = torch.cuda.Stream(device=pred.device)
             if self.encoder == "mjpeg" and self._avi is None:
                 self._t_first = int(t0)
-                self._avi = MjpegAviWriter(os.path.join(self.output_dir, self.prefix + "video.avi"), W, H, self.fps)
+                self._avi = MjpegAviWriter(os.path.join(self.output_dir, self.prefix + self.video_name), W, H, self.fps)
             produced = torch.cuda.Event()
             produced.record(torch.cuda.current_stream(pred.device))
             with torch.cuda.stream(self._copy_stream):
@@ -406,14 +534,18 @@ class FrameWriter(object):
             self._jobs.put((batch, i))
 
     # ---- producer side ---------------------------------------------------------------------------------------
-    def submit(self, pred, t0):
-        """pred: (B,3,S,S) fp32 frames t0 .. t0+B-1, on the device (or on the CPU: tests)."""
+    def submit(self, pred, t0, ref=None, more=()):
+        """pred: (B,3,S,S) fp32 frames t0 .. t0+B-1, on the device (or on the CPU: tests).  With ``fuse``: ref = the batch's (B,S,S,3) uint8
+        RGB reference frames (a device tensor, or a host tensor / array, which is uploaded on the copy stream) where the spec has them, and
+        ``more`` = up to three further (B,3,S,S) outputs shown behind ``pred``."""
         B = pred.shape[0]
+        if self.fuse is not None and not pred.is_cuda:
+            raise RuntimeError("FrameWriter(fuse=...) needs device frames: there is no CPU fallback")
         if self.coded:
             if not pred.is_cuda:
                 raise RuntimeError("FrameWriter(encoder=%r) needs device frames: there is no CPU fallback" % (self.encoder,))
             if B:
-                self._submit_coded(pred, t0)
+                self._submit_coded(pred, t0, ref, more)
             return
         event = None
         nbytes_host = None
@@ -421,10 +553,11 @@ class FrameWriter(object):
             raise RuntimeError("FrameWriter(encoder='device') needs device frames: there is no CPU fallback")
         if pred.is_cuda:
             from . import ops
-            u8 = ops.frames_to_u8(pred.contiguous())
+            u8 = self._to_u8(pred, ref, more)
+            H, W = u8.shape[1], u8.shape[2]
             nbytes = None
             if self.encoder == "device":                   # what is copied and handed to the workers is the streams, not the pixels
-                u8, nbytes = ops.png_deflate(u8, self.ROWS_PER_SEGMENT)
+                u8, nbytes = ops.png_deflate(u8, ops.png_rows_per_segment(H, W, self.ROWS_PER_SEGMENT))
                 nbytes_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
             host = self._host_buffer(tuple(u8.shape), True)
             if self._copy_stream is None:
@@ -442,10 +575,11 @@ class FrameWriter(object):
             if nbytes is not None:
                 nbytes.record_stream(self._copy_stream)
         else:
-            host = self._host_buffer((B, pred.shape[2], pred.shape[3], 3), False)
+            H, W = pred.shape[2], pred.shape[3]
+            host = self._host_buffer((B, H, W, 3), False)
             x = np.transpose(pred.detach().numpy().astype(np.float32), (0, 2, 3, 1))
             host.copy_(torch.from_numpy(((x + 1) / 2.0 * 255).astype(np.uint8)))
-        batch = {"host": host, "t0": int(t0), "left": B, "ready": threading.Event(), "nbytes": nbytes_host, "h": pred.shape[2], "w": pred.shape[3]}
+        batch = {"host": host, "t0": int(t0), "left": B, "ready": threading.Event(), "nbytes": nbytes_host, "h": H, "w": W}
         with self._cv:
             self._submitted += B
         threading.Thread(target=self._wait_copy, args=(batch, event), daemon=True).start()
