@@ -674,6 +674,26 @@ int lwg_jpeg_scan_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab
 size_t lwg_jpeg_scan_capacity(int H, int W, int mcus_per_segment);
 size_t lwg_jpeg_scan_ws_bytes(int B, int H, int W, int mcus_per_segment);
 int lwg_jpeg_max_mcus_per_segment(void);
+/* lwg_jpeg420_scan_u8: the same encoder with 4:2:0 chroma subsampling (opt-in through output.FrameWriter(subsampling="420"),
+ * opt.jpeg_subsampling; the default everywhere stays 4:4:4).  Arguments, buffers, launch structure (launch 2 is the same device code) and
+ * refusals as lwg_jpeg_scan_u8, with lwg_jpeg420_scan_capacity / _ws_bytes / _max_mcus_per_segment (64) in place of its helpers.
+ * Scan format (tests/jpeg420_emu.py is the definition; the kernels equal it byte for byte; output.jpeg_from_scan(subsampling="420") writes
+ * SOF0 with the sampling factors 0x22 for Y and 0x11 for Cb, Cr and every other header byte as for 4:4:4):
+ *   MCU = 16x16 pixels, raster order, ceil(W/16) x ceil(H/16) of them; H or W not a multiple of 16 is padded by replicating the last row /
+ *   column.  Six blocks per MCU: Y top-left, Y top-right, Y bottom-left, Y bottom-right, Cb, Cr.  Colour per pixel as above, clamped to
+ *   0..255; a chroma sample is (a + b + c + d + 2) >> 2 of the four clamped values of its 2x2 pixel square; then minus 128.  DCT,
+ *   quantiser, zigzag, Huffman coding, padding, stuffing and markers as above.  One DC predictor per component, following block order: the
+ *   Y predictor runs through the four Y blocks of an MCU and on into the next MCU; all three are 0 at the start of every segment.  Restart
+ *   interval = mcus_per_segment, counted in 16x16 MCUs.  capacity = MCUs x 6 x 208 x 2 + 2 (segments - 1).
+ *   What it costs: chroma detail.  Measured at quality 90 on 512x512 frames (profiles/jpeg420_ab.txt): smooth 51.4 -> 50.1 dB at 0.67 of the
+ *   bytes, smooth + noise 37.1 -> 36.7 dB at 0.69, constant-chroma content nothing; frames whose colour is noise-like lose most of their
+ *   chroma (the bench clip: 29.8 -> 19.0 dB at 0.48 of the bytes), and so does the source panel of a fused canvas, whose cells are already at
+ *   half or quarter size.  Launch 1: 4.45 us per 512x512 frame against 5.60 us at 4:4:4; 134 864 bytes of LDS at 64 MCUs per segment. */
+int lwg_jpeg420_scan_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint8_t* scans, int32_t* nbytes,
+                        lwg_stream_t stream);
+size_t lwg_jpeg420_scan_capacity(int H, int W, int mcus_per_segment);
+size_t lwg_jpeg420_scan_ws_bytes(int B, int H, int W, int mcus_per_segment);
+int lwg_jpeg420_max_mcus_per_segment(void);
 /* lwg_fuse_sources_u8 / lwg_fuse_canvas_u8: the comparison canvas of the reference's fuse_src_ref_multi_outputs
  * (tools/utils/multimedia/video.py:451-505), composed on the device (csrc/fuse_canvas.hip; the layout is csrc/lwg_fuse_geom.h's and
  * tests/fusecanvas_emu.py is the definition, which the kernels equal byte for byte; opt-in through output.FrameWriter(fuse=...)).

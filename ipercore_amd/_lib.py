@@ -164,6 +164,10 @@ _SIGS = {
     "lwg_jpeg_scan_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "lwg_jpeg_scan_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "lwg_jpeg_max_mcus_per_segment": (c_i, []),
+    "lwg_jpeg420_scan_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f, c_f]),
+    "lwg_jpeg420_scan_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "lwg_jpeg420_scan_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "lwg_jpeg420_max_mcus_per_segment": (c_i, []),
     "lwg_fuse_sources_u8": (c_i, [c_f, c_i, c_i, c_f, c_f]),
     "lwg_fuse_canvas_u8": (c_i, [c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_fuse_panel_width": (c_i, [c_i, c_i]),

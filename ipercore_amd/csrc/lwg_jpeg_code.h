@@ -38,6 +38,31 @@ static inline bool jpg_geom(int B, int H, int W, int ri, JpgGeom& g) {
 // words of launch 1's bit buffer: the unstuffed bytes of a full segment, one word of slack
 constexpr unsigned jpg_out_words(int ri) { return (unsigned)ri * (JPG_MCU_BYTES / 4u) + 2u; }
 
+// ---- 4:2:0 (lwg_jpeg420_scan_u8; tests/jpeg420_emu.py): an MCU is 16 x 16 pixels and six blocks - Y00 Y01 Y10 Y11 Cb Cr.  Launch 1 runs one wave
+// per block of the MCU, one lane per MCU of the segment; launch 2 is the 4:4:4 one, on a JpgGeom whose slot and cap follow the six-block MCU.
+constexpr int JPG420_NT = 384;                 // threads per workgroup of launch 1: six waves
+constexpr int JPG420_MAX_MCUS = 64;            // MCUs of a segment: one lane each
+constexpr unsigned JPG420_MCU_BYTES = 6u * JPG_BLOCK_BYTES;
+constexpr unsigned JPG420_PIX_STRIDE = 772u;   // LDS bytes of an MCU's 16 x 48 pixel bytes: 193 words, an odd word stride across the lanes
+
+static inline bool jpg420_geom(int B, int H, int W, int ri, JpgGeom& g) {
+    if (B <= 0 || H <= 0 || W <= 0 || ri <= 0 || ri > JPG420_MAX_MCUS || ri > 65535) return false;
+    if (H > 65535 || W > 65535) return false;                                         // SOF0 carries 16-bit sizes
+    const long long mcux = ((long long)W + 15) / 16, mcuy = ((long long)H + 15) / 16;
+    const long long nmcu = mcux * mcuy, nseg = (nmcu + ri - 1) / ri;
+    const long long cap = nmcu * 2ll * JPG420_MCU_BYTES + 2ll * (nseg - 1);
+    if (cap > 0x7fffffffll || nseg * B > 0x7fffffffll) return false;                  // nbytes is an int32; the grid is B nseg workgroups
+    g.B = B, g.H = H, g.W = W, g.ri = ri;
+    g.mcux = (int)mcux, g.nmcu = (int)nmcu, g.nseg = (int)nseg;
+    g.slot = ((2u * (unsigned)ri * JPG420_MCU_BYTES + 15u) & ~15u) + 16u;
+    g.meta = (unsigned)(((size_t)B * (size_t)nseg * 4u + 15u) & ~(size_t)15u);
+    g.cap = (size_t)cap;
+    return true;
+}
+constexpr unsigned jpg420_out_words(int ri) { return (unsigned)ri * (JPG420_MCU_BYTES / 4u) + 2u; }
+// bytes of launch 1's coefficients: int16 [64 positions][6 ri]: the thread of block k, MCU m at k ri + m
+constexpr unsigned jpg420_coef_bytes(int ri) { return 64u * 6u * (unsigned)ri * 2u; }
+
 // M[k][n] = rint(8192 a_k cos((2n + 1) k pi / 16)), a_0 = sqrt(1/8), a_k = sqrt(2/8)
 constexpr int JPG_DCT[8][8] = {
     {2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896},     {4017, 3406, 2276, 799, -799, -2276, -3406, -4017},

@@ -91,6 +91,11 @@ class Imitator(object):
         if self.output_format not in ("png", "jpeg", "mjpeg"):
             raise ValueError("opt.output_format must be 'png', 'jpeg' or 'mjpeg', not %r" % (self.output_format,))
         self.jpeg_quality = int(_opt_get(opt, "jpeg_quality", 90))
+        # the chroma format of "jpeg", "mjpeg" and the fused video: "444", or "420" (16 x 16 MCUs, chroma at half resolution: fewer bytes, the
+        # format players expect; chroma detail is lost); "png" ignores it
+        self.jpeg_subsampling = _opt_get(opt, "jpeg_subsampling", "444")
+        if self.jpeg_subsampling not in ("444", "420"):
+            raise ValueError("opt.jpeg_subsampling must be '444' or '420', not %r" % (self.jpeg_subsampling,))
         self.output_fps = float(_opt_get(opt, "output_fps", 25))
         # the reference's comparison video next to the usual output (services/run_imitator.py:169 -> fuse_src_ref_multi_outputs): "src_out" =
         # [source panel | pad | frame], "src_ref_out" = [source panel | pad | reference frame | pad | frame] (inference(..., ref_imgs=...)), one
@@ -313,7 +318,8 @@ class Imitator(object):
         from .output import FrameWriter
         if self.output_format == "png":
             return FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
-        return FrameWriter(output_dir, prefix=prefix, encoder=self.output_format, quality=self.jpeg_quality, fps=self.output_fps)
+        return FrameWriter(output_dir, prefix=prefix, encoder=self.output_format, quality=self.jpeg_quality, fps=self.output_fps,
+                           subsampling=self.jpeg_subsampling)
 
     def _fused_writer(self, output_dir, prefix, ref_imgs, n_frames, batches):
         """-> (writer, reference feed) of "{prefix}fused.avi", or (None, None) with opt.fuse_output unset.  Raises before a frame is made."""
@@ -331,7 +337,7 @@ class Imitator(object):
         refs = RefFrames(ref_imgs, n_frames, self.image_size, batches) if with_ref else None
         spec = FuseSpec(ops.fuse_source_panel(self.src_info["img"]), pad=self.fuse_pad, pad_val=self.fuse_pad_val, with_ref=with_ref)
         return FrameWriter(output_dir, prefix=prefix, encoder="mjpeg", quality=self.jpeg_quality, fps=self.output_fps, fuse=spec,
-                           video_name="fused.avi"), refs
+                           video_name="fused.avi", subsampling=self.jpeg_subsampling), refs
 
     @staticmethod
     def _submit_fused(fused, refs, k, preds, t0):

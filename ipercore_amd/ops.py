@@ -1383,16 +1383,33 @@ def png_deflate(u8, rows_per_segment=16):
     return streams, nbytes
 
 
-def jpeg_max_mcus_per_segment():
-    """The largest restart interval ``jpeg_scan`` takes (include/lwg_hip.h lwg_jpeg_max_mcus_per_segment)."""
-    return int(_lib.lib().lwg_jpeg_max_mcus_per_segment())
+_JPEG_ENTRIES = {"444": "lwg_jpeg", "420": "lwg_jpeg420"}      # subsampling -> the prefix of its four C entry points
 
 
-def jpeg_scan(u8, quality=90, mcus_per_segment=None):
+def _jpeg_entries(subsampling):
+    try:
+        return _JPEG_ENTRIES[subsampling]
+    except (KeyError, TypeError):
+        raise ValueError("jpeg subsampling must be '444' or '420', not %r" % (subsampling,)) from None
+
+
+def jpeg_mcu_size(subsampling="444"):
+    """Pixels along an MCU's side: 8 at 4:4:4, 16 at 4:2:0 (restart intervals count MCUs of that size)."""
+    return 8 if _jpeg_entries(subsampling) == "lwg_jpeg" else 16
+
+
+def jpeg_max_mcus_per_segment(subsampling="444"):
+    """The largest restart interval ``jpeg_scan`` takes (include/lwg_hip.h lwg_jpeg_max_mcus_per_segment, lwg_jpeg420_max_mcus_per_segment)."""
+    return int(getattr(_lib.lib(), _jpeg_entries(subsampling) + "_max_mcus_per_segment")())
+
+
+def jpeg_scan(u8, quality=90, mcus_per_segment=None, subsampling="444"):
     """(B,H,W,3) uint8 RGB device frames -> (scans (B, capacity) uint8, nbytes (B,) int32): scans[b, :nbytes[b]] is the entropy-coded scan of
     frame b's baseline JPEG (4:4:4, restart interval ``mcus_per_segment`` MCUs, default min(ceil(W / 8), the largest); include/lwg_hip.h
     lwg_jpeg_scan_u8; ``output.jpeg_from_scan`` wraps it into a file).  capacity is the worst case, several times the raw frame: copy
-    prefixes.  Bytes behind nbytes[b] are not written."""
+    prefixes.  Bytes behind nbytes[b] are not written.  ``subsampling="420"``: lwg_jpeg420_scan_u8 - 16 x 16 MCUs of four Y blocks and one
+    Cb and Cr block each, the default interval min(ceil(W / 16), the largest); chroma detail is lost (noise-like colour almost entirely)."""
+    entry = _jpeg_entries(subsampling)
     if not u8.is_cuda:
         raise RuntimeError("jpeg_scan needs a device tensor: there is no CPU fallback")
     if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
@@ -1401,18 +1418,20 @@ def jpeg_scan(u8, quality=90, mcus_per_segment=None):
     luma, chroma = jpeg_tables(quality)
     B, H, W, _ = u8.shape
     lib = _lib.lib()
-    ri = int(mcus_per_segment) if mcus_per_segment is not None else min((W + 7) // 8, lib.lwg_jpeg_max_mcus_per_segment())
-    cap = lib.lwg_jpeg_scan_capacity(H, W, ri)
-    nws = lib.lwg_jpeg_scan_ws_bytes(max(B, 1), H, W, ri)
+    most = getattr(lib, entry + "_max_mcus_per_segment")()
+    side = jpeg_mcu_size(subsampling)
+    ri = int(mcus_per_segment) if mcus_per_segment is not None else min((W + side - 1) // side, most)
+    cap = getattr(lib, entry + "_scan_capacity")(H, W, ri)
+    nws = getattr(lib, entry + "_scan_ws_bytes")(max(B, 1), H, W, ri)
     if cap == 0 or nws == 0:
-        raise ValueError(f"jpeg_scan: no encoding for {B} frames of {H} x {W} in segments of {ri} MCUs (1 .. {lib.lwg_jpeg_max_mcus_per_segment()})")
+        raise ValueError(f"jpeg_scan: no encoding for {B} frames of {H} x {W} in segments of {ri} MCUs (1 .. {most})")
     scans = torch.empty(B, cap, device=u8.device, dtype=torch.uint8)
     nbytes = torch.empty(B, device=u8.device, dtype=torch.int32)
     if B == 0:
         return scans, nbytes
     ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
-    _lib.check(lib.lwg_jpeg_scan_u8(_ptr(u8.contiguous(), torch.uint8), B, H, W, bytes(luma) + bytes(chroma), ri, _ptr(ws, torch.uint8),
-                                    _ptr(scans, torch.uint8), _ptr(nbytes, torch.int32), _stream()), "lwg_jpeg_scan_u8")
+    _lib.check(getattr(lib, entry + "_scan_u8")(_ptr(u8.contiguous(), torch.uint8), B, H, W, bytes(luma) + bytes(chroma), ri, _ptr(ws, torch.uint8),
+                                                _ptr(scans, torch.uint8), _ptr(nbytes, torch.int32), _stream()), entry + "_scan_u8")
     return scans, nbytes
 
 

@@ -20,7 +20,9 @@ pixels.
 frame's baseline JPEG scan on the device (4:4:4, fixed Annex K Huffman tables, restart segments; include/lwg_hip.h), only the CODED bytes cross
 PCIe (the lengths first, then - from the helper thread that waits for them - the used prefix of every frame's buffer), and a host thread puts
 the constant headers in front (``jpeg_from_scan``).  ``"jpeg"`` writes ``"{prefix}{t:0>8}.jpg"`` files, ``"mjpeg"`` ONE Motion-JPEG AVI file
-(``MjpegAviWriter``: the container is ``struct.pack`` on the host, no codec library).
+(``MjpegAviWriter``: the container is ``struct.pack`` on the host, no codec library).  ``subsampling="420"`` (opt-in; ``opt.jpeg_subsampling``)
+codes 16 x 16 MCUs with the chroma at half resolution instead (``lwg_jpeg420_scan_u8``): about half the bytes and the format players expect, at
+the price of chroma detail - nearly all of it on noise-like frames.
 
 ``FrameWriter(fuse=FuseSpec(panel, ...))`` (opt-in; ``opt.fuse_output`` of the runners) hands the encoders the reference's comparison canvas
 instead of the bare frame: ``lwg_fuse_canvas_u8`` composes [source panel | pad | reference frame | pad | frame ...] (fuse_src_ref_multi_outputs,
@@ -113,17 +115,28 @@ def _jpeg_marker(code, body):
     return struct.pack(">BBH", 0xFF, code, len(body) + 2) + body
 
 
+JPEG_SUBSAMPLINGS = ("444", "420")     # the device encoder's chroma formats; "444" is the default everywhere
+_JPEG_Y_SAMPLING = {"444": 0x11, "420": 0x22}
+
+
+def jpeg_check_subsampling(subsampling):
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("jpeg subsampling must be '444' or '420', not %r" % (subsampling,))
+    return subsampling
+
+
 @functools.lru_cache(maxsize=64)
-def jpeg_headers(w, h, quality, mcus_per_segment):
-    """Everything in front of the scan - SOI, APP0 JFIF, two DQT, SOF0 (8 bit, h x w, three components 1x1), four DHT, DRI, SOS: constant per
-    (w, h, quality, restart interval), built once."""
+def jpeg_headers(w, h, quality, mcus_per_segment, subsampling="444"):
+    """Everything in front of the scan - SOI, APP0 JFIF, two DQT, SOF0 (8 bit, h x w, three components; Y 1x1, with ``subsampling="420"``
+    2x2), four DHT, DRI, SOS: constant per (w, h, quality, restart interval, subsampling), built once."""
     w, h, ri = int(w), int(h), int(mcus_per_segment)
     if not (0 < w <= 65535 and 0 < h <= 65535 and 0 < ri <= 65535):
         raise ValueError("jpeg: sizes and the restart interval are 16-bit fields")
+    y_sampling = _JPEG_Y_SAMPLING[jpeg_check_subsampling(subsampling)]
     out = [b"\xff\xd8", _jpeg_marker(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
     for tq, table in enumerate(jpeg_tables(quality)):
         out.append(_jpeg_marker(0xDB, bytes([tq]) + bytes(table[k] for k in _JPEG_ZIGZAG)))
-    out.append(_jpeg_marker(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    out.append(_jpeg_marker(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, y_sampling, 0, 2, 0x11, 1, 3, 0x11, 1])))
     for tc_th, bits, vals in _JPEG_DHT:
         out.append(_jpeg_marker(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals)))
     out.append(_jpeg_marker(0xDD, struct.pack(">H", ri)))
@@ -131,10 +144,10 @@ def jpeg_headers(w, h, quality, mcus_per_segment):
     return b"".join(out)
 
 
-def jpeg_from_scan(scan, w, h, quality, mcus_per_segment):
-    """The entropy-coded scan of a (h, w) frame (``ops.jpeg_scan``: bytes, or a uint8 array) -> the bytes of the JFIF file: the headers, the
-    scan, EOI.  The host's share of the device encoder: one concatenation."""
-    return jpeg_headers(int(w), int(h), int(quality), int(mcus_per_segment)) + bytes(scan) + b"\xff\xd9"
+def jpeg_from_scan(scan, w, h, quality, mcus_per_segment, subsampling="444"):
+    """The entropy-coded scan of a (h, w) frame (``ops.jpeg_scan`` with the same ``subsampling``: bytes, or a uint8 array) -> the bytes of the
+    JFIF file: the headers, the scan, EOI.  The host's share of the device encoder: one concatenation."""
+    return jpeg_headers(int(w), int(h), int(quality), int(mcus_per_segment), subsampling) + bytes(scan) + b"\xff\xd9"
 
 
 class MjpegAviWriter(object):
@@ -328,7 +341,8 @@ class FrameWriter(object):
                                 # producer waits for the per-file form (GPU side 1 069 against 1 165 frames/s, profiles/jpeg_device_ab*.txt)
 
     def __init__(self, output_dir, prefix="pred_", workers=None, ring=None, compress_level=1, encoder="host", quality=90, fps=25, fuse=None,
-                 video_name="video.avi"):
+                 video_name="video.avi", subsampling="444"):
+        self.subsampling = jpeg_check_subsampling(subsampling)    # encoder="jpeg" | "mjpeg": the chroma format of the device encoder (the PNG encoders ignore it)
         if fuse is not None and not isinstance(fuse, FuseSpec):
             raise TypeError("fuse must be a FuseSpec or None")
         self.fuse, self.video_name = fuse, str(video_name)
@@ -379,7 +393,7 @@ class FrameWriter(object):
                     if batch["error"] is not None:
                         raise batch["error"]
                     a, n = batch["offs"][i], int(batch["nbytes"][i])
-                    data = jpeg_from_scan(batch["host"].numpy()[a:a + n], batch["w"], batch["h"], self.quality, batch["ri"])
+                    data = jpeg_from_scan(batch["host"].numpy()[a:a + n], batch["w"], batch["h"], self.quality, batch["ri"], self.subsampling)
                     if self._avi is not None:
                         path = self._avi.path
                         self._avi.add(t - self._t_first, data)
@@ -505,8 +519,9 @@ class FrameWriter(object):
         try:
             u8 = self._to_u8(pred, ref, more)
             H, W = u8.shape[1], u8.shape[2]
-            ri = min((W + 7) // 8, ops.jpeg_max_mcus_per_segment())
-            scans, nbytes = ops.jpeg_scan(u8, self.quality, ri)
+            side = ops.jpeg_mcu_size(self.subsampling)
+            ri = min((W + side - 1) // side, ops.jpeg_max_mcus_per_segment(self.subsampling))
+            scans, nbytes = ops.jpeg_scan(u8, self.quality, ri, self.subsampling)
             nbytes_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
             if self._copy_stream is None:
                 self._copy_stream = torch.cuda.Stream(device=pred.device)
