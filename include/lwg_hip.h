@@ -694,6 +694,40 @@ int lwg_jpeg420_scan_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* q
 size_t lwg_jpeg420_scan_capacity(int H, int W, int mcus_per_segment);
 size_t lwg_jpeg420_scan_ws_bytes(int B, int H, int W, int mcus_per_segment);
 int lwg_jpeg420_max_mcus_per_segment(void);
+/* lwg_jpeg_scan_opt_u8 / lwg_jpeg420_scan_opt_u8: the same two encoders with PER-FRAME Huffman tables (opt-in through
+ * output.FrameWriter(huffman="optimized"), opt.jpeg_huffman; the default everywhere stays the fixed Annex K tables).  Every frame is coded
+ * with four tables built from its own symbol counts, so the quantised coefficients - and the decoded pixels - are those of the fixed-table
+ * scan; only the scan's and the DHT segments' bytes change.  tests/jpeghuff_emu.py is the definition; the kernels equal it bit for bit.
+ * Arguments, buffers and refusals as lwg_jpeg_scan_u8, with lwg_jpeg_scan_opt_capacity / lwg_jpeg_scan_opt_ws_bytes (420: lwg_jpeg420_...)
+ * in place of its helpers and the same _max_mcus_per_segment; additionally tables (B, 4, 272) uint8, 4-byte aligned: per frame and table, in
+ * DHT order DC luminance, AC luminance, DC chrominance, AC chrominance, the 16 counts per code length and 256 symbol slots in code order
+ * (unused slots 0) - the body of a DHT segment behind its Tc/Th byte is the counts and the first sum(counts) symbols
+ * (output.jpeg_from_scan(tables=...)).  A DC code may have 16 bits, so a block is at most (16 + 11 + 63 (16 + 10) + 7) / 8 = 209 bytes;
+ * capacity = MCUs x blocks x 212 x 2 + 2 (segments - 1).  Four launches on `stream`:
+ *   1. statistics: the front half of the fixed-table launch 1 (pixels, colour, DCT, quantiser, zigzag, DC differences), then one lane per
+ *      block counts its symbols - DC size categories, (run << 4) | size, 0xF0 per ZRL, 0x00 per EOB - into a 544-word histogram in LDS with
+ *      LDS integer atomics; the workgroup stores it to its segment's place in ws.  No global atomics, nothing to zero, deterministic.
+ *   2. tables, one wave per (frame, table): sums the segments' histograms and runs Annex K.2 as libjpeg 6b codes it - 257 slots (slot 256,
+ *      count 1, reserves the all-1-bits code); merge the slot of least non-zero count (ties: the LARGEST index) with the next such slot
+ *      until one is left, 64-bit sums; limit the lengths to 16 bits; take the reserved code away; symbols in (length before limiting, value)
+ *      order.  Writes `tables` and the coder's 544 words code | length << 16 (DC luminance[16], DC chrominance[16], AC luminance[256], AC
+ *      chrominance[256]).
+ *   3. coding: the fixed-table launch 1 with the frame's 544 words in place of the constant ones.  4. packing: the fixed-table launch 2.
+ * lwg_jpeg_hist_u8 / lwg_jpeg420_hist_u8 run step 1 alone and sum it: hist (B, 4, 256) uint32, DHT order (the DC rows are 0 from symbol 16
+ * on); ws as for the _scan_opt_ entry point of the format.  lwg_jpeg_huff_tables runs step 2 alone on counts given by the caller: hist (B, 4,
+ * 256) uint32 (ANY values: lengths before limiting reach 256) -> tables (B, 4, 272) and codes (B, 544) uint32; a DC table's symbols from 16 on
+ * are in `tables` only.  All counts 0: the empty table (counts 0, no symbols).  It refuses NULL or unaligned pointers and B <= 0. */
+int lwg_jpeg_scan_opt_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint8_t* scans, int32_t* nbytes,
+                         uint8_t* tables, lwg_stream_t stream);
+size_t lwg_jpeg_scan_opt_capacity(int H, int W, int mcus_per_segment);
+size_t lwg_jpeg_scan_opt_ws_bytes(int B, int H, int W, int mcus_per_segment);
+int lwg_jpeg420_scan_opt_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint8_t* scans, int32_t* nbytes,
+                            uint8_t* tables, lwg_stream_t stream);
+size_t lwg_jpeg420_scan_opt_capacity(int H, int W, int mcus_per_segment);
+size_t lwg_jpeg420_scan_opt_ws_bytes(int B, int H, int W, int mcus_per_segment);
+int lwg_jpeg_hist_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint32_t* hist, lwg_stream_t stream);
+int lwg_jpeg420_hist_u8(const uint8_t* u8, int B, int H, int W, const uint8_t* qtab, int mcus_per_segment, void* ws, uint32_t* hist, lwg_stream_t stream);
+int lwg_jpeg_huff_tables(const uint32_t* hist, int B, uint8_t* tables, uint32_t* codes, lwg_stream_t stream);
 /* lwg_fuse_sources_u8 / lwg_fuse_canvas_u8: the comparison canvas of the reference's fuse_src_ref_multi_outputs
  * (tools/utils/multimedia/video.py:451-505), composed on the device (csrc/fuse_canvas.hip; the layout is csrc/lwg_fuse_geom.h's and
  * tests/fusecanvas_emu.py is the definition, which the kernels equal byte for byte; opt-in through output.FrameWriter(fuse=...)).

@@ -168,6 +168,15 @@ _SIGS = {
     "lwg_jpeg420_scan_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
     "lwg_jpeg420_scan_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
     "lwg_jpeg420_max_mcus_per_segment": (c_i, []),
+    "lwg_jpeg_scan_opt_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f, c_f, c_f]),
+    "lwg_jpeg_scan_opt_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "lwg_jpeg_scan_opt_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "lwg_jpeg420_scan_opt_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f, c_f, c_f]),
+    "lwg_jpeg420_scan_opt_capacity": (ctypes.c_size_t, [c_i, c_i, c_i]),
+    "lwg_jpeg420_scan_opt_ws_bytes": (ctypes.c_size_t, [c_i, c_i, c_i, c_i]),
+    "lwg_jpeg_hist_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f]),
+    "lwg_jpeg420_hist_u8": (c_i, [c_f, c_i, c_i, c_i, ctypes.c_char_p, c_i, c_f, c_f, c_f]),
+    "lwg_jpeg_huff_tables": (c_i, [c_f, c_i, c_f, c_f, c_f]),
     "lwg_fuse_sources_u8": (c_i, [c_f, c_i, c_i, c_f, c_f]),
     "lwg_fuse_canvas_u8": (c_i, [c_f, c_i, c_f, ctypes.POINTER(ctypes.c_void_p), c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "lwg_fuse_panel_width": (c_i, [c_i, c_i]),

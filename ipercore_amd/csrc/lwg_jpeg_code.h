@@ -20,21 +20,22 @@ struct JpgGeom {
     size_t cap;               // bytes of a frame's scan buffer
 };
 
-// false: arguments the encoder does not take
-static inline bool jpg_geom(int B, int H, int W, int ri, JpgGeom& g) {
-    if (B <= 0 || H <= 0 || W <= 0 || ri <= 0 || ri > JPG_MAX_MCUS || ri > 65535) return false;
+// false: arguments the encoder does not take.  side: pixels along an MCU's side; mcu_bytes: the bound of an MCU's coded bytes
+static inline bool jpg_geom_of(int B, int H, int W, int ri, int side, int most, unsigned mcu_bytes, JpgGeom& g) {
+    if (B <= 0 || H <= 0 || W <= 0 || ri <= 0 || ri > most || ri > 65535) return false;
     if (H > 65535 || W > 65535) return false;                                         // SOF0 carries 16-bit sizes
-    const long long mcux = ((long long)W + 7) / 8, mcuy = ((long long)H + 7) / 8;
+    const long long mcux = ((long long)W + side - 1) / side, mcuy = ((long long)H + side - 1) / side;
     const long long nmcu = mcux * mcuy, nseg = (nmcu + ri - 1) / ri;
-    const long long cap = nmcu * 2ll * JPG_MCU_BYTES + 2ll * (nseg - 1);
+    const long long cap = nmcu * 2ll * mcu_bytes + 2ll * (nseg - 1);
     if (cap > 0x7fffffffll || nseg * B > 0x7fffffffll) return false;                  // nbytes is an int32; the grid is B nseg workgroups
     g.B = B, g.H = H, g.W = W, g.ri = ri;
     g.mcux = (int)mcux, g.nmcu = (int)nmcu, g.nseg = (int)nseg;
-    g.slot = ((2u * (unsigned)ri * JPG_MCU_BYTES + 15u) & ~15u) + 16u;
+    g.slot = ((2u * (unsigned)ri * mcu_bytes + 15u) & ~15u) + 16u;
     g.meta = (unsigned)(((size_t)B * (size_t)nseg * 4u + 15u) & ~(size_t)15u);
     g.cap = (size_t)cap;
     return true;
 }
+static inline bool jpg_geom(int B, int H, int W, int ri, JpgGeom& g) { return jpg_geom_of(B, H, W, ri, 8, JPG_MAX_MCUS, JPG_MCU_BYTES, g); }
 // words of launch 1's bit buffer: the unstuffed bytes of a full segment, one word of slack
 constexpr unsigned jpg_out_words(int ri) { return (unsigned)ri * (JPG_MCU_BYTES / 4u) + 2u; }
 
@@ -45,23 +46,25 @@ constexpr int JPG420_MAX_MCUS = 64;            // MCUs of a segment: one lane ea
 constexpr unsigned JPG420_MCU_BYTES = 6u * JPG_BLOCK_BYTES;
 constexpr unsigned JPG420_PIX_STRIDE = 772u;   // LDS bytes of an MCU's 16 x 48 pixel bytes: 193 words, an odd word stride across the lanes
 
-static inline bool jpg420_geom(int B, int H, int W, int ri, JpgGeom& g) {
-    if (B <= 0 || H <= 0 || W <= 0 || ri <= 0 || ri > JPG420_MAX_MCUS || ri > 65535) return false;
-    if (H > 65535 || W > 65535) return false;                                         // SOF0 carries 16-bit sizes
-    const long long mcux = ((long long)W + 15) / 16, mcuy = ((long long)H + 15) / 16;
-    const long long nmcu = mcux * mcuy, nseg = (nmcu + ri - 1) / ri;
-    const long long cap = nmcu * 2ll * JPG420_MCU_BYTES + 2ll * (nseg - 1);
-    if (cap > 0x7fffffffll || nseg * B > 0x7fffffffll) return false;                  // nbytes is an int32; the grid is B nseg workgroups
-    g.B = B, g.H = H, g.W = W, g.ri = ri;
-    g.mcux = (int)mcux, g.nmcu = (int)nmcu, g.nseg = (int)nseg;
-    g.slot = ((2u * (unsigned)ri * JPG420_MCU_BYTES + 15u) & ~15u) + 16u;
-    g.meta = (unsigned)(((size_t)B * (size_t)nseg * 4u + 15u) & ~(size_t)15u);
-    g.cap = (size_t)cap;
-    return true;
-}
+static inline bool jpg420_geom(int B, int H, int W, int ri, JpgGeom& g) { return jpg_geom_of(B, H, W, ri, 16, JPG420_MAX_MCUS, JPG420_MCU_BYTES, g); }
 constexpr unsigned jpg420_out_words(int ri) { return (unsigned)ri * (JPG420_MCU_BYTES / 4u) + 2u; }
 // bytes of launch 1's coefficients: int16 [64 positions][6 ri]: the thread of block k, MCU m at k ri + m
 constexpr unsigned jpg420_coef_bytes(int ri) { return 64u * 6u * (unsigned)ri * 2u; }
+
+// ---- per-frame Huffman tables (lwg_jpeg_scan_opt_u8, lwg_jpeg420_scan_opt_u8; tests/jpeghuff_emu.py): a DC code may have 16 bits, so a block is at
+// most (16 + 11 + 63 (16 + 10) + 7) / 8 = 209 bytes; slots, capacity and bit buffers follow the next multiple of 4 (their word counts are bytes / 4).
+constexpr unsigned JPG_OPT_BLOCK_BYTES = 212u;
+constexpr int JPG_HIST_WORDS = 2 * 16 + 2 * 256;   // a histogram, and a frame's code words, in the JpgCodes layout below
+constexpr int JPG_DHT_BYTES = 16 + 256;            // a table for the host: codes per length 1 .. 16, then the symbols in code order (unused slots 0)
+static_assert(JPG_OPT_BLOCK_BYTES % 4u == 0 && JPG_OPT_BLOCK_BYTES >= 209u, "the block bound is whole words");
+
+static inline bool jpg_geom_opt(int B, int H, int W, int ri, JpgGeom& g) { return jpg_geom_of(B, H, W, ri, 8, JPG_MAX_MCUS, 3u * JPG_OPT_BLOCK_BYTES, g); }
+static inline bool jpg420_geom_opt(int B, int H, int W, int ri, JpgGeom& g) {
+    return jpg_geom_of(B, H, W, ri, 16, JPG420_MAX_MCUS, 6u * JPG_OPT_BLOCK_BYTES, g);
+}
+// words of launch 1's bit buffer for nb blocks per MCU of bb bytes each
+constexpr unsigned jpg_out_words_of(int ri, unsigned nb, unsigned bb) { return (unsigned)ri * (nb * bb / 4u) + 2u; }
+static_assert(jpg_out_words_of(7, 3u, JPG_BLOCK_BYTES) == jpg_out_words(7) && jpg_out_words_of(7, 6u, JPG_BLOCK_BYTES) == jpg420_out_words(7), "one rule");
 
 // M[k][n] = rint(8192 a_k cos((2n + 1) k pi / 16)), a_0 = sqrt(1/8), a_k = sqrt(2/8)
 constexpr int JPG_DCT[8][8] = {

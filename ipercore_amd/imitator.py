@@ -96,6 +96,11 @@ class Imitator(object):
         self.jpeg_subsampling = _opt_get(opt, "jpeg_subsampling", "444")
         if self.jpeg_subsampling not in ("444", "420"):
             raise ValueError("opt.jpeg_subsampling must be '444' or '420', not %r" % (self.jpeg_subsampling,))
+        # the Huffman tables of "jpeg", "mjpeg" and the fused video: "fixed" (Annex K's), or "optimized" (every frame coded with tables built on
+        # the device from its own symbols: the same pixels in fewer bytes, two more launches per batch)
+        self.jpeg_huffman = _opt_get(opt, "jpeg_huffman", "fixed")
+        if self.jpeg_huffman not in ("fixed", "optimized"):
+            raise ValueError("opt.jpeg_huffman must be 'fixed' or 'optimized', not %r" % (self.jpeg_huffman,))
         self.output_fps = float(_opt_get(opt, "output_fps", 25))
         # the reference's comparison video next to the usual output (services/run_imitator.py:169 -> fuse_src_ref_multi_outputs): "src_out" =
         # [source panel | pad | frame], "src_ref_out" = [source panel | pad | reference frame | pad | frame] (inference(..., ref_imgs=...)), one
@@ -319,7 +324,7 @@ class Imitator(object):
         if self.output_format == "png":
             return FrameWriter(output_dir, prefix=prefix, encoder=self.png_encoder)
         return FrameWriter(output_dir, prefix=prefix, encoder=self.output_format, quality=self.jpeg_quality, fps=self.output_fps,
-                           subsampling=self.jpeg_subsampling)
+                           subsampling=self.jpeg_subsampling, huffman=self.jpeg_huffman)
 
     def _fused_writer(self, output_dir, prefix, ref_imgs, n_frames, batches):
         """-> (writer, reference feed) of "{prefix}fused.avi", or (None, None) with opt.fuse_output unset.  Raises before a frame is made."""
@@ -337,7 +342,8 @@ class Imitator(object):
         refs = RefFrames(ref_imgs, n_frames, self.image_size, batches) if with_ref else None
         spec = FuseSpec(ops.fuse_source_panel(self.src_info["img"]), pad=self.fuse_pad, pad_val=self.fuse_pad_val, with_ref=with_ref)
         return FrameWriter(output_dir, prefix=prefix, encoder="mjpeg", quality=self.jpeg_quality, fps=self.output_fps, fuse=spec,
-                           video_name="fused.avi", subsampling=self.jpeg_subsampling), refs
+                           video_name="fused.avi", subsampling=self.jpeg_subsampling,
+                           huffman=self.jpeg_huffman), refs
 
     @staticmethod
     def _submit_fused(fused, refs, k, preds, t0):

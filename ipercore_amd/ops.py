@@ -1403,17 +1403,13 @@ def jpeg_max_mcus_per_segment(subsampling="444"):
     return int(getattr(_lib.lib(), _jpeg_entries(subsampling) + "_max_mcus_per_segment")())
 
 
-def jpeg_scan(u8, quality=90, mcus_per_segment=None, subsampling="444"):
-    """(B,H,W,3) uint8 RGB device frames -> (scans (B, capacity) uint8, nbytes (B,) int32): scans[b, :nbytes[b]] is the entropy-coded scan of
-    frame b's baseline JPEG (4:4:4, restart interval ``mcus_per_segment`` MCUs, default min(ceil(W / 8), the largest); include/lwg_hip.h
-    lwg_jpeg_scan_u8; ``output.jpeg_from_scan`` wraps it into a file).  capacity is the worst case, several times the raw frame: copy
-    prefixes.  Bytes behind nbytes[b] are not written.  ``subsampling="420"``: lwg_jpeg420_scan_u8 - 16 x 16 MCUs of four Y blocks and one
-    Cb and Cr block each, the default interval min(ceil(W / 16), the largest); chroma detail is lost (noise-like colour almost entirely)."""
+def _jpeg_frames(u8, quality, mcus_per_segment, subsampling, what, scan):
+    """The argument checks in front of the jpeg entry points -> (entry prefix, quantiser bytes, B, H, W, interval)."""
     entry = _jpeg_entries(subsampling)
     if not u8.is_cuda:
-        raise RuntimeError("jpeg_scan needs a device tensor: there is no CPU fallback")
+        raise RuntimeError(what + " needs a device tensor: there is no CPU fallback")
     if u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
-        raise ValueError("jpeg_scan takes a (B,H,W,3) uint8 tensor")
+        raise ValueError(what + " takes a (B,H,W,3) uint8 tensor")
     from .output import jpeg_tables
     luma, chroma = jpeg_tables(quality)
     B, H, W, _ = u8.shape
@@ -1421,18 +1417,67 @@ def jpeg_scan(u8, quality=90, mcus_per_segment=None, subsampling="444"):
     most = getattr(lib, entry + "_max_mcus_per_segment")()
     side = jpeg_mcu_size(subsampling)
     ri = int(mcus_per_segment) if mcus_per_segment is not None else min((W + side - 1) // side, most)
-    cap = getattr(lib, entry + "_scan_capacity")(H, W, ri)
-    nws = getattr(lib, entry + "_scan_ws_bytes")(max(B, 1), H, W, ri)
+    cap = getattr(lib, entry + scan + "_capacity")(H, W, ri)
+    nws = getattr(lib, entry + scan + "_ws_bytes")(max(B, 1), H, W, ri)
     if cap == 0 or nws == 0:
-        raise ValueError(f"jpeg_scan: no encoding for {B} frames of {H} x {W} in segments of {ri} MCUs (1 .. {most})")
+        raise ValueError(f"{what}: no encoding for {B} frames of {H} x {W} in segments of {ri} MCUs (1 .. {most})")
+    return entry, bytes(luma) + bytes(chroma), B, H, W, ri, cap, nws
+
+
+def jpeg_scan(u8, quality=90, mcus_per_segment=None, subsampling="444", huffman="fixed"):
+    """(B,H,W,3) uint8 RGB device frames -> (scans (B, capacity) uint8, nbytes (B,) int32): scans[b, :nbytes[b]] is the entropy-coded scan of
+    frame b's baseline JPEG (4:4:4, restart interval ``mcus_per_segment`` MCUs, default min(ceil(W / 8), the largest); include/lwg_hip.h
+    lwg_jpeg_scan_u8; ``output.jpeg_from_scan`` wraps it into a file).  capacity is the worst case, several times the raw frame: copy
+    prefixes.  Bytes behind nbytes[b] are not written.  ``subsampling="420"``: lwg_jpeg420_scan_u8 - 16 x 16 MCUs of four Y blocks and one
+    Cb and Cr block each, the default interval min(ceil(W / 16), the largest); chroma detail is lost (noise-like colour almost entirely).
+    ``huffman="optimized"``: lwg_jpeg_scan_opt_u8 / lwg_jpeg420_scan_opt_u8 - every frame is coded with Huffman tables built from its own
+    symbol counts; -> (scans, nbytes, tables (B, 4, 272) uint8: per table, in DHT order, 16 counts per length and 256 symbol slots), which
+    ``output.jpeg_from_scan(tables=...)`` takes.  The decoded pixels are those of the fixed-table scan."""
+    from .output import jpeg_check_huffman
+    opt = jpeg_check_huffman(huffman) == "optimized"
+    scan = "_scan_opt" if opt else "_scan"
+    entry, qtab, B, H, W, ri, cap, nws = _jpeg_frames(u8, quality, mcus_per_segment, subsampling, "jpeg_scan", scan)
     scans = torch.empty(B, cap, device=u8.device, dtype=torch.uint8)
     nbytes = torch.empty(B, device=u8.device, dtype=torch.int32)
-    if B == 0:
-        return scans, nbytes
-    ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
-    _lib.check(getattr(lib, entry + "_scan_u8")(_ptr(u8.contiguous(), torch.uint8), B, H, W, bytes(luma) + bytes(chroma), ri, _ptr(ws, torch.uint8),
-                                                _ptr(scans, torch.uint8), _ptr(nbytes, torch.int32), _stream()), entry + "_scan_u8")
-    return scans, nbytes
+    tables = torch.empty(B, 4, 272, device=u8.device, dtype=torch.uint8) if opt else None
+    if B:
+        ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
+        args = (_ptr(u8.contiguous(), torch.uint8), B, H, W, qtab, ri, _ptr(ws, torch.uint8), _ptr(scans, torch.uint8), _ptr(nbytes, torch.int32))
+        if opt:
+            args += (_ptr(tables, torch.uint8),)
+        _lib.check(getattr(_lib.lib(), entry + scan + "_u8")(*args, _stream()), entry + scan + "_u8")
+    return (scans, nbytes, tables) if opt else (scans, nbytes)
+
+
+def jpeg_symbol_histogram(u8, quality=90, mcus_per_segment=None, subsampling="444"):
+    """(B,H,W,3) uint8 RGB device frames -> (B, 4, 256) int32 (the bits of the uint32 counts): how often frame b's scan codes every symbol of
+    its DC luminance, AC luminance, DC chrominance and AC chrominance table - the first step of ``jpeg_scan(huffman="optimized")`` alone
+    (include/lwg_hip.h lwg_jpeg_hist_u8, lwg_jpeg420_hist_u8; tests/jpeghuff_emu.py ``histogram``)."""
+    entry, qtab, B, H, W, ri, _, nws = _jpeg_frames(u8, quality, mcus_per_segment, subsampling, "jpeg_symbol_histogram", "_scan_opt")
+    hist = torch.empty(B, 4, 256, device=u8.device, dtype=torch.int32)
+    if B:
+        ws = torch.empty(nws, device=u8.device, dtype=torch.uint8)
+        name = entry + "_hist_u8"
+        _lib.check(getattr(_lib.lib(), name)(_ptr(u8.contiguous(), torch.uint8), B, H, W, qtab, ri, _ptr(ws, torch.uint8), _ptr(hist, torch.int32),
+                                             _stream()), name)
+    return hist
+
+
+def jpeg_huffman_tables(hist):
+    """(B, 4, 256) int32 device counts (read as uint32) -> (tables (B, 4, 272) uint8, codes (B, 544) int32): the second step of
+    ``jpeg_scan(huffman="optimized")`` alone (include/lwg_hip.h lwg_jpeg_huff_tables; tests/jpeghuff_emu.py ``table``, ``dht`` and
+    ``coder_words``).  Any counts are taken; a DC table's symbols from 16 on have no place in ``codes``."""
+    if not hist.is_cuda:
+        raise RuntimeError("jpeg_huffman_tables needs a device tensor: there is no CPU fallback")
+    if hist.dtype != torch.int32 or hist.dim() != 3 or tuple(hist.shape[1:]) != (4, 256):
+        raise ValueError("jpeg_huffman_tables takes a (B,4,256) int32 tensor")
+    B = hist.shape[0]
+    tables = torch.empty(B, 4, 272, device=hist.device, dtype=torch.uint8)
+    codes = torch.empty(B, 544, device=hist.device, dtype=torch.int32)
+    if B:
+        _lib.check(_lib.lib().lwg_jpeg_huff_tables(_ptr(hist.contiguous(), torch.int32), B, _ptr(tables, torch.uint8), _ptr(codes, torch.int32),
+                                                   _stream()), "lwg_jpeg_huff_tables")
+    return tables, codes
 
 
 def png_rows_per_segment(H, W, most=16):

@@ -22,7 +22,9 @@ PCIe (the lengths first, then - from the helper thread that waits for them - the
 the constant headers in front (``jpeg_from_scan``).  ``"jpeg"`` writes ``"{prefix}{t:0>8}.jpg"`` files, ``"mjpeg"`` ONE Motion-JPEG AVI file
 (``MjpegAviWriter``: the container is ``struct.pack`` on the host, no codec library).  ``subsampling="420"`` (opt-in; ``opt.jpeg_subsampling``)
 codes 16 x 16 MCUs with the chroma at half resolution instead (``lwg_jpeg420_scan_u8``): about half the bytes and the format players expect, at
-the price of chroma detail - nearly all of it on noise-like frames.
+the price of chroma detail - nearly all of it on noise-like frames.  ``huffman="optimized"`` (opt-in; ``opt.jpeg_huffman``) codes every frame
+with Huffman tables built on the device from its own symbol counts (``lwg_jpeg_scan_opt_u8``, ``lwg_jpeg420_scan_opt_u8``): the same decoded
+pixels in fewer bytes, for two more launches per batch; the tables cross PCIe with the lengths and the worker writes them into the frame's DHT.
 
 ``FrameWriter(fuse=FuseSpec(panel, ...))`` (opt-in; ``opt.fuse_output`` of the runners) hands the encoders the reference's comparison canvas
 instead of the bare frame: ``lwg_fuse_canvas_u8`` composes [source panel | pad | reference frame | pad | frame ...] (fuse_src_ref_multi_outputs,
@@ -125,11 +127,19 @@ def jpeg_check_subsampling(subsampling):
     return subsampling
 
 
+JPEG_HUFFMAN = ("fixed", "optimized")  # the device encoder's Huffman tables: Annex K's, or per-frame ones; "fixed" is the default everywhere
+_JPEG_TC_TH = (0x00, 0x10, 0x01, 0x11)  # the order of a frame's tables: DC luminance, AC luminance, DC chrominance, AC chrominance
+
+
+def jpeg_check_huffman(huffman):
+    if huffman not in JPEG_HUFFMAN:
+        raise ValueError("jpeg huffman must be 'fixed' or 'optimized', not %r" % (huffman,))
+    return huffman
+
+
 @functools.lru_cache(maxsize=64)
-def jpeg_headers(w, h, quality, mcus_per_segment, subsampling="444"):
-    """Everything in front of the scan - SOI, APP0 JFIF, two DQT, SOF0 (8 bit, h x w, three components; Y 1x1, with ``subsampling="420"``
-    2x2), four DHT, DRI, SOS: constant per (w, h, quality, restart interval, subsampling), built once."""
-    w, h, ri = int(w), int(h), int(mcus_per_segment)
+def _jpeg_header_parts(w, h, quality, ri, subsampling):
+    """-> (the bytes in front of the four DHT segments, the fixed DHT segments, the bytes behind them)."""
     if not (0 < w <= 65535 and 0 < h <= 65535 and 0 < ri <= 65535):
         raise ValueError("jpeg: sizes and the restart interval are 16-bit fields")
     y_sampling = _JPEG_Y_SAMPLING[jpeg_check_subsampling(subsampling)]
@@ -137,17 +147,29 @@ def jpeg_headers(w, h, quality, mcus_per_segment, subsampling="444"):
     for tq, table in enumerate(jpeg_tables(quality)):
         out.append(_jpeg_marker(0xDB, bytes([tq]) + bytes(table[k] for k in _JPEG_ZIGZAG)))
     out.append(_jpeg_marker(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, y_sampling, 0, 2, 0x11, 1, 3, 0x11, 1])))
-    for tc_th, bits, vals in _JPEG_DHT:
-        out.append(_jpeg_marker(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals)))
-    out.append(_jpeg_marker(0xDD, struct.pack(">H", ri)))
-    out.append(_jpeg_marker(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
-    return b"".join(out)
+    dht = b"".join(_jpeg_marker(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals)) for tc_th, bits, vals in _JPEG_DHT)
+    back = _jpeg_marker(0xDD, struct.pack(">H", ri)) + _jpeg_marker(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    return b"".join(out), dht, back
 
 
-def jpeg_from_scan(scan, w, h, quality, mcus_per_segment, subsampling="444"):
+def jpeg_headers(w, h, quality, mcus_per_segment, subsampling="444", tables=None):
+    """Everything in front of the scan - SOI, APP0 JFIF, two DQT, SOF0 (8 bit, h x w, three components; Y 1x1, with ``subsampling="420"``
+    2x2), four DHT, DRI, SOS: constant per (w, h, quality, restart interval, subsampling), built once.  ``tables``: the frame's own Huffman
+    tables as ``ops.jpeg_scan(huffman="optimized")`` returns them - (4, 272) uint8, per table 16 counts and 256 symbol slots - go into the
+    four DHT segments instead of the Annex K ones."""
+    front, dht, back = _jpeg_header_parts(int(w), int(h), quality, int(mcus_per_segment), subsampling)
+    if tables is not None:
+        t = np.asarray(tables)
+        if t.dtype != np.uint8 or t.shape != (4, 272):
+            raise ValueError("jpeg: a frame's tables are (4, 272) uint8")
+        dht = b"".join(_jpeg_marker(0xC4, bytes([tc_th]) + row[:16 + int(row[:16].sum(dtype=np.int64))].tobytes()) for tc_th, row in zip(_JPEG_TC_TH, t))
+    return front + dht + back
+
+
+def jpeg_from_scan(scan, w, h, quality, mcus_per_segment, subsampling="444", tables=None):
     """The entropy-coded scan of a (h, w) frame (``ops.jpeg_scan`` with the same ``subsampling``: bytes, or a uint8 array) -> the bytes of the
-    JFIF file: the headers, the scan, EOI.  The host's share of the device encoder: one concatenation."""
-    return jpeg_headers(int(w), int(h), int(quality), int(mcus_per_segment), subsampling) + bytes(scan) + b"\xff\xd9"
+    JFIF file: the headers, the scan, EOI.  The host's share of the device encoder: one concatenation.  ``tables``: as for ``jpeg_headers``."""
+    return jpeg_headers(int(w), int(h), int(quality), int(mcus_per_segment), subsampling, tables) + bytes(scan) + b"\xff\xd9"
 
 
 class MjpegAviWriter(object):
@@ -341,8 +363,9 @@ class FrameWriter(object):
                                 # producer waits for the per-file form (GPU side 1 069 against 1 165 frames/s, profiles/jpeg_device_ab*.txt)
 
     def __init__(self, output_dir, prefix="pred_", workers=None, ring=None, compress_level=1, encoder="host", quality=90, fps=25, fuse=None,
-                 video_name="video.avi", subsampling="444"):
+                 video_name="video.avi", subsampling="444", huffman="fixed"):
         self.subsampling = jpeg_check_subsampling(subsampling)    # encoder="jpeg" | "mjpeg": the chroma format of the device encoder (the PNG encoders ignore it)
+        self.huffman = jpeg_check_huffman(huffman)                # encoder="jpeg" | "mjpeg": "optimized" codes every frame with tables of its own (the PNG encoders ignore it)
         if fuse is not None and not isinstance(fuse, FuseSpec):
             raise TypeError("fuse must be a FuseSpec or None")
         self.fuse, self.video_name = fuse, str(video_name)
@@ -393,7 +416,8 @@ class FrameWriter(object):
                     if batch["error"] is not None:
                         raise batch["error"]
                     a, n = batch["offs"][i], int(batch["nbytes"][i])
-                    data = jpeg_from_scan(batch["host"].numpy()[a:a + n], batch["w"], batch["h"], self.quality, batch["ri"], self.subsampling)
+                    tables = None if batch["tables"] is None else batch["tables"].numpy()[i]
+                    data = jpeg_from_scan(batch["host"].numpy()[a:a + n], batch["w"], batch["h"], self.quality, batch["ri"], self.subsampling, tables)
                     if self._avi is not None:
                         path = self._avi.path
                         self._avi.add(t - self._t_first, data)
@@ -521,7 +545,12 @@ class FrameWriter(object):
             H, W = u8.shape[1], u8.shape[2]
             side = ops.jpeg_mcu_size(self.subsampling)
             ri = min((W + side - 1) // side, ops.jpeg_max_mcus_per_segment(self.subsampling))
-            scans, nbytes = ops.jpeg_scan(u8, self.quality, ri, self.subsampling)
+            tables = tables_host = None
+            if self.huffman == "fixed":
+                scans, nbytes = ops.jpeg_scan(u8, self.quality, ri, self.subsampling)
+            else:                                          # the frames' tables ride with the lengths in the first, small copy
+                scans, nbytes, tables = ops.jpeg_scan(u8, self.quality, ri, self.subsampling, self.huffman)
+                tables_host = torch.empty(tuple(tables.shape), dtype=torch.uint8, pin_memory=True)
             nbytes_host = torch.empty(B, dtype=torch.int32, pin_memory=True)
             if self._copy_stream is None:
                 self._copy_stream = torch.cuda.Stream(device=pred.device)
@@ -533,15 +562,19 @@ class FrameWriter(object):
             with torch.cuda.stream(self._copy_stream):
                 self._copy_stream.wait_event(produced)
                 nbytes_host.copy_(nbytes, non_blocking=True)
+                if tables is not None:
+                    tables_host.copy_(tables, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record(self._copy_stream)
             nbytes.record_stream(self._copy_stream)
             scans.record_stream(self._copy_stream)
+            if tables is not None:
+                tables.record_stream(self._copy_stream)
         except Exception:
             self._slots.release()
             raise
         batch = {"host": None, "offs": None, "t0": int(t0), "left": B, "ready": threading.Event(), "nbytes": nbytes_host, "h": H, "w": W, "ri": ri,
-                 "error": None}
+                 "error": None, "tables": tables_host}
         with self._cv:
             self._submitted += B
         threading.Thread(target=self._wait_coded, args=(batch, event, scans), daemon=True).start()
